@@ -29,8 +29,11 @@ Workloads (BASELINE.json):
   cfg3     Rayleigh+Love x phase+group, 10 layers, 40 periods, 8192 models
   cfg4     Rayleigh phase (21) + P-RF, 15 layers, 64 models per GPU
   cfg5     ragged 2..31 layers, Rayleigh phase (21) + P-RF
-The default run times the headline and then each of cfg2..cfg5 for a bounded number of steps
-(`configs` in the line: value, ms_per_step, kernel form, roofline, cpu_baseline per config).
+A plain run sets up, warms up, times --steps steps of the workload and prints the line (metric, value, unit,
+ms_per_step, ...); with --dump-outputs DIR it first writes what the last timed step computed.  `--full` adds
+what takes runs of its own: the per-kernel durations and rooflines, the CPU baseline, cfg2..cfg5 for a
+bounded number of steps after the headline (`configs` in the line: value, ms_per_step, kernel form,
+roofline, cpu_baseline per config) and the chain-pool legs.
 """
 import argparse
 import json
@@ -59,6 +62,9 @@ WORKLOADS = {
 CONFIG_ORDER = ['cfg2', 'cfg3', 'cfg4', 'cfg5']
 REF_TAGS = {'rdispgr': (2, 1), 'ldispgr': (1, 1), 'rdispph': (2, 0), 'ldispph': (1, 0)}
 RF_NSAMP, RF_NOUT = 512, 201
+# --dump-outputs: at most this many models' output rows (a fixed, seeded sample of a larger batch), i.e. at most
+# 16 384 x 222 doubles = 29 MB for the headline
+DUMP_ROWS, DUMP_SEED = 16384, 7
 
 
 def make_models(wl, B, rank):
@@ -466,11 +472,30 @@ class Ranks(object):
         return [float(p.item()) for p in parts]
 
 
-def run_workload(name, B, rank, ranks, steps, warmup, serial=False, budget_s=None):
-    """Upload one batch of `name`, time `steps` passes (or, with budget_s, as many as fit that many
-    seconds after a probe), then the per-kernel durations with events on the launch stream."""
+def dump_outputs(directory, eng, out, err):
+    """--dump-outputs: what the timed path handed its caller after the last step, for a fixed, seeded sample of
+    DUMP_ROWS models of the batch (all of them in a smaller batch), as DIR/<name>.npy: `swd_<ref>` / `rf_<ref>`
+    float64 [n, values of that target] (the target's columns of `out`), `err` float32 [n, dispersion targets]
+    (the error flags) and `rows` float64 [n] (the models' indices in the batch)."""
     import torch
-    from bayhunter_amd import _lib as bhlib
+    B = out.shape[0]
+    rows = np.arange(B) if B <= DUMP_ROWS else \
+        np.sort(np.random.RandomState(DUMP_SEED).choice(B, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(out.device)
+    vals = out.index_select(0, idx).cpu().numpy()
+    arrays = {'rows': rows.astype(np.float64), 'err': err.index_select(0, idx).cpu().numpy().astype(np.float32)}
+    for kind, spec, sl in zip(['swd'] * len(eng.swd) + ['rf'] * len(eng.rf), list(eng.swd) + list(eng.rf), eng.slices):
+        arrays['%s_%s' % (kind, spec.ref)] = np.ascontiguousarray(vals[:, sl], dtype=np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
+def run_workload(name, B, rank, ranks, steps, warmup, serial=False, budget_s=None, kernels=False, dump=None):
+    """Upload one batch of `name`, time `steps` passes (or, with budget_s, as many as fit that many
+    seconds after a probe), write the last step's outputs to `dump` if given, then -- with `kernels` --
+    the per-kernel durations with events on the launch stream."""
+    import torch
     from bayhunter_amd.engine import ForwardEngine, RfSpec, SwdSpec
     wl = WORKLOADS[name]
     per = np.linspace(1, 41, wl['P'])
@@ -478,12 +503,6 @@ def run_workload(name, B, rank, ranks, steps, warmup, serial=False, budget_s=Non
     swd_specs = [SwdSpec(r, per) for r in wl['refs']]
     rf_specs = [RfSpec('prf', np.linspace(-5, 35, RF_NOUT))] if wl['rf'] else []
     eng = ForwardEngine(swd=swd_specs, rf=rf_specs)               # the product path: one engine
-    eng_only_swd = ForwardEngine(swd=swd_specs)                     # per-kernel timing only
-    eng_only_rf = ForwardEngine(rf=rf_specs) if rf_specs else None
-    if eng_only_rf:                                                 # same output row layout
-        eng_only_rf._rfp[0].out_off = eng._rfp[0].out_off
-        eng_only_rf.row = eng.row
-    eng_only_swd.row = eng.row
     dmodels = eng.upload(H, VP, VS, RHO, nl)                       # inputs resident in HBM
     out, err = eng.alloc_out(B)
     if serial:
@@ -514,11 +533,30 @@ def run_workload(name, B, rank, ranks, steps, warmup, serial=False, budget_s=Non
     ranks.barrier()
     torch.cuda.synchronize()
     dt = ranks.max(time.perf_counter() - t0)
-    form = bhlib.load().bh_swd_last_form()
+    res = dict(name=name, B=B, steps=steps, dt=dt, dt_local=dt_local, nerr=int(err.sum().item()))
+    if dump is not None:
+        dump_outputs(dump, eng, out, err)
+    if kernels:
+        res.update(kernel_times(eng, swd_specs, rf_specs, dmodels, out, err, steps))
+    return res
+
+
+def kernel_times(eng, swd_specs, rf_specs, dmodels, out, err, steps):
+    """The kernel forms the timed steps ran and the per-kernel durations for the rooflines (--full)."""
     import ctypes
+    import torch
+    from bayhunter_amd import _lib as bhlib
+    from bayhunter_amd.engine import ForwardEngine
+    form = bhlib.load().bh_swd_last_form()
     fl = (ctypes.c_int * len(swd_specs))()
     bhlib.check(bhlib.load().bh_swd_last_forms(fl, len(swd_specs)))
-    forms = {r: int(f) for r, f in zip(wl['refs'], fl)}      # per target: a call may use one form per target
+    forms = {sp.ref: int(f) for sp, f in zip(swd_specs, fl)}      # per target: a call may use one form per target
+    eng_only_swd = ForwardEngine(swd=swd_specs)                     # per-kernel timing only
+    eng_only_rf = ForwardEngine(rf=rf_specs) if rf_specs else None
+    if eng_only_rf:                                                 # same output row layout
+        eng_only_rf._rfp[0].out_off = eng._rfp[0].out_off
+        eng_only_rf.row = eng.row
+    eng_only_swd.row = eng.row
 
     # per-kernel durations for the roofline: the same launches, serialised on one stream, bracketed
     # by events on that stream (in the timed steps above rf_kernel overlaps the tail of swd_kernel)
@@ -539,8 +577,7 @@ def run_workload(name, B, rank, ranks, steps, warmup, serial=False, budget_s=Non
     ms_swd = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
     ms_rf = float(np.mean([e[1].elapsed_time(e[2]) for e in ev])) if eng_only_rf else 0.0
     nact = int(bhlib.load().bh_rf_active_frequencies(eng._rfp[0])) if eng_only_rf else 0
-    return dict(name=name, B=B, steps=steps, dt=dt, dt_local=dt_local, ms_swd=ms_swd, ms_rf=ms_rf,
-                nerr=int(err.sum().item()), form=form, forms=forms, nact=nact)
+    return dict(ms_swd=ms_swd, ms_rf=ms_rf, form=form, forms=forms, nact=nact)
 
 
 def kernel_symbol(form):
@@ -615,11 +652,16 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--workload', default='joint10', choices=sorted(WORKLOADS))
     ap.add_argument('--batch', type=int, default=None, help='models per GPU per step')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also the per-kernel durations and rooflines, the CPU baseline, cfg2..cfg5 after the headline '
+                         'and the chain-pool legs (a plain run times the workload alone)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-baseline-only', default=None, metavar='WORKLOADS',
                     help='(internal) comma separated workload=seconds list; prints a JSON dict')
-    ap.add_argument('--no-chain-pool', action='store_true')
-    ap.add_argument('--no-configs', action='store_true', help='skip the cfg2..cfg5 lines after the headline')
+    ap.add_argument('--no-chain-pool', action='store_true', help='with --full: skip the chain-pool legs')
+    ap.add_argument('--no-configs', action='store_true', help='with --full: skip the cfg2..cfg5 lines after the headline')
     ap.add_argument('--probe-ranks', action='store_true',
                     help='(test hook) rendezvous only, on the CPU over gloo: prints who showed up, no GPU work')
     ap.add_argument('--serial', action='store_true',
@@ -627,6 +669,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.cpu_baseline_only:
         res = {}
@@ -666,11 +710,12 @@ def main():
                              "launcher": os.environ.get('BH_BENCH_LAUNCHER', 'external' if world > 1 else None)}))
         return
     headline = args.workload == 'joint10' and args.batch is None
-    with_configs = headline and not args.no_configs
+    with_configs = headline and args.full and not args.no_configs
+    with_chain_pool = headline and args.full and not args.no_chain_pool
 
-    # CPU baseline first, in a child that never initialises the GPU (rank 0, N=1 only)
+    # CPU baseline first (--full), in a child that never initialises the GPU (rank 0, N=1 only)
     cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         want = ['%s=%g' % (args.workload, 22.0)]      # >= 10 s of solver time per core on the box's CPU
         if with_configs:
             want += ['%s=%g' % (c, 4.0) for c in CONFIG_ORDER]
@@ -732,29 +777,24 @@ def main():
         sys.exit('bench.py: %d ranks on %d distinct devices' % (world, devices_seen))
 
     B = args.batch or WORKLOADS[args.workload]['B']
-    head = run_workload(args.workload, B, rank, ranks, args.steps, args.warmup, serial=args.serial)
+    head = run_workload(args.workload, B, rank, ranks, args.steps, args.warmup, serial=args.serial, kernels=args.full,
+                        dump=args.dump_outputs if rank == 0 else None)
     per_rank_ms = [t / args.steps * 1e3 for t in ranks.all_floats(head['dt_local'])]
     cfg_runs = []
     if with_configs:
         for c in CONFIG_ORDER:
-            cfg_runs.append(run_workload(c, WORKLOADS[c]['B'], rank, ranks, 0, 3, serial=args.serial, budget_s=0.6))
+            cfg_runs.append(run_workload(c, WORKLOADS[c]['B'], rank, ranks, 0, 3, serial=args.serial, budget_s=0.6,
+                                         kernels=True))
 
     # N > 1 (or the one-rank rehearsal of its code): the sharded sampler and the gather of its sample blocks --
     # collectives, so every rank takes part
     sharded = None
-    if use_dist and headline and not args.no_chain_pool:
+    if use_dist and with_chain_pool:
         sharded = sharded_chain_pools(rank, world, ranks, backend)
 
     exit_code = 0
     if rank == 0:
-        lib_hash = bhlib.loaded_hash()
-        dom, swd, rf, flop_eval = rooflines(head, lib_hash)
         value = world * B * args.steps / head['dt']
-        dom = dict(dom, flop_per_eval_reference_path=flop_eval,
-                   note="achieved = reference-path flops / kernel time, timed live with events on the launch "
-                        "stream; traffic and the *_pmc fields come from the committed rocprofv3 --pmc passes and "
-                        "are null unless that profile was taken with this very library and its kernel time "
-                        "matches this run's")
         res = {
             "metric": "forward evals/sec (SWD+RF, 10-layer)" if args.workload == 'joint10'
                       else "forward evals/sec (%s)" % args.workload,
@@ -769,15 +809,23 @@ def main():
                        "models_per_gpu": B, "sharding": "models block-partitioned over ranks, no data-path collective",
                        "err_models": head['nerr'], "library": bhlib.load().bh_version().decode(),
                        "overlap": not args.serial},
+            "cpu_baseline": cpu.get(args.workload),
+        }
+        if args.full:
+            lib_hash = bhlib.loaded_hash()
+            dom, swd, rf, flop_eval = rooflines(head, lib_hash)
+            dom = dict(dom, flop_per_eval_reference_path=flop_eval,
+                       note="achieved = reference-path flops / kernel time, timed live with events on the launch "
+                            "stream; traffic and the *_pmc fields come from the committed rocprofv3 --pmc passes and "
+                            "are null unless that profile was taken with this very library and its kernel time "
+                            "matches this run's")
             # The dominant kernel is an fp64 scalar recurrence: FP64 vector issue is the roofline that
             # binds it, so that is the headline fraction; the HBM figure the contract asks
             # for is kept beside it.
-            "roofline": dom,
-            "roofline_rf": rf,
-            "kernels_ms": {"swd_kernel": head['ms_swd'], "rf_kernel": head['ms_rf'],
-                           "note": "serialised; in the timed steps rf_kernel runs on a second stream, co-resident with swd_kernel (2 x 192 + 128 VGPRs per SIMD)"},
-            "cpu_baseline": cpu.get(args.workload),
-        }
+            res["roofline"] = dom
+            res["roofline_rf"] = rf
+            res["kernels_ms"] = {"swd_kernel": head['ms_swd'], "rf_kernel": head['ms_rf'],
+                                 "note": "serialised; in the timed steps rf_kernel runs on a second stream, co-resident with swd_kernel (2 x 192 + 128 VGPRs per SIMD)"}
         if cfg_runs:
             cfgs = {}
             for r in cfg_runs:
@@ -797,7 +845,7 @@ def main():
         if sharded is not None:
             res["chain_pool_sharded"], res["gather"] = sharded
         failed_legs = []
-        if world == 1 and not use_dist and headline and not args.no_chain_pool:
+        if world == 1 and not use_dist and with_chain_pool:
             # A failing leg must be seen: the line is still emitted (it carries the error) and the process then exits
             # non-zero -- after a library error the state of the process is unknown, the run is not a healthy one.
             try:

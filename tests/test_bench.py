@@ -3,8 +3,9 @@
 CPU tier: the launcher (a parent that never touches torch or the GPU starts N fresh rank processes)
 and the refusal of a process group whose size is not --gpus, through the rendezvous-only probe.
 GPU tier: two ranks sharing the one GPU of the box over gloo (rehearsal of the N>1 path: barrier, MAX
-over ranks, gather of the ranks' devices), the refusal to stack RCCL ranks on one device, and the
-shape of the N=1 line (roofline for both kernels, the BASELINE configs)."""
+over ranks, gather of the ranks' devices), the refusal to stack RCCL ranks on one device, the lean
+plain line and its output dump, and the shape of the --full N=1 line (roofline for both kernels, the
+BASELINE configs)."""
 import json
 import os
 import subprocess
@@ -68,6 +69,48 @@ def test_parent_of_the_ranks_never_imports_torch():
     assert 'import torch' not in head and 'bayhunter_amd' not in head.split('"""', 2)[2]
 
 
+def test_steps_must_be_at_least_one():
+    r = _run(['--steps', '0', '--probe-ranks'])
+    assert r.returncode == 2 and '--steps must be >= 1' in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_dumps_what_the_path_computed(tmp_path):
+    """A plain run times the workload and nothing else: no per-kernel passes, CPU baseline, configs or chain pools.
+    --dump-outputs writes the last timed step's outputs: the same for two runs with the same arguments, and what
+    the engine returns for the same models."""
+    import numpy as np
+    args = ['--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4096']
+    d = _line(_run(args + ['--dump-outputs', str(tmp_path / 'a')]))
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0 and d['ok'] is True
+    assert abs(d['value'] - 4096 / (d['ms_per_step'] * 1e-3)) <= 1e-6 * d['value']
+    assert d['unit'] == 'evals/s' and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert d['cpu_baseline'] is None
+    for k in ('roofline', 'roofline_rf', 'kernels_ms', 'configs', 'chain_pool', 'chain_pool_sharded', 'gather'):
+        assert k not in d, k
+    _line(_run(args + ['--dump-outputs', str(tmp_path / 'b')]))
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['err.npy', 'rf_prf.npy', 'rows.npy', 'swd_rdispph.npy'] == sorted(os.listdir(tmp_path / 'b'))
+    got = {n[:-4]: np.load(str(tmp_path / 'a' / n)) for n in names}
+    for n in names:
+        assert np.array_equal(got[n[:-4]], np.load(str(tmp_path / 'b' / n)), equal_nan=True), n
+    assert got['swd_rdispph'].shape == (4096, 21) and got['rf_prf'].shape == (4096, 201) and got['err'].shape == (4096, 1)
+    assert all(got[k].dtype in (np.float32, np.float64) for k in got)
+    assert np.array_equal(got['rows'], np.arange(4096))
+    sys.path.insert(0, ROOT)
+    import bench
+    from bayhunter_amd.engine import ForwardEngine, RfSpec, SwdSpec
+    wl = bench.WORKLOADS['joint10']
+    H, VP, VS, RHO, nl = bench.make_models(wl, 4096, 0)
+    eng = ForwardEngine(swd=[SwdSpec('rdispph', np.linspace(1, 41, wl['P']))],
+                        rf=[RfSpec('prf', np.linspace(-5, 35, bench.RF_NOUT))])
+    out, err = eng.run(H, VP, VS, RHO, nl)
+    out, err = out.cpu().numpy(), err.cpu().numpy()
+    assert np.array_equal(got['swd_rdispph'], out[:, eng.slices[0]], equal_nan=True)
+    assert np.array_equal(got['rf_prf'], out[:, eng.slices[1]], equal_nan=True)
+    assert np.array_equal(got['err'], err.astype(np.float32))
+
+
 @pytest.mark.gpu
 def test_two_ranks_on_one_gpu_over_gloo():
     d = _line(_run(['--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '8192'],
@@ -103,7 +146,7 @@ def test_rccl_ranks_are_not_stacked_on_one_gpu():
 
 @pytest.mark.gpu
 def test_single_gpu_line_has_both_rooflines_and_the_configs():
-    d = _line(_run(['--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-chain-pool']))
+    d = _line(_run(['--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-chain-pool']))
     assert d['n_gpus'] == 1 and d['ranks_seen'] == 1 and d['metric'] == 'forward evals/sec (SWD+RF, 10-layer)'
     for k in ('roofline', 'roofline_rf'):
         rl = d[k]
@@ -117,10 +160,10 @@ def test_single_gpu_line_has_both_rooflines_and_the_configs():
 
 @pytest.mark.gpu
 def test_default_line_includes_a_healthy_chain_pool_leg():
-    """the chain-pool leg of the DEFAULT run (a warm-up pool and three 4 096-chain pools
+    """the chain-pool leg of the --full run (a warm-up pool and three 4 096-chain pools
     made and closed in a row) was never run by the suite -- both bench tests passed --no-chain-pool -- and the
     driver's run lost it to a HIP error that the line then hid behind rc 0."""
-    d = _line(_run(['--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-configs']))
+    d = _line(_run(['--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-configs']))
     cp = d['chain_pool']
     assert d['ok'] is True and cp['ok'] is True and cp['value'] > 1e5 and len(cp['samples']) == 3
     assert cp['nchains'] == 4096 and cp['models_evaluated'] > 0.5 * 4096 * 150 and 'error' not in cp
@@ -128,11 +171,12 @@ def test_default_line_includes_a_healthy_chain_pool_leg():
 
 @pytest.mark.gpu
 def test_a_failed_leg_is_in_the_line_and_in_the_exit_code():
-    r = _run(['--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-configs', '--batch', '8192', '--workload', 'joint10'],
-             env=dict(BH_BENCH_INJECT_FAILURE='chain_pool'))
+    r = _run(['--full', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-configs', '--batch', '8192',
+              '--workload', 'joint10'], env=dict(BH_BENCH_INJECT_FAILURE='chain_pool'))
     # (--batch makes it a non-headline run: no chain pool leg, nothing to fail)
     assert r.returncode == 0
-    r = _run(['--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-configs'], env=dict(BH_BENCH_INJECT_FAILURE='chain_pool'))
+    r = _run(['--full', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-configs'],
+             env=dict(BH_BENCH_INJECT_FAILURE='chain_pool'))
     d = _line(r, rc=1)
     assert d['ok'] is False and d['chain_pool']['ok'] is False and d['chain_pool']['value'] is None
     assert 'injected failure' in d['chain_pool']['error'] and 'failed legs: chain_pool' in r.stderr
@@ -146,8 +190,8 @@ def test_two_rank_line_has_the_sharded_sampler_and_the_gather():
     blocks gathered over the process group -- timed.  Rehearsed with two ranks sharing this box's GPU over gloo;
     the gathered chains are the chains ONE process produces for the same seeds."""
     import numpy as np
-    d = _line(_run(['--gpus', '2', '--steps', '1', '--warmup', '1', '--no-configs'], env=dict(BH_DIST_BACKEND='gloo'),
-                   timeout=900))
+    d = _line(_run(['--full', '--gpus', '2', '--steps', '1', '--warmup', '1', '--no-configs'],
+                   env=dict(BH_DIST_BACKEND='gloo'), timeout=900))
     assert d['n_gpus'] == 2 and d['ok'] is True and 'chain_pool' not in d
     sh, ga = d['chain_pool_sharded'], d['gather']
     assert sorted(sh) == sorted(ga) == ['cfg4', 'cfg5']
@@ -176,7 +220,7 @@ def test_two_rank_line_has_the_sharded_sampler_and_the_gather():
 
 @pytest.mark.gpu
 def test_sharded_sampler_and_gather_over_rccl_with_one_rank():
-    d = _line(_run(['--gpus', '1', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-configs'],
+    d = _line(_run(['--full', '--gpus', '1', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--no-configs'],
                    env=dict(BH_BENCH_FORCE_DIST='1')))
     assert d['dist_backend'] == 'nccl' and d['ok'] is True
     assert d['gather']['cfg5']['backend'] == 'nccl' and d['chain_pool_sharded']['cfg4']['nchains'] == 64

@@ -407,7 +407,7 @@ def test_team_and_lane_kernels_agree_bitwise(lib, oracle):
             assert np.array_equal(res['team'][1][:, 0], werr)
 
 
-def test_work_queue_path(lib, oracle):
+def test_work_queue_path(lib, oracle, tmp_path):
     """The persistent-lane work queue only engages above ~4e5 searches per call; force it with a
     tiny resident-wave budget (test hook BH_SWD_RESIDENT_WAVES) in a child process and compare with
     the oracle: every lane then runs many searches back to back, on ragged models."""
@@ -427,8 +427,7 @@ eng = ForwardEngine(swd=[SwdSpec('rdispph', per), SwdSpec('ldispgr', per)])
 out, err = eng.run(H, VP, VS, RHO, nl)
 np.savez(sys.argv[1], out=out.cpu().numpy(), err=err.cpu().numpy())
 """ % ROOT
-    path = os.path.join(ROOT, 'gpurun_out', 'queue_test.npz')
-    os.makedirs(os.path.dirname(path), exist_ok=True)
+    path = str(tmp_path / 'queue_test.npz')
     env = dict(os.environ, BH_SWD_RESIDENT_WAVES='6')      # 3 waves per target -> ~16 searches per lane
     subprocess.run([sys.executable, '-c', code, path], check=True, env=env)
     got = np.load(path)
@@ -661,7 +660,7 @@ def test_ragged_batch_is_reordered_transparently(lib, oracle):
     assert np.abs(out.cpu().numpy()[sl][ok][:, :11] - want[ok]).max() <= TOL_PHASE
 
 
-def test_more_launches_in_flight_than_queue_slots(lib, oracle):
+def test_more_launches_in_flight_than_queue_slots(lib, oracle, tmp_path):
     """The work-queue counters live in a ring of slots; a slot is re-used only after the launch that
     used it has finished (event per slot).  600 small launches on two streams with the ring shrunk to
     4 slots (BH_SWD_QUEUE_SLOTS, child process): every launch must still produce the oracle's rows
@@ -699,8 +698,7 @@ np.savez(sys.argv[1], bad=bad, **{'o%%d' %% i: ref[i][0] for i in range(6)}, **{
 """ % ROOT
     per = np.linspace(1, 41, 7)
     for kernel, waves in (('lane', '4'), ('team16', '')):
-        path = os.path.join(ROOT, 'gpurun_out', 'slots_test_%s.npz' % kernel)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
+        path = str(tmp_path / ('slots_test_%s.npz' % kernel))
         env = dict(os.environ, BH_SWD_QUEUE_SLOTS='4')
         if waves:
             env['BH_SWD_RESIDENT_WAVES'] = waves                      # the queue path of the lane kernel

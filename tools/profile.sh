@@ -15,8 +15,8 @@ if [ -n "$PROFILE_CMD" ]; then
   BENCH="$PROFILE_CMD"
   echo "${PROFILE_CMD//$R\//}" > $OUT/config.txt
 else
-  BENCH="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-chain-pool --no-configs --serial ${@:2}"
-  echo "bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-chain-pool --no-configs --serial ${@:2}" > $OUT/config.txt
+  BENCH="python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-chain-pool --no-configs --serial ${@:2}"
+  echo "bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-chain-pool --no-configs --serial ${@:2}" > $OUT/config.txt
 fi
 (cd $R && python3 -c "from bayhunter_amd import _lib; print(_lib.loaded_hash())") > $OUT/src_hash.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace.log 2>&1
