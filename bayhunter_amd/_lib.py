@@ -11,9 +11,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
-SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp"]
+SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h",
-           "swd_form_table.h"]
+           "swd_form_table.h", "posterior_core.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->
@@ -213,6 +213,11 @@ _SIGS = {
     "bh_stream_create": (C.c_int, [C.POINTER(_vp)]),
     "bh_stream_destroy": (C.c_int, [_vp]),
     "bh_rf_cached_tables": (C.c_int, []),
+    "bh_posterior_create": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, _vp, C.c_int,
+                                      _vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "bh_posterior_scan": (C.c_int, [_vp, C.POINTER(C.c_longlong), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)]),
+    "bh_posterior_finish": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "bh_posterior_destroy": (None, [_vp]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -535,6 +535,22 @@ class ChainPool(object):
                 lo += int(n)
         return out
 
+    def outliers(self, dev=0.05):
+        """PlotFromStorage.get_outliers (src/Plotting.py:113-154) on the likes save() writes: chains whose
+        median main-phase likelihood deviates from the best chain's by more than `dev` (relative).  Global
+        chain indices; chains without main-phase rows are not listed."""
+        from .posterior import pool_outliers
+        return pool_outliers(self, dev)
+
+    def posterior(self, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None):
+        """Velocity-depth posterior of the main phase on the device (posterior.summarize), no row expanded:
+        selection 'weighted' takes every main-phase iteration (the rows of weighted(i)[2]), 'saved' exactly the
+        rows save() writes, i.e. what PlotFromStorage reads.  Outlier chains (outliers(dev)) are left out unless
+        exclude_outliers=False.  The depth grid defaults to plot_posterior_models2d's arange(z0, z1 + depint,
+        depint) over the depth prior.  -> summarize()'s dict plus 'chains' (global indices used)."""
+        from .posterior import pool_posterior
+        return pool_posterior(self, dep_int, depint, dev, exclude_outliers, selection, device)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

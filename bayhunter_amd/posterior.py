@@ -1,0 +1,282 @@
+"""Velocity-depth posterior of a block of sampled models, on the device (include/bayhunter_amd.h, bh_posterior_*).
+
+What the reference computes after an inversion, from the rows of the main phase:
+
+    ModelMatrix.get_singlemodels(models, dep_int, misfits)   src/Models.py:160-226   mean, median, minmax,
+                                                                                    stdminmax, mode, minmisfit
+    PlotFromStorage._plot_bestmodels_hist(models, dep_int)   src/Plotting.py:462-536 the Vs-depth density and
+                                                                                    the interface-depth histogram
+    PlotFromStorage.plot_posterior_nlayers                   src/Plotting.py:607-625 the layer-count histogram
+
+Every row carries an integer weight (the iterations it stayed current); the result equals the reference's on
+the matrix in which each row is repeated `weight` times, without building that matrix.  Edge arrays are made
+here with numpy exactly as the reference makes them; the device bins by binary search over them.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+VS_INTERVAL = 0.025          # km/s: the reference's Vs bin width (Models.py:204, Plotting.py:495)
+
+
+def default_dep_int():
+    """get_singlemodels' default grid: 0.5 km steps to 100 km."""
+    return np.linspace(0, 100, 201)
+
+
+def models2d_dep_int(z, depint=1):
+    """The grid plot_posterior_models2d passes (Plotting.py:741-742): arange(z0, z1 + depint, depint)."""
+    return np.arange(z[0], z[1] + depint, depint)
+
+
+def hist_grids(dep_int=None):
+    """(half-step depth grid, depth bin edges) of _plot_bestmodels_hist (Plotting.py:470-480)."""
+    if dep_int is None:
+        return np.linspace(0, 100, 201), np.linspace(0, 100, 101)
+    dep_int = np.asarray(dep_int, dtype=np.float64)
+    maxdepth = int(np.ceil(dep_int.max()))
+    interp = dep_int[1] - dep_int[0]
+    return (np.arange(dep_int[0], dep_int[-1] + interp / 2., interp / 2.),
+            np.arange(0, maxdepth + 2 * interp, interp))
+
+
+def vs_round(vs):
+    """Plotting.py:29-33: rounds to the nearest 0.025 km/s."""
+    vs_floor = np.floor(vs)
+    return np.round((vs - vs_floor) * 40) / 40 + vs_floor
+
+
+def bin_index(values, edges):
+    """Bin of each value, -1 outside: edges[i] <= v < edges[i+1], the last bin closed (numpy's histogram rule)."""
+    values, edges = np.asarray(values, dtype=np.float64), np.asarray(edges, dtype=np.float64)
+    i = np.searchsorted(edges, values, side='right') - 1
+    i[values == edges[-1]] = edges.size - 2
+    i[(i < 0) | (i > edges.size - 2)] = -1
+    return i.astype(np.int32)
+
+
+def stepmodel(row):
+    """Model.get_stepmodel (Models.py:55-70) of one row: (vs_step, dep_step)."""
+    model = np.asarray(row, dtype=np.float64)
+    model = model[~np.isnan(model)]
+    n = int(model.size / 2)
+    vs, z = model[:n], model[-n:]
+    z_disc = (z[:n - 1] + z[1:n]) / 2.
+    h = np.concatenate((z_disc - np.concatenate(([0], z_disc[:-1])), [0]))
+    dep = np.cumsum(h)
+    dep = np.concatenate([(d, d) for d in dep])
+    dep_step = np.concatenate([[0], dep[:-1]])
+    vs_step = np.concatenate([(v, v) for v in vs])
+    dep_step[-1] = np.max([150, dep_step[-1] * 2.5])
+    return vs_step, dep_step
+
+
+def _torch_device(device):
+    import torch
+    if device is None:
+        return torch.device('cuda', torch.cuda.current_device())
+    if isinstance(device, int):
+        return torch.device('cuda', device)
+    return torch.device(device)
+
+
+class _Grid(object):
+    """One bh_posterior handle: the rows on one depth grid."""
+
+    def __init__(self, rows, weights, misfits, dep, ifedges, stream):
+        self.lib = _lib.load()
+        self.dep = np.ascontiguousarray(dep, dtype=np.float64)
+        self.ifedges = None if ifedges is None else np.ascontiguousarray(ifedges, dtype=np.float64)
+        self.width = rows.shape[1]
+        self.h = C.c_void_p()
+        nif = 0 if self.ifedges is None else self.ifedges.size
+        _lib.check(self.lib.bh_posterior_create(
+            rows.data_ptr(), int(rows.dtype.itemsize == 8), rows.shape[0], rows.stride(0), self.width,
+            None if weights is None else weights.data_ptr(), None if misfits is None else misfits.data_ptr(),
+            self.dep.ctypes.data, self.dep.size, None if not nif else self.ifedges.ctypes.data, nif,
+            stream, C.byref(self.h)))
+
+    def scan(self):
+        D = self.dep.size
+        total, argmin = C.c_longlong(0), C.c_longlong(-1)
+        vmin, vmax, mean = np.zeros(D), np.zeros(D), np.zeros(D)
+        nlay = np.zeros(self.width // 2 + 1, dtype=np.int64)
+        ifh = np.zeros(max(0, (0 if self.ifedges is None else self.ifedges.size) - 1), dtype=np.int64)
+        _lib.check(self.lib.bh_posterior_scan(self.h, C.byref(total), vmin.ctypes.data, vmax.ctypes.data,
+                                              mean.ctypes.data, nlay.ctypes.data,
+                                              ifh.ctypes.data if ifh.size else None, C.byref(argmin)))
+        return dict(total=total.value, vmin=vmin, vmax=vmax, mean=mean, nlayers=nlay, ifhist=ifh, argmin=argmin.value)
+
+    def finish(self, vedges, dbin, ndbins, stats):
+        D = self.dep.size
+        vedges = np.ascontiguousarray(vedges, dtype=np.float64)
+        dbin = np.ascontiguousarray(dbin, dtype=np.int32)
+        hist = np.zeros((ndbins, vedges.size - 1), dtype=np.int64)
+        std, median = (np.zeros(D), np.zeros(D)) if stats else (None, None)
+        _lib.check(self.lib.bh_posterior_finish(self.h, vedges.ctypes.data, vedges.size, dbin.ctypes.data, ndbins,
+                                                hist.ctypes.data, None if std is None else std.ctypes.data,
+                                                None if median is None else median.ctypes.data))
+        return hist, std, median
+
+    def close(self):
+        if self.h:
+            self.lib.bh_posterior_destroy(self.h)
+            self.h = C.c_void_p()
+
+
+def _to_device(a, dtype, dev):
+    import torch
+    if isinstance(a, torch.Tensor):
+        t = a.to(device=dev, dtype=dtype)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
+    return t if t.dim() < 2 or t.stride(1) == 1 else t.contiguous()
+
+
+def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, device=None):
+    """Posterior statistics of `models` ([rows, 2*maxlayers], reference layout, float32 or float64; numpy or
+    a torch tensor) with integer `weights` (>= 0, default 1 each).
+
+    dep_int   depth grid of get_singlemodels and _plot_bestmodels_hist (default: their own defaults).  With
+              `depint` and no dep_int: plot_posterior_models2d's grid arange(0, 100 + depint, depint).
+    misfits   one value per row: singlemodels['minmisfit'] is the step model of the first least misfit.
+
+    -> dict(singlemodels = get_singlemodels(models, dep_int, misfits),
+            hist2d       = (counts[vs bin, depth bin], vs edges, depth edges)  as np.histogram2d returns them,
+            interfaces   = (counts, depth edges)  of the interface depths,
+            nlayers      = counts by number of nuclei n (index n; plot_posterior_nlayers shows n - 1 layers),
+            nmodels      = the weighted number of models (the reference's "%d models"))
+    ValueError where the reference raises (all values equal: no mode bin) and for an empty selection."""
+    import torch
+    dev = _torch_device(device)
+    if not isinstance(models, torch.Tensor):
+        models = np.asarray(models)
+    if models.ndim != 2:
+        raise ValueError("models: [rows, 2*maxlayers]")
+    fdtype = torch.float32 if str(models.dtype).endswith('float32') else torch.float64
+    rows = _to_device(models, fdtype, dev)
+    if rows.shape[0] == 0:
+        raise ValueError("empty selection: no models")
+    w = None if weights is None else _to_device(weights, torch.int32, dev)
+    mf = None if misfits is None else _to_device(misfits, torch.float64, dev)
+    if w is not None and w.numel() != rows.shape[0] or mf is not None and mf.numel() != rows.shape[0]:
+        raise ValueError("one weight and one misfit per row")
+    hist_dep_int = dep_int
+    if dep_int is None and depint is not None:
+        dep_int = hist_dep_int = models2d_dep_int((0, 100), depint)
+    dep_int = default_dep_int() if dep_int is None else np.asarray(dep_int, dtype=np.float64)
+    dep2, depbins = hist_grids(hist_dep_int)
+    if dep_int.size < 2:
+        raise ValueError("dep_int: at least two depths (they are the mode histogram's depth edges)")
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        ga = _Grid(rows, w, mf, dep_int, depbins, stream)
+        gb = None
+        try:
+            s = ga.scan()
+            # (5) mode: int((max - min) / 0.025) Vs bins over linspace(min, max), depth edges dep_int
+            vmin, vmax = s['vmin'].min(), s['vmax'].max()
+            vsbins = int((vmax - vmin) / VS_INTERVAL)
+            if vsbins < 1:
+                raise ValueError("`bins[0]` must be positive, when an integer (all Vs values within 0.025 km/s)")
+            vedges = np.linspace(vmin, vmax, vsbins + 1)
+            mhist, std, median = ga.finish(vedges, bin_index(dep_int, dep_int), dep_int.size - 1, True)
+            # the density of _plot_bestmodels_hist on its half-step grid
+            gb = _Grid(rows, w, None, dep2, None, stream)
+            s2 = gb.scan()
+            vmin2, vmax2 = s2['vmin'].min(), s2['vmax'].max()
+            vsb = np.arange(vs_round(vmin2) - 2 * VS_INTERVAL, vs_round(vmax2) + 3 * VS_INTERVAL, VS_INTERVAL)
+            h2, _, _ = gb.finish(vsb, bin_index(dep2, depbins), depbins.size - 1, False)
+        finally:
+            ga.close()
+            if gb is not None:
+                gb.close()
+    mean = s['mean']
+    vs_center = (vedges[:-1] + vedges[1:]) / 2.
+    dep_center = (dep_int[:-1] + dep_int[1:]) / 2.
+    single = dict(mean=(mean, dep_int), median=(median, dep_int),
+                  minmax=(np.array((s['vmin'], s['vmax'])), dep_int),
+                  stdminmax=(np.array((mean - std, mean + std)), dep_int),
+                  mode=(vs_center[np.argmax(mhist, axis=1)], dep_center))
+    if mf is not None:
+        single['minmisfit'] = stepmodel(rows[s['argmin']].cpu().numpy())
+    return dict(singlemodels=single, hist2d=(h2.T.copy(), vsb, depbins), interfaces=(s['ifhist'], depbins),
+                nlayers=s['nlayers'], nmodels=s['total'])
+
+
+# ---- the chain pool's own sample block ------------------------------------------------------------------
+
+def pool_selection(pool, selection='weighted'):
+    """Main-phase rows of a pool without a per-chain loop -> (chain index [rows] (local), row index [rows],
+    weight [rows] int64).  'weighted': residence time, ChainPool.weighted (next row's iter, or iter_main, minus
+    this row's).  'saved': how many of the rows save() writes are this row -- a row spanning the expanded
+    range [a, a + w) of its chain contributes ceil((a + w) / t) - ceil(a / t) rows at thinning t."""
+    if selection not in ('weighted', 'saved'):
+        raise ValueError("selection: 'weighted' or 'saved'")
+    n = np.asarray(pool.counters()[0], dtype=np.int64)
+    it = pool.iter
+    with np.errstate(invalid='ignore'):
+        main = (np.arange(it.shape[1])[None, :] < n[:, None]) & (it >= 0)
+    ci, ri = np.nonzero(main)
+    if ci.size == 0:
+        return ci, ri, np.zeros(0, dtype=np.int64)
+    iv = it[ci, ri].astype(np.int64)
+    last = np.r_[ci[1:] != ci[:-1], True]
+    nxt = np.r_[iv[1:], 0]
+    nxt[last] = pool.iter_main
+    w = nxt - iv
+    if selection == 'saved':
+        first = np.r_[True, ci[1:] != ci[:-1]]
+        start = np.maximum.accumulate(np.where(first, np.arange(ci.size), 0))
+        a = iv - iv[start]
+        total = pool.iter_main - iv[start]
+        t = -(-total // int(pool.initparams['maxmodels']))
+        w = -(-(a + w) // t) - (-(-a // t))
+    return ci, ri, w
+
+
+def pool_outliers(pool, dev=0.05):
+    """PlotFromStorage.get_outliers (Plotting.py:113-154) on the likes save() writes: the median of each
+    chain's thinned main-phase likes against the best chain's -> global chain indices (sorted)."""
+    ci, ri, cnt = pool_selection(pool, 'saved')
+    if ci.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    likes = pool.likes[ci, ri]
+    order = np.lexsort((likes, ci))
+    cs, ls = cnt[order], likes[order]
+    cum = np.cumsum(cs)
+    chains = np.unique(ci)
+    tot = np.bincount(ci, weights=cnt, minlength=pool.nchains).astype(np.int64)[chains]
+    off = np.concatenate(([0], np.cumsum(tot)[:-1]))
+    pick = lambda r: ls[np.searchsorted(cum, off + r, side='right')]
+    lo, hi = pick((tot - 1) // 2), pick(tot // 2)
+    # np.median of float32: the middle value, or the float32 mean of the two middle ones
+    med = np.where(tot % 2 == 1, lo, (lo + hi) / np.float32(2)).astype(np.float32).astype(np.float64)
+    maxlike = np.max(med)
+    if maxlike > 0:
+        scores = med / maxlike
+    elif maxlike < 0:
+        scores = maxlike / med
+    else:
+        raise ValueError("best chain median likelihood is 0: outliers are undefined (Plotting.py:136-140)")
+    return (chains[(1 - scores) > dev] + pool.first).astype(np.int64)
+
+
+def pool_posterior(pool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None):
+    """ChainPool.posterior: summarize() over the pool's main-phase rows (see ChainPool.posterior)."""
+    ci, ri, w = pool_selection(pool, selection)
+    if exclude_outliers and ci.size:
+        out = pool_outliers(pool, dev) - pool.first
+        keep = ~np.isin(ci, out)
+        ci, ri, w = ci[keep], ri[keep], w[keep]
+    if ci.size == 0:
+        raise ValueError("empty selection: no main-phase rows")
+    if w.max() > np.iinfo(np.int32).max:
+        raise ValueError("a weight above 2^31 - 1")
+    if dep_int is None:
+        dep_int = models2d_dep_int(pool.priors['z'], depint)
+    res = summarize(pool.models[ci, ri], w.astype(np.int32), dep_int=dep_int, device=device)
+    res['chains'] = np.unique(ci) + pool.first
+    return res

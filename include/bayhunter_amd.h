@@ -423,6 +423,40 @@ int  bh_eval_wait(bh_eval_plan *plan, int *count);   /* blocks until the last su
  * argument with every submission. */
 int  bh_eval_set_concurrency(bh_eval_plan *plan, int plans_in_flight);
 
+/* ---- velocity-depth posterior of a block of sampled models ------------------------------- */
+/* The statistics the reference computes after an inversion (ModelMatrix.get_singlemodels, src/Models.py:160-226;
+ * PlotFromStorage._plot_bestmodels_hist, src/Plotting.py:462-536), on the device, over rows that each carry an
+ * integer weight: the result equals the reference's on the matrix in which every row is repeated `weight` times.
+ *
+ * rows      DEVICE [nrows][stride] float32 (fp64 = 0) or float64 (fp64 = 1), the layout [vs(n), z_vnoi(n), NaN...]
+ *           with width = 2 * maxlayers; rows that are all NaN are dropped
+ * weights   DEVICE int32 [nrows] >= 0, or NULL for all ones; a row of weight 0 is not part of the sample
+ * misfits   DEVICE float64 [nrows] or NULL: bh_posterior_scan reports the first row of the least misfit
+ * dep       HOST depth grid [ndep], strictly ascending; Vs is evaluated at these depths
+ * ifedges   HOST interface-depth histogram edges [nifedges] (ascending) or NULL / 0
+ * stream    the caller's (NULL: the null stream).  A stream handed in here follows the bh_stream_retire rules
+ *           below: retire it before destroying it.  Destroy the handle first.
+ * Histogram bins are edges[i] <= v < edges[i+1], the last one closed on the right (numpy's rule).
+ *
+ *   bh_posterior_create   uploads the grid; BH_ERR_ARG for a non-ascending grid or more than 2^32 rows
+ *   bh_posterior_scan     weighted count (BH_ERR_ARG if it is 0: an empty selection; or a weight is negative),
+ *                         per depth min / max / mean [ndep], counts of rows per number of nuclei [width/2 + 1],
+ *                         interface-depth histogram [nifedges - 1], the first argmin row of the misfits (-1: none)
+ *   bh_posterior_finish   after a scan: with vedges, the 2-D histogram hist[ndbins][nvedges - 1] of (depth bin
+ *                         dbin[d] of grid depth d, -1 = outside; Vs bin); std [ndep] (population) and the median
+ *                         [ndep] (mean of the two middle order statistics) when not NULL
+ * Every output is a HOST buffer; each call returns when its results are there.  Floating sums go through per-block
+ * partials reduced in a fixed order: two runs give bit-identical results. */
+typedef struct bh_posterior bh_posterior;
+int  bh_posterior_create(const void *rows, int fp64, long long nrows, long long stride, int width, const int *weights,
+                         const double *misfits, const double *dep, int ndep, const double *ifedges, int nifedges,
+                         void *stream, bh_posterior **post);
+int  bh_posterior_scan(bh_posterior *post, long long *total, double *vmin, double *vmax, double *mean,
+                       long long *nlayers, long long *ifhist, long long *argmin);
+int  bh_posterior_finish(bh_posterior *post, const double *vedges, int nvedges, const int *dbin, int ndbins,
+                         long long *hist, double *stdev, double *median);
+void bh_posterior_destroy(bh_posterior *post);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
