@@ -169,6 +169,9 @@ _SIGS = {
     "bh_eval_submit": (C.c_int, [_vp, C.c_int]),
     "bh_eval_wait": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "bh_eval_set_concurrency": (C.c_int, [_vp, C.c_int]),
+    "bh_forward_batch": (C.c_int, [C.c_int] * 3 + [_vp] * 5 + [C.c_int, C.POINTER(SwdTarget), _vp, C.c_int,
+                                   C.POINTER(EvalInterp), C.c_int, C.POINTER(RfParams), _vp, C.c_double, C.c_int, _vp,
+                                   C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
     "bh_swd_hint": (C.c_int, [C.c_double, C.c_int]),
     "bh_version": (C.c_char_p, []),
     "bh_last_error": (C.c_char_p, []),

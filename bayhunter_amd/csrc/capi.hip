@@ -37,6 +37,19 @@ int fail_arg(const char *what)
 namespace bh {
 int fail_arg_(const char *what) { g_err = what; return BH_ERR_ARG; }
 int fail_hip_(int e, const char *what) { return fail_hip((hipError_t)e, what); }     // evalplan.hip
+
+// bh_rf_batch's parameter checks: bh_forward_batch (evalplan.hip) makes them before its first launch
+int check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool zr)
+{
+    const int n = par->nsamp;
+    if (n < 8 || n > 4096 || (n & (n - 1))) return fail_arg("nsamp must be a power of two in 8..4096");
+    if (par->waveno != 0 && par->waveno != 1) return fail_arg("waveno must be 0 (P) or 1 (SV)");
+    if (par->nout < 1 || par->nout > n) return fail_arg("nout out of range");
+    if (par->out_off < 0 || par->out_off + par->nout > out_stride) return fail_arg("RF does not fit the output row");
+    if (!(par->gauss > 0) || !(par->fsamp > 0)) return fail_arg("gauss and fsamp must be positive");
+    if (rf_lds_bytes(Lmax, n, 1, zr) > 160 * 1024) return fail_arg("model does not fit LDS");
+    return BH_OK;
+}
 }
 namespace {
 #define BH_HIP(call)                                          \
@@ -587,7 +600,6 @@ int bh_swd_batch_ordered(int B, int Lmax, int model_stride, const int *nlay, con
         return fail_arg("NULL pointer");
     int rc = ensure_device();
     if (rc) return rc;
-    if (B == 0) return BH_OK;
     bh::SwdArgs A;
     std::memset(&A, 0, sizeof(A));
     for (int t = 0; t < ntargets; t++) {
@@ -773,15 +785,9 @@ static int rf_launch_common(int B, int Lmax, int model_stride, const int *nlay, 
     if (model_stride < Lmax) return fail_arg("model_stride < Lmax");
     if (B == 0) return BH_OK;
     if (!nlay || !h || !vp || !vs || !rho || !out) return fail_arg("NULL pointer");
-    int n = par->nsamp;
-    if (n < 8 || n > 4096 || (n & (n - 1))) return fail_arg("nsamp must be a power of two in 8..4096");
-    if (par->waveno != 0 && par->waveno != 1) return fail_arg("waveno must be 0 (P) or 1 (SV)");
-    if (par->nout < 1 || par->nout > n) return fail_arg("nout out of range");
-    if (par->out_off < 0 || par->out_off + par->nout > out_stride) return fail_arg("RF does not fit the output row");
-    if (!(par->gauss > 0) || !(par->fsamp > 0)) return fail_arg("gauss and fsamp must be positive");
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (B == 0) return BH_OK;
+    int rc = bh::check_rf_params(par, Lmax, out_stride, out_fz && out_fr);
+    if (rc || (rc = ensure_device())) return rc;
+    const int n = par->nsamp;
     bh::RfArgs A;
     std::memset(&A, 0, sizeof(A));
     bh::rf_fill_launch(A.P, par->p, par->gauss, n, par->fsamp, par->tshift, par->nsv, par->waveno, par->nout);
@@ -791,7 +797,6 @@ static int rf_launch_common(int B, int Lmax, int model_stride, const int *nlay, 
     A.P.Lmax = Lmax;
     A.P.depth_input = depth_input;
     A.P.M = (out_fz && out_fr) ? 1 : pick_rf_M(B, Lmax, n);
-    if (bh::rf_lds_bytes(Lmax, n, 1, out_fz && out_fr) > 160 * 1024) return fail_arg("model does not fit LDS");
     A.out_fz = out_fz; A.out_fr = out_fr;
     rc = get_twiddles(n, &A.tw);
     if (rc) return rc;

@@ -8,6 +8,7 @@
 // everything a batch needs (device buffers, pinned staging, two streams, events, sort scratch), so a
 // submission is: three async copies (or one), at most seven kernel launches, one async copy back, one
 // event.  No allocation, no Python object, no torch in the loop.
+// The forward stage of a submission is bh_forward_batch, which ForwardEngine.run (bayhunter_amd/engine.py) calls too.
 #include <hip/hip_runtime.h>
 #include <cstring>                     // (before rocprim: its texture iterator calls the host memset)
 #include <rocprim/rocprim.hpp>
@@ -18,7 +19,9 @@
 #include <vector>
 #include "../../include/bayhunter_amd.h"
 
-namespace bh { int fail_arg_(const char *what); int fail_hip_(int e, const char *what); }
+namespace bh {   // capi.hip
+int fail_arg_(const char *what); int fail_hip_(int e, const char *what);
+int check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool zr); }
 extern "C" const char *bh_last_error(void);
 
 namespace {
@@ -30,37 +33,32 @@ namespace {
     } while (0)
 
 constexpr int kOrderMin = 1024;   // up to this every team is resident at once: order is irrelevant (layout.py: ORDER_MIN)
-struct Interp {                   // numpy.interp(obsx, periods, solved values) for a target with > 60 periods
-    int src_off, n_src, dst_off, n_dst;
-    long long *j;                 // device tables [n_dst]
-    double *xm, *dx;
-    unsigned char *last;
-};
 
-// y = ((f[j+1] - f[j]) / dx) * xm + f[j]; an observed period that sits on the last solved one takes f[-1]
-// (numpy/core/src/multiarray/compiled_base.c: arr_interp; same expression as bayhunter_amd/engine.py)
-__global__ void interp_kernel(int B, double *out, int stride, Interp T)
+// numpy.interp(obsx, xp, f) for the n values f solved at xp (a target with more than 60 periods); an observed period on
+// the last solved one takes f[n-1] (numpy/core/src/multiarray/compiled_base.c: arr_interp).  Exactly rounded
+// subtractions and comparisons, no fused multiply-add (-ffp-contract=off): the bits of numpy.interp on the host.
+__global__ void interp_kernel(int B, double *out, int stride, const double *xp, int n, int src_off, bh_eval_interp d)
 {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)B * T.n_dst) return;
-    const int b = (int)(idx / T.n_dst), i = (int)(idx - (long)b * T.n_dst);
+    if (idx >= (long)B * d.n_dst) return;
+    const int b = (int)(idx / d.n_dst), i = (int)(idx - (long)b * d.n_dst);
+    const double x = d.obsx[i];
+    int j = 0;                                     // searchsorted(xp, x, 'right'): xp is sorted, n <= 60
+    for (int k = 0; k < n; k++) j += !(x < xp[k]);
+    j = min(max(j - 1, 0), n - 2);
     double *row = out + (long)b * stride;
-    const double *f = row + T.src_off;
-    const long long j = T.j[i];
+    const double *f = row + src_off;
     const double f0 = f[j], f1 = f[j + 1];
-    const double y = ((f1 - f0) / T.dx[i]) * T.xm[i] + f0;
-    row[T.dst_off + i] = T.last[i] ? f[T.n_src - 1] : y;
+    const double y = ((f1 - f0) / (xp[j + 1] - xp[j])) * (x - xp[j]) + f0;
+    row[d.dst_off + i] = x == xp[n - 1] ? f[n - 1] : y;
 }
 
-// A plan without dispersion targets has no kernel that raises BH_MODEL_BAD_DEPTH: the flag of a model whose
-// layer count is outside 1..L (its receiver-function row is NaN) is set here, as ForwardEngine.run does.
-__global__ void depth_flags_kernel(int n, const int *nlay, int L, int nflags, int *err)
+// Without a dispersion target no kernel raises BH_MODEL_BAD_DEPTH: the flag of a model whose layer count is outside
+// 1..L (its receiver-function row is NaN) is set here.  err has one column then.
+__global__ void depth_flags_kernel(int n, const int *nlay, int L, int *err)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int nl = nlay[i];
-    err[(long)i * nflags] = (nl < 1 || nl > L) ? BH_MODEL_BAD_DEPTH : 0;
-    for (int k = 1; k < nflags; k++) err[(long)i * nflags + k] = 0;
+    if (i < n) err[i] = (nlay[i] < 1 || nlay[i] > L) ? BH_MODEL_BAD_DEPTH : 0;
 }
 
 __global__ void iota_kernel(int n, int *v)
@@ -77,14 +75,14 @@ struct bh_eval_plan {
     std::vector<bh_swd_target> swd;
     std::vector<bh_rf_params> rf;
     std::vector<bh_like_target> like;
-    std::vector<Interp> interp;
+    std::vector<bh_eval_interp> interp;   // obsx: device pointers into `obsx`
     // pinned host staging: [packed rows*4*Lmax | noise rows*2T] doubles, then [nlay rows | chain rows] ints
     char *hblock = nullptr;
     size_t off_noise = 0, off_nlay = 0, off_chain = 0, hbytes = 0;
     double *hres = nullptr;       // [rows] logL, then [rows][T+1] misfits of the last submission
     // device
     char *dblock = nullptr;       // same layout as hblock up to the end of nlay
-    double *periods = nullptr, *yobs = nullptr, *aux = nullptr, *out = nullptr, *dres = nullptr;
+    double *periods = nullptr, *obsx = nullptr, *yobs = nullptr, *aux = nullptr, *out = nullptr, *dres = nullptr;
     int *err = nullptr, *keys = nullptr, *keys_out = nullptr, *iota = nullptr, *order = nullptr;
     void *sort_tmp = nullptr, *like_ws = nullptr, *swd_ws = nullptr;
     size_t sort_bytes = 0, like_bytes = 0, swd_bytes = 0;
@@ -104,8 +102,7 @@ static void plan_free(bh_eval_plan *p)
     (void)hipSetDevice(p->dev);
     if (p->st) (void)hipStreamSynchronize(p->st);
     if (p->side) (void)hipStreamSynchronize(p->side);
-    for (auto &t : p->interp) { (void)hipFree(t.j); (void)hipFree(t.xm); (void)hipFree(t.dx); (void)hipFree(t.last); }
-    void *dptr[] = {p->dblock, p->periods, p->yobs, p->aux, p->out, p->dres, p->err, p->keys, p->keys_out,
+    void *dptr[] = {p->dblock, p->periods, p->obsx, p->yobs, p->aux, p->out, p->dres, p->err, p->keys, p->keys_out,
                     p->iota, p->order, p->sort_tmp, p->like_ws, p->swd_ws};
     for (void *d : dptr)
         if (d) (void)hipFree(d);
@@ -130,6 +127,18 @@ static int upload(T **d, const T *h, size_t n)
     return BH_OK;
 }
 
+// an interpolation names a dispersion target of at least two periods and columns inside the output row
+static int check_interp(int nswd, const bh_swd_target *swd, int out_stride, int ninterp, const bh_eval_interp *interp)
+{
+    for (int i = 0; i < ninterp; i++) {
+        const bh_eval_interp &s = interp[i];
+        if (s.target < 0 || s.target >= nswd || swd[s.target].nper < 2 || !s.obsx || s.n_dst < 1 || s.dst_off < 0 ||
+            s.dst_off + s.n_dst > out_stride)
+            return bh::fail_arg_("bad interpolation descriptor");
+    }
+    return BH_OK;
+}
+
 extern "C" {
 
 int bh_eval_create(int max_models, int Lmax, int row, int nswd, const bh_swd_target *swd,
@@ -145,6 +154,7 @@ int bh_eval_create(int max_models, int Lmax, int row, int nswd, const bh_swd_tar
     if (ntargets < 1 || ntargets > BH_MAX_TARGETS || !like || !yobs) return bh::fail_arg_("likelihood targets missing");
     if ((nswd && (!swd || !periods)) || (nrf && !rf) || (ninterp && !interp)) return bh::fail_arg_("NULL pointer");
     if (nflags != (nswd > 0 ? nswd : 1)) return bh::fail_arg_("nflags must be the number of dispersion targets (1 without any)");
+    if (int rc = check_interp(nswd, swd, row, ninterp, interp)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
@@ -186,30 +196,11 @@ int bh_eval_create(int max_models, int Lmax, int row, int nswd, const bh_swd_tar
     if ((rc = upload(&p->periods, periods, (size_t)(nswd ? nperiods : 0)))) return bail(rc);
     if ((rc = upload(&p->yobs, yobs, (size_t)row))) return bail(rc);
     if ((rc = upload(&p->aux, aux, aux ? naux : 0))) return bail(rc);
-    for (int i = 0; i < ninterp; i++) {
-        const bh_eval_interp &s = interp[i];
-        if (s.target < 0 || s.target >= nswd || !s.obsx || s.n_dst < 1 || swd[s.target].nper < 2)
-            return bail(bh::fail_arg_("bad interpolation descriptor"));
-        const bh_swd_target &tg = swd[s.target];
-        const double *xp = periods + tg.per_off;
-        const int n = tg.nper;
-        std::vector<long long> j(s.n_dst);
-        std::vector<double> xm(s.n_dst), dx(s.n_dst);
-        std::vector<unsigned char> last(s.n_dst);
-        for (int k = 0; k < s.n_dst; k++) {          // np.clip(np.searchsorted(xp, x, side='right') - 1, 0, n - 2)
-            const double x = s.obsx[k];
-            long long jj = (long long)(std::upper_bound(xp, xp + n, x) - xp) - 1;
-            jj = std::min<long long>(std::max<long long>(jj, 0), n - 2);
-            j[k] = jj; xm[k] = x - xp[jj]; dx[k] = xp[jj + 1] - xp[jj]; last[k] = x == xp[n - 1];
-        }
-        Interp T{tg.out_off, n, s.dst_off, s.n_dst, nullptr, nullptr, nullptr, nullptr};
-        if ((rc = upload(&T.j, j.data(), j.size())) || (rc = upload(&T.xm, xm.data(), xm.size())) ||
-            (rc = upload(&T.dx, dx.data(), dx.size())) || (rc = upload(&T.last, last.data(), last.size()))) {
-            p->interp.push_back(T);
-            return bail(rc);
-        }
-        p->interp.push_back(T);
-    }
+    std::vector<double> obsx;                        // every target's observed periods, uploaded once
+    for (int i = 0; i < ninterp; i++) obsx.insert(obsx.end(), interp[i].obsx, interp[i].obsx + interp[i].n_dst);
+    if ((rc = upload(&p->obsx, obsx.data(), obsx.size()))) return bail(rc);
+    p->interp.assign(interp, interp + ninterp);
+    for (size_t i = 0, off = 0; i < p->interp.size(); off += p->interp[i++].n_dst) p->interp[i].obsx = p->obsx + off;
     p->like_bytes = use_mfma ? bh_likelihood_workspace_bytes(max_models, ntargets, like) : 0;
     p->swd_bytes = nswd ? bh_swd_workspace_bytes(max_models, nswd, swd) : 0;
     if ((p->like_bytes && hipMalloc(&p->like_ws, p->like_bytes) != hipSuccess) ||
@@ -264,6 +255,47 @@ int bh_eval_buffers(bh_eval_plan *p, double **packed, int **nlay, double **noise
     return BH_OK;
 }
 
+int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                     const double *vs, const double *rho, int nswd, const bh_swd_target *swd, const double *periods,
+                     int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
+                     double mean_layers, int concurrent_calls, double *out, int out_stride, int *err, void *workspace,
+                     size_t workspace_bytes, void *stream, void *rf_stream)
+{
+    if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return bh::fail_arg_("B/Lmax out of range");
+    if (model_stride < Lmax) return bh::fail_arg_("model_stride < Lmax");
+    if (nswd < 0 || nswd > BH_MAX_TARGETS || nrf < 0 || nswd + nrf < 1) return bh::fail_arg_("no forward targets");
+    if (B == 0) return BH_OK;
+    if (!nlay || !h || !vp || !vs || !rho || !out || !err || (nswd && (!swd || !periods)) || (nrf && !rf) ||
+        (ninterp && !interp))
+        return bh::fail_arg_("NULL pointer");
+    // the dispersion targets are checked by bh_swd_batch_ordered, before its launch: the first one
+    int rc = check_interp(nswd, swd, out_stride, ninterp, interp);
+    for (int i = 0; i < nrf && !rc; i++) rc = bh::check_rf_params(rf + i, Lmax, out_stride, false);
+    if (rc) return rc;
+    if (nswd) {
+        if ((rc = bh_swd_hint(mean_layers, concurrent_calls))) return rc;
+        if ((rc = bh_swd_batch_ordered(B, Lmax, model_stride, nlay, h, vp, vs, rho, nswd, swd, periods, out, out_stride,
+                                       err, order, workspace, workspace_bytes, stream)))
+            return rc;
+        for (int i = 0; i < ninterp; i++) {
+            const bh_swd_target &t = swd[interp[i].target];
+            const long n = (long)B * interp[i].n_dst;
+            hipLaunchKernelGGL(interp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B,
+                               out, out_stride, periods + t.per_off, t.nper, t.out_off, interp[i]);
+            EP_HIP(hipGetLastError());
+        }
+    } else {
+        hipLaunchKernelGGL(depth_flags_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B,
+                           nlay, Lmax, err);
+        EP_HIP(hipGetLastError());
+    }
+    for (int i = 0; i < nrf; i++)
+        if ((rc = bh_rf_batch(B, Lmax, model_stride, nlay, h, vp, vs, rho, nullptr, nullptr, rf + i, out, out_stride,
+                              nullptr, 0, rf_stream)))
+            return rc;
+    return BH_OK;
+}
+
 // the launches of one submission; `forked` tells the caller whether the side stream was made to wait
 static int submit_batch(bh_eval_plan *p, int count, bool *forked)
 {
@@ -297,34 +329,21 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
         EP_HIP(hipStreamWaitEvent(p->side, p->fork, 0));
         *forked = true;
     }
-    if (p->nswd) {
-        const int *order = nullptr;
-        if (count > kOrderMin) {          // deepest first, longest searches first, alike neighbours (engine.reorder)
-            if ((rc = bh_swd_order_keys(count, L, 4 * L, dnlay, h, vs, p->tmax, 1, p->keys, p->st))) return rc;
-            size_t bytes = p->sort_bytes;
-            EP_HIP(rocprim::radix_sort_pairs(p->sort_tmp, bytes, p->keys, p->keys_out, p->iota, p->order,
-                                             (size_t)count, 0, 32, p->st));
-            order = p->order;
-        }
-        // the batch is ragged: the planner prices it by its mean depth, not by its deepest model (capi.hip: plan_forms)
-        if ((rc = bh_swd_hint((double)layers / (double)count, p->concurrency))) return rc;
-        if ((rc = bh_swd_batch_ordered(count, Leff, 4 * L, dnlay, h, vp, vs, rho, p->nswd, p->swd.data(), p->periods,
-                                       p->out, p->row, p->err, order, p->swd_ws, p->swd_bytes, p->st)))
-            return rc;
-        for (const Interp &t : p->interp) {
-            const long n = (long)count * t.n_dst;
-            hipLaunchKernelGGL(interp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, p->st, count, p->out, p->row, t);
-            EP_HIP(hipGetLastError());
-        }
-    } else {
-        hipLaunchKernelGGL(depth_flags_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, p->st, count, dnlay,
-                           Leff, p->nflags, p->err);
-        EP_HIP(hipGetLastError());
+    const int *order = nullptr;
+    if (p->nswd && count > kOrderMin) {   // deepest first, longest searches first, alike neighbours (engine.reorder)
+        if ((rc = bh_swd_order_keys(count, L, 4 * L, dnlay, h, vs, p->tmax, 1, p->keys, p->st))) return rc;
+        size_t bytes = p->sort_bytes;
+        EP_HIP(rocprim::radix_sort_pairs(p->sort_tmp, bytes, p->keys, p->keys_out, p->iota, p->order,
+                                         (size_t)count, 0, 32, p->st));
+        order = p->order;
     }
+    // the batch is ragged: the planner prices it by its mean depth, not by its deepest model (capi.hip: plan_forms)
     hipStream_t rst = overlap ? p->side : p->st;
-    for (const bh_rf_params &r : p->rf)
-        if ((rc = bh_rf_batch(count, Leff, 4 * L, dnlay, h, vp, vs, rho, nullptr, nullptr, &r, p->out, p->row, nullptr, 0, rst)))
-            return rc;
+    if ((rc = bh_forward_batch(count, Leff, 4 * L, dnlay, h, vp, vs, rho, p->nswd, p->swd.data(), p->periods,
+                               (int)p->interp.size(), p->interp.data(), p->nrf, p->rf.data(), order,
+                               (double)layers / (double)count, p->concurrency, p->out, p->row, p->err, p->swd_ws,
+                               p->swd_bytes, p->st, rst)))
+        return rc;
     double *logL = p->dres, *mis = p->dres + count;
     // The dense Gaussian product of a receiver-function target needs that target's columns only: it follows
     // rf_kernel on the side stream, beside this batch's dispersion searches.  Behind the join it was on the critical

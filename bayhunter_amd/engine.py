@@ -53,10 +53,11 @@ class ForwardEngine(object):
         self.swd, self.rf = lay.swd, lay.rf
         self.slices, self.ncols, self.row = lay.slices, lay.ncols, lay.row
         self._tg, self._rfp = lay.tg, lay.rfp
-        # (user slice, scratch offset, device tables) of every target with more than 60 periods
-        self._interp = [(sl, koff, self._interp_tables(sp)) for _, sl, koff, sp in lay.resampled]
         with torch.cuda.device(self.device):
             self.periods = torch.from_numpy(lay.periods).to(self.device)
+            # observed periods of every target with more than 60: the library interpolates to them on the device
+            self._obsx = [torch.from_numpy(sp.obsx).to(self.device) for _, _, _, sp in lay.resampled]
+        self._interp = lay.interp([x.data_ptr() for x in self._obsx])
         # per launch stream (batches may be in flight on several streams at once, chains.GpuEvaluator):
         self._ws = {}            # workspace of bh_swd_batch
         self._side = {}          # side stream: RF back-fills the SIMDs the SWD tail leaves idle
@@ -65,16 +66,6 @@ class ForwardEngine(object):
         self.order_by_length = os.environ.get('BH_ORDER_BY_LENGTH', '1') != '0'   # (A/B switch)
 
     # -- helpers
-    def _interp_tables(self, sp):
-        """numpy.interp(obsx, periods, values) as gather + two flops: left index j, x - xp[j],
-        xp[j+1] - xp[j], and which observed periods sit exactly on the last solved one."""
-        xp, x = sp.periods, sp.obsx
-        j = np.clip(np.searchsorted(xp, x, side='right') - 1, 0, xp.size - 2)
-        with torch.cuda.device(self.device):
-            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-            return dict(j=dev(j.astype(np.int64)), xm=dev(x - xp[j]), dx=dev(xp[j + 1] - xp[j]),
-                        last=dev(x == xp[-1]), n=xp.size)
-
     def _as_dev(self, x, dtype):
         if isinstance(x, torch.Tensor):
             if x.device != self.device or x.dtype != dtype or not x.is_contiguous():
@@ -139,9 +130,7 @@ class ForwardEngine(object):
             # computed once and kept with them
             models.order = self.reorder(models.packed, models.nlay).order
         H, VP, VS, RHO, nlay = models.H, models.VP, models.VS, models.RHO, models.nlay
-        B = models.B
-        mstride = 4 * models.Lmax
-        Lmax = models.Lmax
+        B, mstride, Lmax = models.B, 4 * models.Lmax, models.Lmax
         if models.depth is not None:                 # even, so that rows can be fetched two layers at a time
             Lmax = min(models.Lmax, models.depth + (models.depth % 2))
         st = torch.cuda.current_stream(self.device) if stream is None else stream
@@ -158,45 +147,26 @@ class ForwardEngine(object):
             # waves retire one by one; launched on a second stream, rf_kernel's workgroups take over
             # the freed SIMDs instead of waiting for the last search to finish.
             side = None
-            if self.swd and self._rfp and self.overlap:
+            if self.swd and self.rf and self.overlap:
                 side = self._side.get(st.cuda_stream)
                 if side is None:
                     side = self._side[st.cuda_stream] = torch.cuda.Stream(device=self.device)
                 side.wait_stream(st)
-            if self.swd:
-                need = self.lib.bh_swd_workspace_bytes(B, len(self.swd), self._tg)
-                ws_ptr = None
-                if need:
-                    ws = self._ws.get(st.cuda_stream)
-                    if ws is None or ws.numel() * 8 < need:
-                        with torch.cuda.stream(st):      # the old block returns to this stream's pool
-                            ws = self._ws[st.cuda_stream] = torch.empty((need + 7) // 8, dtype=torch.float64,
-                                                                        device=self.device)
-                    ws_ptr = ws.data_ptr()
-                if models.mean_depth is not None:
-                    _lib.check(self.lib.bh_swd_hint(models.mean_depth, 1))
-                _lib.check(self.lib.bh_swd_batch_ordered(
-                    B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(),
-                    RHO.data_ptr(), len(self.swd), self._tg, self.periods.data_ptr(),
-                    out.data_ptr(), self.row, err.data_ptr(),
-                    models.order.data_ptr() if models.order is not None else None, ws_ptr, need, sp))
-                with torch.cuda.stream(st):
-                    for sl, koff, tb in self._interp:      # > 60 periods: numpy.interp on the device
-                        f = out[:, koff:koff + tb['n']]
-                        f0, f1 = f.index_select(1, tb['j']), f.index_select(1, tb['j'] + 1)
-                        y = ((f1 - f0) / tb['dx']) * tb['xm'] + f0
-                        out[:, sl] = torch.where(tb['last'], f[:, -1:].expand(-1, y.shape[1]), y)
-            else:
-                # no dispersion kernel to raise BH_MODEL_BAD_DEPTH: the receiver-function kernel NaNs the
-                # row of a model whose nlay is outside 1..Lmax, the flag is set here
-                with torch.cuda.stream(st):
-                    err.zero_()
-                    err[:, 0] = torch.where((nlay < 1) | (nlay > Lmax), 2, 0).to(torch.int32)
-            rsp = sp if side is None else C.c_void_p(side.cuda_stream)
-            for rp in self._rfp:
-                _lib.check(self.lib.bh_rf_batch(
-                    B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(),
-                    RHO.data_ptr(), None, None, C.byref(rp), out.data_ptr(), self.row, None, 0, rsp))
+            need, ws_ptr = self.lib.bh_swd_workspace_bytes(B, len(self.swd), self._tg), None
+            if need:
+                ws = self._ws.get(st.cuda_stream)
+                if ws is None or ws.numel() * 8 < need:
+                    with torch.cuda.stream(st):          # the old block returns to this stream's pool
+                        ws = self._ws[st.cuda_stream] = torch.empty((need + 7) // 8, dtype=torch.float64,
+                                                                    device=self.device)
+                ws_ptr = ws.data_ptr()
+            # row, descriptors and overlap are read at every call: a caller may move a target's columns (bench.py)
+            _lib.check(self.lib.bh_forward_batch(
+                B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(), RHO.data_ptr(),
+                len(self.swd), self._tg, self.periods.data_ptr(), len(self._obsx), self._interp, len(self.rf),
+                self._rfp, models.order.data_ptr() if models.order is not None else None, models.mean_depth or 0.0, 1,
+                out.data_ptr(), self.row, err.data_ptr(), ws_ptr, need, sp,
+                sp if side is None else C.c_void_p(side.cuda_stream)))
             if side is not None:
                 st.wait_stream(side)
                 for t in (H, VP, VS, RHO, nlay, out):

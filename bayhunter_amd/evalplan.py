@@ -31,16 +31,11 @@ class EvalPlan(object):
         self.lib = _lib.load()
         lay, desc = layout['layout'], layout['desc']
         self.rows, self.Lmax, self.T = int(max_models), int(Lmax), len(desc)
-        self._keep = [lay.periods, layout['yobs'], layout['aux']]
-        interp = (_lib.EvalInterp * max(1, len(lay.resampled)))()
-        for i, (t, sl, _, sp) in enumerate(lay.resampled):
-            self._keep.append(sp.obsx)
-            interp[i] = _lib.EvalInterp(t, sl.start, sl.stop - sl.start, 0, sp.obsx.ctypes.data)
-        rfp = (_lib.RfParams * max(1, len(lay.rfp)))(*lay.rfp)
+        interp = lay.interp([sp.obsx.ctypes.data for _, _, _, sp in lay.resampled])   # (copied by bh_eval_create)
         self.handle = C.c_void_p()
         _lib.check(self.lib.bh_eval_create(
             self.rows, self.Lmax, lay.row, len(lay.swd), lay.tg, lay.periods.ctypes.data, lay.periods.size,
-            len(lay.rfp), rfp, self.T, desc, layout['nflags'], layout['yobs'].ctypes.data, layout['aux'].ctypes.data,
+            len(lay.rf), lay.rfp, self.T, desc, layout['nflags'], layout['yobs'].ctypes.data, layout['aux'].ctypes.data,
             layout['aux'].size, len(lay.resampled), interp, 1 if use_mfma else 0, C.byref(self.handle)))
         p = [C.c_void_p() for _ in range(5)]
         _lib.check(self.lib.bh_eval_buffers(self.handle, *[C.byref(x) for x in p]))

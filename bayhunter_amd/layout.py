@@ -38,7 +38,7 @@ class SwdSpec(object):
         self.obsx = np.ascontiguousarray(periods, dtype=np.float64)
         # more than NP = 60 periods (surfdisp96.f:62): solve on 60 evenly spaced periods over the same
         # span and interpolate linearly to the observed ones, like SurfDisp (surf96_modsw.py:35-43,
-        # 106-122); ForwardEngine does the interpolation on the device
+        # 106-122); the library interpolates on the device (bh_forward_batch)
         self.resample = self.obsx.size > _lib.MAX_PERIODS
         self.periods = np.linspace(self.obsx.min(), self.obsx.max(), _lib.MAX_PERIODS) if self.resample \
             else self.obsx
@@ -65,7 +65,7 @@ class RowLayout(object):
     values; `slices[t]` is target t's column range.  Rows are `row` doubles apart: with a dispersion
     target of more than 60 periods `row` > `ncols` (the 60 solved values live behind the visible
     columns and are interpolated into them after the kernel).  `tg` / `rfp` are the descriptor arrays
-    bh_swd_batch / bh_rf_batch take, `periods` the concatenated solved periods, `resampled` the
+    bh_forward_batch takes (at least one element each), `periods` the concatenated solved periods, `resampled` the
     (target index, visible slice, scratch offset, SwdSpec) of every target with more than 60 periods."""
 
     def __init__(self, swd=(), rf=()):
@@ -96,7 +96,13 @@ class RowLayout(object):
             self.tg[t] = _lib.SwdTarget(sp.iwave, sp.igr, sp.mode, sp.flsph, sp.periods.size, per_off, koff, 0)
             pers.append(sp.periods)
             per_off += sp.periods.size
-        self.rfp = [_lib.RfParams(r.p, r.gauss, r.fsamp, r.tshft, -1.0 if r.nsv is None else float(r.nsv),
-                                  int(r.nsamp), r.waveno, r.obsx.size, o) for r, o in zip(self.rf, rf_off)]
+        self.rfp = (_lib.RfParams * max(1, len(self.rf)))(*[
+            _lib.RfParams(r.p, r.gauss, r.fsamp, r.tshft, -1.0 if r.nsv is None else float(r.nsv), int(r.nsamp),
+                          r.waveno, r.obsx.size, o) for r, o in zip(self.rf, rf_off)])
         self.row = off
         self.periods = np.ascontiguousarray(np.concatenate(pers) if pers else np.zeros(1), dtype=np.float64)
+
+    def interp(self, obsx):
+        """The bh_eval_interp array of the targets in `resampled`, with their observed periods at addresses obsx[i]."""
+        return (_lib.EvalInterp * max(1, len(self.resampled)))(
+            *[_lib.EvalInterp(t, sl.start, sl.stop - sl.start, 0, a) for (t, sl, _, _), a in zip(self.resampled, obsx)])

@@ -96,17 +96,15 @@ class SurfDisp(_Plugin):
         return self._to_observed_axis(pers, vel)
 
     def run_models(self, H, VP, VS, RHO, nlay):
-        """Batch of models ([B, Lmax] arrays) -> (x, Y[B, nobs], err[B]); unsolved rows are NaN."""
-        pers = self._solver_periods()
+        """Batch of models ([B, Lmax] arrays) -> (x, Y[B, nobs], err[B]); unsolved rows are NaN.  More than
+        60 periods are interpolated on the device, with run_model's numpy.interp bits."""
         if self._engine is None:
-            self._engine = ForwardEngine(swd=[SwdSpec(self.ref, pers, self.modelparams['mode'],
+            self._engine = ForwardEngine(swd=[SwdSpec(self.ref, self.obsx, self.modelparams['mode'],
                                                       self.modelparams['flsph'])])
         out, err = self._engine.run(H, VP, VS, RHO, nlay)
-        Y, flags = out.cpu().numpy(), err.cpu().numpy()[:, 0]
-        if self.kmax > NP_MAX:
-            Y = np.stack([np.interp(self.obsx, pers, y) for y in Y])
+        Y, flags = out[:, self._engine.slices[0]].cpu().numpy(), err.cpu().numpy()[:, 0]
         Y[flags != 0] = np.nan
-        return (self.obsx if self.kmax > NP_MAX else pers), Y, flags
+        return (self.obsx if self.kmax > NP_MAX else self._solver_periods()), Y, flags
 
 
 class RFminiModRF(_Plugin):

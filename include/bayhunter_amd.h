@@ -128,8 +128,8 @@ int bh_swd_plan_forms(int B, int Lmax, int ntargets, const bh_swd_target *target
  * library cannot see in device memory: the mean layer count of the batch's models (0: unknown -- the deepest model
  * then stands for all, which is right for batches of one depth and pessimistic for a sampler's ragged ones) and the
  * number of such calls in flight on the device together (>= 1; the chain groups of a pool alternate).  The kernel
- * form is chosen with them; results never depend on it.  The evaluation plan and ForwardEngine.upload give the hint
- * themselves. */
+ * form is chosen with them; results never depend on it.  bh_forward_batch (the evaluation plan, ForwardEngine) takes
+ * the hint as arguments. */
 int bh_swd_hint(double mean_layers, int concurrent_calls);
 int bh_swd_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h,
                  const double *vp, const double *vs, const double *rho, int ntargets,
@@ -404,11 +404,22 @@ int  bh_chains_draw(bh_chain_pool *pool, int chain, int kind, double a, double b
  * (surf96_modsw.py:35-43,106-122): one bh_eval_interp per such target. */
 typedef struct bh_eval_plan bh_eval_plan;
 typedef struct bh_eval_interp {
-    int target;          /* index into the dispersion targets                                  */
+    int target;          /* index into the dispersion targets (nper >= 2)                       */
     int dst_off, n_dst;  /* visible columns of the target in the output row, number of obsx    */
     int _pad;
-    const double *obsx;  /* observed periods [n_dst] (host)                                    */
+    const double *obsx;  /* observed periods [n_dst]: a HOST array for bh_eval_create, which uploads
+                            it once, a DEVICE array for bh_forward_batch                        */
 } bh_eval_interp;
+/* The forward stage of a batch (bh_eval_submit, ForwardEngine.run): on `stream` bh_swd_batch_ordered with
+ * bh_swd_hint(mean_layers, concurrent_calls) (mean_layers 0: unknown) and every bh_eval_interp -- or, without
+ * a dispersion target, err[b] = BH_MODEL_BAD_DEPTH if nlay[b] is outside 1..Lmax, else 0 -- then every bh_rf_batch
+ * on `rf_stream` (= stream, or one the caller forks from and joins to it).  Arguments as for those calls; swd,
+ * interp, rf are HOST arrays, err is [B][max(1, nswd)].  Every argument is checked before the first launch. */
+int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                     const double *vs, const double *rho, int nswd, const bh_swd_target *swd, const double *periods,
+                     int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
+                     double mean_layers, int concurrent_calls, double *out, int out_stride, int *err,
+                     void *workspace, size_t workspace_bytes, void *stream, void *rf_stream);
 int  bh_eval_create(int max_models, int Lmax, int row, int nswd, const bh_swd_target *swd,
                     const double *periods, int nperiods, int nrf, const bh_rf_params *rf, int ntargets,
                     const bh_like_target *like, int nflags, const double *yobs, const double *aux,

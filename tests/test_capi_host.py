@@ -76,6 +76,23 @@ def test_arg_validation_without_gpu(lib):
     assert lib.bh_swd_workspace_bytes(100, 1, tg) == 0
     tg[0].mode = 2
     assert lib.bh_swd_workspace_bytes(100, 1, tg) == 100 * 2 * 60 * 8
+    # bh_forward_batch checks every argument before its first launch (fake device pointers: nothing is launched)
+    tg[0].mode = 1
+    rfp = (_lib.RfParams * 1)(_lib.RfParams(6.4, 1.0, 5.0, 5.0, -1.0, 512, 0, 201, 21))
+    good = (_lib.EvalInterp * 1)(_lib.EvalInterp(0, 0, 21, 0, 1))
+
+    def fwd(B=4, stride=40, nlay=1, nswd=1, nrf=1, ninterp=1, interp=good):
+        return lib.bh_forward_batch(B, 10, stride, nlay, 1, 1, 1, 1, nswd, tg, 1, ninterp, interp, nrf, rfp, None,
+                                    0.0, 1, 1, 222, 1, None, 0, None, None)
+    assert fwd(B=0) == _lib.BH_OK                                          # nothing to do
+    assert fwd(nlay=None) == _lib.BH_ERR_ARG and b'NULL' in lib.bh_last_error()
+    assert fwd(ninterp=1, interp=None) == _lib.BH_ERR_ARG and b'NULL' in lib.bh_last_error()
+    assert fwd(nswd=0, nrf=0, ninterp=0) == _lib.BH_ERR_ARG and b'targets' in lib.bh_last_error()
+    assert fwd(stride=9) == _lib.BH_ERR_ARG and b'model_stride' in lib.bh_last_error()
+    for bad in ((1, 0, 21), (0, 210, 21), (0, 0, 0), (0, -1, 21)):        # target out of range, columns outside the row
+        ip = (_lib.EvalInterp * 1)(_lib.EvalInterp(bad[0], bad[1], bad[2], 0, 1))
+        assert fwd(interp=ip) == _lib.BH_ERR_ARG and b'interpolation' in lib.bh_last_error(), bad
+    assert fwd(nswd=0) == _lib.BH_ERR_ARG and b'interpolation' in lib.bh_last_error()   # no target to interpolate
     n = C.c_int(-1)
     assert lib.bh_device_count(C.byref(n)) == 0 and n.value >= 0
 

@@ -285,8 +285,8 @@ def test_eval_plan_equals_the_engine_path(B):
 
 
 def test_eval_plan_more_than_60_periods_and_swd_only():
-    """A dispersion target with 75 observed periods (solved on 60, interpolated on the device by the plan's
-    own kernel) next to an ordinary one, no receiver function: equal to the engine's torch interpolation."""
+    """A dispersion target with 75 observed periods (solved on 60, interpolated on the device) next to an
+    ordinary one, no receiver function: the plan equals the engine path."""
     import torch
     from bayhunter_amd import targets as T
     x75, x21 = np.linspace(2, 80, 75), np.linspace(1, 41, 21)

@@ -144,6 +144,16 @@ def test_more_than_60_periods_in_the_batched_engine(lib):
             assert np.isnan(y) if np.isscalar(y) else False
         else:
             assert np.array_equal(x, per) and np.array_equal(out[b, eng.slices[0]], y), b
+    # SurfDisp.run_models on the same models: run_model row by row, NaN rows where err is set
+    x, Y, e = plug.run_models(H, VP, VS, RHO, nl)
+    assert np.array_equal(x, per) and Y.shape == (40, 75) and np.array_equal(e, err[:, 0])
+    for b in range(40):
+        n = nl[b]
+        _, y = plug.run_model(H[b, :n], VP[b, :n], VS[b, :n], RHO[b, :n])
+        if e[b]:
+            assert np.isscalar(y) and np.isnan(y) and np.all(np.isnan(Y[b])), b
+        else:
+            assert np.array_equal(Y[b], y), b
     # through JointTarget.evaluate_batch against the one-model path
     rs = np.random.RandomState(3)
     t1 = T.RayleighDispersionPhase(per, 3.0 + 0.02 * per + 0.01 * rs.randn(75))
