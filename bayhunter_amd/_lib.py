@@ -11,7 +11,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
-SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip"]
+SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
+           "datafits.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h",
            "swd_form_table.h", "posterior_core.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
@@ -24,6 +25,7 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 
 BH_OK, BH_ERR_ARG, BH_ERR_HIP, BH_ERR_NO_DEVICE, BH_ERR_WORKSPACE = 0, 1, 2, 3, 4
 MAX_LAYERS, MAX_PERIODS, MAX_TARGETS = 100, 60, 16
+MAX_DATAFITS_RANKS = 16           # BH_DATAFITS_MAX_RANKS
 
 
 class SwdTarget(C.Structure):
@@ -221,6 +223,11 @@ _SIGS = {
     "bh_posterior_scan": (C.c_int, [_vp, C.POINTER(C.c_longlong), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)]),
     "bh_posterior_finish": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "bh_posterior_destroy": (None, [_vp]),
+    "bh_datafits_create": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, C.c_int, _vp,
+                                     C.POINTER(_vp)]),
+    "bh_datafits_scan": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _vp, _vp, _vp]),
+    "bh_datafits_finish": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "bh_datafits_destroy": (None, [_vp]),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -551,6 +551,15 @@ class ChainPool(object):
         from .posterior import pool_posterior
         return pool_posterior(self, dep_int, depint, dev, exclude_outliers, selection, device)
 
+    def datafits(self, selection='weighted', dev=0.05, exclude_outliers=True, q=(2.5, 16, 50, 84, 97.5), nbins=100,
+                 device=None):
+        """Statistics of the modelled data over the rows posterior() uses (datafits.summarize, with the rows' vpvs,
+        the prior's mantle rule and the joint misfit), plus 'bestfits' = dict(chains (global), rows, data: per
+        target [chains, S]) -- each chain's first least-misfit row of positive weight, as plot_bestdatafits takes
+        it (src/Plotting.py:1054-1111) -- and 'chains' (global indices used).  One forward pass for all of it."""
+        from .datafits import pool_datafits
+        return pool_datafits(self, selection, dev, exclude_outliers, q, nbins, device)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

@@ -468,6 +468,39 @@ int  bh_posterior_finish(bh_posterior *post, const double *vedges, int nvedges, 
                          long long *hist, double *stdev, double *median);
 void bh_posterior_destroy(bh_posterior *post);
 
+/* ---- posterior statistics of the modelled data -------------------------------------------- */
+/* The data half of looking at an inversion's result (PlotFromStorage.plot_bestdatafits / plot_rfcorr,
+ * src/Plotting.py:1054-1150), over the whole posterior instead of one model per chain: per column of the
+ * modelled data, over rows that each carry an integer weight, as on the matrix in which every row is repeated
+ * `weight` times.
+ *
+ * Y         DEVICE float64 [nrows][stride], the first ncols columns used (ForwardEngine's out: stride = row)
+ * weights   DEVICE int32 [nrows] >= 0, or NULL for all ones
+ * err       DEVICE int32 [nrows][nerr] flags or NULL (ForwardEngine's err).  A row with a non-zero flag or a NaN
+ *           among its ncols values is excluded: its weight is reported as `excluded` and enters no statistic
+ * stream    the caller's (NULL: the null stream), as for bh_posterior_create
+ *
+ *   bh_datafits_create   BH_ERR_ARG for no rows, ncols < 1, stride < ncols, more than 2^32 rows
+ *   bh_datafits_scan     included weight total W (BH_ERR_ARG when 0 or a weight is negative), excluded weight,
+ *                        per column min / max / mean [ncols]
+ *   bh_datafits_finish   after a scan, each part optional: order_stats[nranks][ncols] -- the values of 0-based
+ *                        ranks (ascending order, 0 <= rank < W, at most BH_DATAFITS_MAX_RANKS) of the expanded
+ *                        column, exact; with edges [nsets][nedges] (each set ascending) and eset[ncols] (the set
+ *                        of column c), hist[ncols][nedges - 1] with numpy's bin rule (edges[i] <= v < edges[i+1],
+ *                        the last bin closed); std [ncols] (population, two-pass).  The arguments are checked
+ *                        before the handle is used.
+ * Every output is a HOST buffer; each call returns when its results are there.  Two runs are bit-identical. */
+#define BH_DATAFITS_MAX_RANKS 16
+typedef struct bh_datafits bh_datafits;
+int  bh_datafits_create(const double *Y, long long nrows, long long stride, int ncols, const int *weights,
+                        const int *err, int nerr, void *stream, bh_datafits **fits);
+int  bh_datafits_scan(bh_datafits *fits, long long *total, long long *excluded, double *vmin, double *vmax,
+                      double *mean);
+int  bh_datafits_finish(bh_datafits *fits, const long long *ranks, int nranks, double *order_stats,
+                        const double *edges, int nedges, int nsets, const int *eset, long long *hist,
+                        double *stdev);
+void bh_datafits_destroy(bh_datafits *fits);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
