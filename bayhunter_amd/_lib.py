@@ -171,6 +171,7 @@ _SIGS = {
     "bh_eval_submit": (C.c_int, [_vp, C.c_int]),
     "bh_eval_wait": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "bh_eval_set_concurrency": (C.c_int, [_vp, C.c_int]),
+    "bh_eval_set_observations": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
     "bh_forward_batch": (C.c_int, [C.c_int] * 3 + [_vp] * 5 + [C.c_int, C.POINTER(SwdTarget), _vp, C.c_int,
                                    C.POINTER(EvalInterp), C.c_int, C.POINTER(RfParams), _vp, C.c_double, C.c_int, _vp,
                                    C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
@@ -204,6 +205,8 @@ _SIGS = {
                                       C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bh_likelihood_stage": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(LikeTarget), _vp, C.c_int, _vp,
                                       C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bh_likelihood_sets": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(LikeTarget), _vp, C.c_int, _vp, C.c_int,
+                                     C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bh_surfdisp96": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, _vp, _vp, C.POINTER(C.c_int)]),
     "bh_synrf": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,

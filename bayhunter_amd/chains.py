@@ -61,6 +61,18 @@ def _is_number(x):
     return isinstance(x, (int, float, np.floating, np.integer))
 
 
+def noise_priors(priors, targets):
+    """Per target the (corr, sigma) priors as ((fixed, lo, hi), (fixed, lo, hi)): a number is a fixed value."""
+    out = []
+    for target in targets:
+        pair = []
+        for name in ('noise_corr', 'noise_sigma'):
+            prior = priors[target.noiseref + name]
+            pair.append((1, float(prior), float(prior)) if _is_number(prior) else (0, float(prior[0]), float(prior[1])))
+        out.append(tuple(pair))
+    return out
+
+
 class _CallEvaluator(object):
     """Adapter for a plain function (packed, nlay, noise) -> (logL, misfits)."""
 
@@ -157,7 +169,10 @@ class _Group(object):
         if lookahead != 1:
             _lib.check(lib.bh_chains_set_lookahead(self.handle, int(lookahead)))
         self.lookahead = int(lookahead)
-        self.packed, self.nlay, self.noise, self.chain = evaluator.buffers(n * self.lookahead, Lmax, ntargets)
+        # an evaluator whose results depend on the chain a row belongs to (stations.py) is told which chains of the
+        # pool this group's chain[] counts from
+        extra = dict(chains=(first, last)) if getattr(evaluator, 'per_chain', False) else {}
+        self.packed, self.nlay, self.noise, self.chain = evaluator.buffers(n * self.lookahead, Lmax, ntargets, **extra)
         self.count = 0
         self.ticket = None
 
@@ -360,17 +375,11 @@ class ChainPool(object):
         c.acceptance[0], c.acceptance[1] = float(ip['acceptance'][0]), float(ip['acceptance'][1])
         c.iter_burnin, c.iter_main = self.iter_burnin, self.iter_main
         corrfix, corr = [], []
-        for t, target in enumerate(self.targets.targets):
-            for j, name in enumerate(('noise_corr', 'noise_sigma')):
-                prior = pr[target.noiseref + name]
-                k = 2 * t + j
-                if _is_number(prior):
-                    c.noise_fixed[k], c.noise_lo[k], c.noise_hi[k] = 1, float(prior), float(prior)
-                else:
-                    c.noise_fixed[k], c.noise_lo[k], c.noise_hi[k] = 0, float(prior[0]), float(prior[1])
-                if j == 0:
-                    corrfix.append(bool(c.noise_fixed[k]))
-                    corr.append(c.noise_lo[k])
+        for t, pair in enumerate(noise_priors(pr, self.targets.targets)):
+            for j, (fixed, lo, hi) in enumerate(pair):
+                c.noise_fixed[2 * t + j], c.noise_lo[2 * t + j], c.noise_hi[2 * t + j] = fixed, lo, hi
+            corrfix.append(bool(pair[0][0]))
+            corr.append(pair[0][1])
         return c, corrfix, corr
 
     # -- running -----------------------------------------------------------------------------

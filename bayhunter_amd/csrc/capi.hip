@@ -861,14 +861,24 @@ int bh_likelihood_stage(int stages, int B, int ntargets, const bh_like_target *t
                         const double *noise, const double *aux, double *logL, double *misfits,
                         void *workspace, size_t workspace_bytes, void *stream)
 {
+    return bh_likelihood_sets(stages, B, ntargets, targets, out, out_stride, err, nflags, 1, nullptr, yobs, out_stride,
+                              nullptr, nullptr, noise, aux, logL, misfits, workspace, workspace_bytes, stream);
+}
+
+int bh_likelihood_sets(int stages, int B, int ntargets, const bh_like_target *targets, const double *out,
+                       int out_stride, const int *err, int nflags, int nsets, const int *obs_id, const double *yobs,
+                       int set_stride, const double *set_scale, const double *set_logdet, const double *noise,
+                       const double *aux, double *logL, double *misfits, void *workspace, size_t workspace_bytes,
+                       void *stream)
+{
     if (stages < 1 || stages > 3) return fail_arg("bh_likelihood_stage: stages is BH_LIKE_STAGE_GAUSS | BH_LIKE_STAGE_REST");
     if (B < 0 || ntargets < 1 || ntargets > BH_MAX_TARGETS) return fail_arg("B/ntargets out of range");
+    if (nsets < 1) return fail_arg("bh_likelihood_sets: nsets < 1");
     if (B == 0) return BH_OK;
     if (!targets || !out || !yobs || !noise || !logL || !misfits) return fail_arg("NULL pointer");
     if (nflags < 0 || (nflags > 0 && !err)) return fail_arg("err is NULL but nflags > 0");
-    int rc = ensure_device();
-    if (rc) return rc;
-    if (B == 0) return BH_OK;
+    if (nsets > 1 && !obs_id) return fail_arg("bh_likelihood_sets: obs_id is NULL but nsets > 1");
+    if (!set_scale != !set_logdet) return fail_arg("bh_likelihood_sets: set_scale and set_logdet come together");
     bh::LikeArgs A;
     std::memset(&A, 0, sizeof(A));
     int nmax = 1;
@@ -876,13 +886,19 @@ int bh_likelihood_stage(int stages, int B, int ntargets, const bh_like_target *t
         const bh_like_target &s = targets[t];
         if (s.n < 1 || s.n > bh::LIKE_NMAX) return fail_arg("target size out of range (1..1024)");
         if (s.off < 0 || s.off + s.n > out_stride) return fail_arg("target does not fit the output row");
+        if (s.off + s.n > set_stride) return fail_arg("bh_likelihood_sets: target does not fit a set's row (set_stride)");
         if (s.cov < 0 || s.cov > 3) return fail_arg("unknown covariance model");
-        if ((s.cov == BH_COV_NOCORR_SCALED || s.cov == BH_COV_GAUSS) && !aux) return fail_arg("aux is NULL");
+        if (s.cov == BH_COV_NOCORR_SCALED && nsets > 1 && !set_scale)
+            return fail_arg("bh_likelihood_sets: a BH_COV_NOCORR_SCALED target needs set_scale and set_logdet with nsets > 1");
+        if (((s.cov == BH_COV_NOCORR_SCALED && !set_scale) || s.cov == BH_COV_GAUSS) && !aux) return fail_arg("aux is NULL");
         A.tg[t] = bh::LikeTargetDev{s.n, s.off, s.cov, s.aux_off, s.logdet_extra};
         if (s.n > nmax) nmax = s.n;
     }
+    int rc = ensure_device();
+    if (rc) return rc;
     A.B = B; A.ntargets = ntargets; A.out_stride = out_stride; A.nflags = nflags;
     A.out = out; A.err = err; A.yobs = yobs; A.noise = noise; A.aux = aux;
+    A.nsets = nsets; A.set_stride = set_stride; A.obs_id = obs_id; A.set_scale = set_scale; A.set_logdet = set_logdet;
     A.logL = logL; A.misfits = misfits;
     size_t need = bh_likelihood_workspace_bytes(B, ntargets, targets);
     A.gq = (need > 0 && workspace && workspace_bytes >= need) ? (double *)workspace : nullptr;

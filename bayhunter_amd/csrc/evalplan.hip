@@ -76,12 +76,13 @@ struct bh_eval_plan {
     std::vector<bh_rf_params> rf;
     std::vector<bh_like_target> like;
     std::vector<bh_eval_interp> interp;   // obsx: device pointers into `obsx`
-    // pinned host staging: [packed rows*4*Lmax | noise rows*2T] doubles, then [nlay rows | chain rows] ints
+    // pinned host staging: [packed rows*4*Lmax | noise rows*2T] doubles, then [nlay rows | set rows | chain rows] ints
+    // (set: the observation set of each row, filled by bh_eval_submit from chain[] once bh_eval_set_observations was called)
     char *hblock = nullptr;
-    size_t off_noise = 0, off_nlay = 0, off_chain = 0, hbytes = 0;
+    size_t off_noise = 0, off_nlay = 0, off_set = 0, off_chain = 0, hbytes = 0;
     double *hres = nullptr;       // [rows] logL, then [rows][T+1] misfits of the last submission
     // device
-    char *dblock = nullptr;       // same layout as hblock up to the end of nlay
+    char *dblock = nullptr;       // same layout as hblock up to the end of set
     double *periods = nullptr, *obsx = nullptr, *yobs = nullptr, *aux = nullptr, *out = nullptr, *dres = nullptr;
     int *err = nullptr, *keys = nullptr, *keys_out = nullptr, *iota = nullptr, *order = nullptr;
     void *sort_tmp = nullptr, *like_ws = nullptr, *swd_ws = nullptr;
@@ -91,6 +92,11 @@ struct bh_eval_plan {
     int concurrency = 1;          // plans taking turns on the device (bh_eval_set_concurrency)
     bool gauss_on_side = false;   // every dense-Gaussian target is a receiver function's: its product runs behind
                                   // rf_kernel on the side stream, beside the dispersion searches (bh_eval_submit)
+    // observation sets (bh_eval_set_observations): yobs holds nsets rows; set_of_chain maps chain[k] to its set
+    int nsets = 1;
+    double *set_scale = nullptr, *set_logdet = nullptr;
+    std::vector<int> set_of_chain;
+    bool submitted = false;       // a batch has been submitted: the observations are fixed from then on
     int last_count = 0;           // models of the submission `done` belongs to (set once `done` is recorded)
     bool failed = false;          // the last submission returned an error: nothing to wait for, no results
     std::string failure;
@@ -102,8 +108,8 @@ static void plan_free(bh_eval_plan *p)
     (void)hipSetDevice(p->dev);
     if (p->st) (void)hipStreamSynchronize(p->st);
     if (p->side) (void)hipStreamSynchronize(p->side);
-    void *dptr[] = {p->dblock, p->periods, p->obsx, p->yobs, p->aux, p->out, p->dres, p->err, p->keys, p->keys_out,
-                    p->iota, p->order, p->sort_tmp, p->like_ws, p->swd_ws};
+    void *dptr[] = {p->dblock, p->periods, p->obsx, p->yobs, p->aux, p->set_scale, p->set_logdet, p->out, p->dres, p->err, p->keys,
+                    p->keys_out, p->iota, p->order, p->sort_tmp, p->like_ws, p->swd_ws};
     for (void *d : dptr)
         if (d) (void)hipFree(d);
     if (p->hblock) (void)hipHostFree(p->hblock);
@@ -178,7 +184,8 @@ int bh_eval_create(int max_models, int Lmax, int row, int nswd, const bh_swd_tar
     const size_t R = (size_t)max_models;
     p->off_noise = R * 4 * Lmax * sizeof(double);
     p->off_nlay = p->off_noise + R * 2 * ntargets * sizeof(double);
-    p->off_chain = p->off_nlay + R * sizeof(int);
+    p->off_set = p->off_nlay + R * sizeof(int);
+    p->off_chain = p->off_set + R * sizeof(int);
     p->hbytes = p->off_chain + R * sizeof(int);
     if (hipHostMalloc((void **)&p->hblock, p->hbytes, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc((void **)&p->hres, R * (ntargets + 2) * sizeof(double), hipHostMallocDefault) != hipSuccess)
@@ -309,9 +316,23 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
     // fetched two layers at a time), not by the allocated row length
     const int Leff = std::min(L, depth + (depth & 1));
     // small pools: the whole block in one copy; large ones: only the used part of each section
+    const bool sets = !p->set_of_chain.empty();
+    if (sets) {                            // one int per row: the set of the chain the proposal belongs to
+        const int *chain = (const int *)(p->hblock + p->off_chain);
+        int *set = (int *)(p->hblock + p->off_set);
+        const int nchains = (int)p->set_of_chain.size();
+        for (int k = 0; k < count; k++) {
+            if (chain[k] < 0 || chain[k] >= nchains) return bh::fail_arg_("bh_eval_submit: chain[] names a chain outside bh_eval_set_observations' set_of_chain");
+            set[k] = p->set_of_chain[chain[k]];
+        }
+    }
     if (p->rows <= 16384) {
-        EP_HIP(hipMemcpyAsync(p->dblock, p->hblock, p->off_nlay + (size_t)count * sizeof(int), hipMemcpyHostToDevice, p->st));
+        EP_HIP(hipMemcpyAsync(p->dblock, p->hblock, (sets ? p->off_set : p->off_nlay) + (size_t)count * sizeof(int),
+                              hipMemcpyHostToDevice, p->st));
     } else {
+        if (sets)
+            EP_HIP(hipMemcpyAsync(p->dblock + p->off_set, p->hblock + p->off_set, (size_t)count * sizeof(int),
+                                  hipMemcpyHostToDevice, p->st));
         EP_HIP(hipMemcpyAsync(p->dblock, p->hblock, (size_t)count * 4 * L * sizeof(double), hipMemcpyHostToDevice, p->st));
         EP_HIP(hipMemcpyAsync(p->dblock + p->off_noise, p->hblock + p->off_noise, (size_t)count * 2 * T * sizeof(double),
                               hipMemcpyHostToDevice, p->st));
@@ -321,6 +342,7 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
     const double *dm = (const double *)p->dblock;
     const double *dnoise = (const double *)(p->dblock + p->off_noise);
     const int *dnlay = (const int *)(p->dblock + p->off_nlay);
+    const int *dset = sets ? (const int *)(p->dblock + p->off_set) : nullptr;
     const double *h = dm, *vp = dm + L, *vs = dm + 2 * L, *rho = dm + 3 * L;
     int rc;
     const bool overlap = p->nswd > 0 && p->nrf > 0;
@@ -351,17 +373,18 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
     // third of a millisecond for the OTHER chain group's teams to drain (rocprofv3 of a 4 096-chain pool: 0.31 ms per
     // call where it takes 0.04 ms alone, 22 % of the kernel time).
     const bool staged = overlap && p->gauss_on_side;
-    if (staged && (rc = bh_likelihood_stage(BH_LIKE_STAGE_GAUSS, count, T, p->like.data(), p->out, p->row, p->err, p->nflags,
-                                            p->yobs, dnoise, p->aux, logL, mis, p->like_ws, p->like_bytes, rst)))
+    if (staged && (rc = bh_likelihood_sets(BH_LIKE_STAGE_GAUSS, count, T, p->like.data(), p->out, p->row, p->err, p->nflags,
+                                           p->nsets, dset, p->yobs, p->row, p->set_scale, p->set_logdet, dnoise, p->aux, logL,
+                                           mis, p->like_ws, p->like_bytes, rst)))
         return rc;
     if (overlap) {
         EP_HIP(hipEventRecord(p->join, p->side));
         EP_HIP(hipStreamWaitEvent(p->st, p->join, 0));
         *forked = false;                  // joined
     }
-    if ((rc = bh_likelihood_stage(staged ? BH_LIKE_STAGE_REST : (BH_LIKE_STAGE_GAUSS | BH_LIKE_STAGE_REST), count, T,
-                                  p->like.data(), p->out, p->row, p->err, p->nflags, p->yobs, dnoise, p->aux, logL, mis,
-                                  p->like_ws, p->like_bytes, p->st)))
+    if ((rc = bh_likelihood_sets(staged ? BH_LIKE_STAGE_REST : (BH_LIKE_STAGE_GAUSS | BH_LIKE_STAGE_REST), count, T,
+                                 p->like.data(), p->out, p->row, p->err, p->nflags, p->nsets, dset, p->yobs, p->row,
+                                 p->set_scale, p->set_logdet, dnoise, p->aux, logL, mis, p->like_ws, p->like_bytes, p->st)))
         return rc;
     // results: [count] logL then [count][T+1] misfits, contiguous on both sides
     EP_HIP(hipMemcpyAsync(p->hres, p->dres, (size_t)count * (T + 2) * sizeof(double), hipMemcpyDeviceToHost, p->st));
@@ -375,6 +398,7 @@ int bh_eval_submit(bh_eval_plan *p, int count)
     if (count < 0 || count > p->rows) return bh::fail_arg_("count out of range");
     p->failed = false;
     p->last_count = 0;
+    p->submitted = true;
     if (count == 0) return BH_OK;
     bool forked = false;
     const int rc = submit_batch(p, count, &forked);
@@ -389,6 +413,40 @@ int bh_eval_submit(bh_eval_plan *p, int count)
         return rc;
     }
     p->last_count = count;                            // only now: `done` has been recorded for this batch
+    return BH_OK;
+}
+
+int bh_eval_set_observations(bh_eval_plan *p, int nsets, const double *yobs, const double *set_scale,
+                             const double *set_logdet, const int *set_of_chain, int nchains)
+{
+    if (nsets < 1) return bh::fail_arg_("bh_eval_set_observations: nsets < 1");
+    if (!yobs || !set_of_chain) return bh::fail_arg_("bh_eval_set_observations: NULL pointer (yobs / set_of_chain)");
+    if (nchains < 1) return bh::fail_arg_("bh_eval_set_observations: nchains < 1");
+    if (!set_scale != !set_logdet) return bh::fail_arg_("bh_eval_set_observations: set_scale and set_logdet come together");
+    for (int c = 0; c < nchains; c++)
+        if (set_of_chain[c] < 0 || set_of_chain[c] >= nsets)
+            return bh::fail_arg_(("bh_eval_set_observations: set_of_chain[" + std::to_string(c) + "] = " +
+                                  std::to_string(set_of_chain[c]) + " is outside 0 .. nsets-1").c_str());
+    if (!p) return bh::fail_arg_("plan is NULL");
+    if (p->submitted) return bh::fail_arg_("bh_eval_set_observations: called after bh_eval_submit");
+    if (!p->set_of_chain.empty()) return bh::fail_arg_("bh_eval_set_observations: the plan has its observation sets already");
+    for (const bh_like_target &t : p->like)
+        if (t.cov == BH_COV_NOCORR_SCALED && !set_scale)
+            return bh::fail_arg_("bh_eval_set_observations: a BH_COV_NOCORR_SCALED target needs set_scale and set_logdet");
+    EP_HIP(hipSetDevice(p->dev));
+    double *dy = nullptr, *ds = nullptr, *dl = nullptr;
+    int rc = upload(&dy, yobs, (size_t)nsets * p->row);
+    if (!rc && set_scale) rc = upload(&ds, set_scale, (size_t)nsets * p->row);
+    if (!rc && set_scale) rc = upload(&dl, set_logdet, (size_t)nsets * p->T);
+    if (rc) {
+        for (void *d : {(void *)dy, (void *)ds, (void *)dl})
+            if (d) (void)hipFree(d);
+        return rc;
+    }
+    (void)hipFree(p->yobs);
+    p->yobs = dy; p->set_scale = ds; p->set_logdet = dl;
+    p->nsets = nsets;
+    p->set_of_chain.assign(set_of_chain, set_of_chain + nchains);
     return BH_OK;
 }
 

@@ -83,8 +83,23 @@ struct LikeArgs {
     double *logL, *misfits;
     double *gq;              // [ntargets][B][gq_groups][2] partial (q, sum d^2) of dense-Gaussian targets, or null
     int gq_groups;           // column-tile groups per model in gq (the widest Gaussian target's)
+    // Observation sets (stations): row b is compared with set obs_id[b] of yobs[nsets][set_stride].  What depends on a
+    // set's yerr lies in tables of the same shape: set_scale[nsets][set_stride] holds the scaled errors of the
+    // BH_COV_NOCORR_SCALED targets in the targets' own columns, set_logdet[nsets][ntargets] their log(prod(scaled_err)).
+    // obs_id null: every row takes set 0; set_scale / set_logdet null: aux + aux_off and tg.logdet_extra (one set).
+    // The dense R^-1 of a BH_COV_GAUSS target depends on the fixed correlation and n only: one copy in aux for all sets.
+    int nsets, set_stride;
+    const int *obs_id;
+    const double *set_scale, *set_logdet;
     LikeTargetDev tg[BH_NT];
 };
+// The set of row b, or -1 for an index outside [0, nsets): such a row gets the failed-model result
+__device__ __forceinline__ int like_set_of(const LikeArgs &A, long b)
+{
+    if (!A.obs_id) return 0;
+    const int s = A.obs_id[b];
+    return (s >= 0 && s < A.nsets) ? s : -1;
+}
 // The dense Gaussian product runs per group of GQ_NTG column tiles of 16 (like_kernel.hip: gauss_q_kernel)
 constexpr int GQ_NTG = 4;
 __host__ __device__ inline int gq_groups_of(int n) { return ((n + 15) / 16 + GQ_NTG - 1) / GQ_NTG; }

@@ -61,7 +61,9 @@ __global__ __launch_bounds__(64 * GQ_WAVES) __attribute__((amdgpu_waves_per_eu(2
     const long bm = b0 + mrow;
     const bool mvalid = bm < A.B;
     const double *drow = A.out + (mvalid ? bm : 0) * (long)A.out_stride + tg.off;
-    const double *yobs = A.yobs + tg.off;
+    // the 16 models of a wave may belong to 16 observation sets: every lane subtracts its own model's row
+    // (a row with an index out of range reads set 0; like_kernel gives it the failed-model result)
+    const double *yobs = A.yobs + (long)max(mvalid ? like_set_of(A, bm) : 0, 0) * A.set_stride + tg.off;
     const int ntiles = (n + 15) / 16;
     const int nchunk = (n + GQ_KC - 1) / GQ_KC;
     const int tb0 = SPLIT ? (int)blockIdx.y * NT : 0, tb1 = SPLIT ? tb0 + NT : ntiles;
@@ -110,11 +112,12 @@ __global__ __launch_bounds__(64 * GQ_WAVES) __attribute__((amdgpu_waves_per_eu(2
                 const long bmod = b0 + kq + 4 * r;
                 const bool ok = bmod < A.B;
                 const double *dr = A.out + (ok ? bmod : 0) * (long)A.out_stride + tg.off;
+                const double *yr = A.yobs + (long)max(ok ? like_set_of(A, bmod) : 0, 0) * A.set_stride + tg.off;
                 double q = 0.0, s2 = 0.0;
 #pragma unroll
                 for (int i = g * GQ_NTG; i < (g + 1) * GQ_NTG && i < NT; i++) {
                     const int col = (tb + i) * 16 + mrow;
-                    const double d = (ok && col < n) ? dr[col] - yobs[col] : 0.0;
+                    const double d = (ok && col < n) ? dr[col] - yr[col] : 0.0;
                     q += acc[i][r] * d;
                     s2 += d * d;
                 }
@@ -138,6 +141,7 @@ __global__ __launch_bounds__(LIKE_T) void like_kernel(LikeArgs A)
     __shared__ double acc_logl[LIKE_M];
     __shared__ double acc_mis[LIKE_M];
     __shared__ int bad[LIKE_M];
+    __shared__ int setof[LIKE_M];           // the models' observation sets
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int b0 = blockIdx.x * LIKE_M;
     const int Mb = min(LIKE_M, A.B - b0);
@@ -149,7 +153,9 @@ __global__ __launch_bounds__(LIKE_T) void like_kernel(LikeArgs A)
         int flag = 0;
         if (tid < Mb)
             for (int f = 0; f < A.nflags; f++) flag |= A.err[(long)(b0 + tid) * A.nflags + f];
-        bad[tid] = flag;
+        const int set = tid < Mb ? like_set_of(A, b0 + tid) : 0;
+        bad[tid] = flag | (set < 0);
+        setof[tid] = max(set, 0);
     }
     __syncthreads();
 
@@ -159,7 +165,7 @@ __global__ __launch_bounds__(LIKE_T) void like_kernel(LikeArgs A)
         // residuals d = ymod - yobs of the workgroup's models -> LDS (coalesced row reads)
         for (int idx = tid; idx < Mb * n; idx += LIKE_T) {
             int m = idx / n, i = idx - m * n;
-            sm[m * n + i] = A.out[(long)(b0 + m) * A.out_stride + tg.off + i] - A.yobs[tg.off + i];
+            sm[m * n + i] = A.out[(long)(b0 + m) * A.out_stride + tg.off + i] - A.yobs[(long)setof[m] * A.set_stride + tg.off + i];
         }
         __syncthreads();
 
@@ -213,7 +219,7 @@ __global__ __launch_bounds__(LIKE_T) void like_kernel(LikeArgs A)
                         for (int i = lane; i < n; i += 64) s2 += d[i] * d[i];
                         q = s2;
                     } else if (tg.cov == 1) {
-                        const double *se = A.aux + tg.aux_off;
+                        const double *se = A.set_scale ? A.set_scale + (long)setof[m] * A.set_stride + tg.off : A.aux + tg.aux_off;
                         for (int i = lane; i < n; i += 64) {
                             double dd = d[i] * d[i];
                             s2 += dd;
@@ -252,7 +258,7 @@ __global__ __launch_bounds__(LIKE_T) void like_kernel(LikeArgs A)
                 logdet += (n - 1) * log(1.0 - corr * corr);
             } else {
                 madist = q / (sigma * sigma);
-                logdet += tg.logdet_extra;
+                logdet += (tg.cov == 1 && A.set_logdet) ? A.set_logdet[(long)setof[m] * A.ntargets + t] : tg.logdet_extra;
             }
             const double logl_part = -0.5 * (n * log(2.0 * 3.141592653589793) + logdet);
             acc_logl[m] += logl_part - madist / 2.0;

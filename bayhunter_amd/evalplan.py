@@ -30,7 +30,7 @@ class EvalPlan(object):
     def __init__(self, layout, max_models, Lmax, use_mfma=True):
         self.lib = _lib.load()
         lay, desc = layout['layout'], layout['desc']
-        self.rows, self.Lmax, self.T = int(max_models), int(Lmax), len(desc)
+        self.rows, self.Lmax, self.T, self.row = int(max_models), int(Lmax), len(desc), int(lay.row)
         interp = lay.interp([sp.obsx.ctypes.data for _, _, _, sp in lay.resampled])   # (copied by bh_eval_create)
         self.handle = C.c_void_p()
         _lib.check(self.lib.bh_eval_create(
@@ -53,6 +53,25 @@ class EvalPlan(object):
 
     def submit(self, count):
         _lib.check(self.lib.bh_eval_submit(self._live(), int(count)))
+
+    def set_observations(self, yobs, set_of_chain, set_scale=None, set_logdet=None):
+        """The chains behind this plan belong to yobs.shape[0] observation sets (bh_eval_set_observations):
+        yobs[nsets, row], set_scale[nsets, row], set_logdet[nsets, ntargets] (both or neither), set_of_chain[nchains]
+        for the chain numbers the sampler writes to `chain`.  Once, before the first submit."""
+        yobs = np.ascontiguousarray(yobs, dtype=np.float64)
+        soc = np.ascontiguousarray(set_of_chain, dtype=np.int32)
+        if yobs.ndim != 2 or yobs.shape[1] != self.row:
+            raise ValueError("yobs: one row of %d values per observation set" % self.row)
+        tabs = []
+        for tab, width in ((set_scale, self.row), (set_logdet, self.T)):
+            if tab is not None:
+                tab = np.ascontiguousarray(tab, dtype=np.float64)
+                if tab.shape != (yobs.shape[0], width):
+                    raise ValueError("per-set table of shape %s, expected %s" % (tab.shape, (yobs.shape[0], width)))
+            tabs.append(tab)
+        _lib.check(self.lib.bh_eval_set_observations(
+            self._live(), yobs.shape[0], yobs.ctypes.data, *[None if t is None else t.ctypes.data for t in tabs],
+            soc.ctypes.data, soc.size))
 
     def set_concurrency(self, plans_in_flight):
         """How many plans take turns on the device (the chain groups of a pool): the library chooses its kernel

@@ -1,0 +1,309 @@
+"""Many stations in one chain pool: chains that share everything but the observed data.
+
+The reference is run station by station (or node by node of a set of dispersion maps): the same periods, priors
+and `initparams`, 5-40 chains each, differing in `obsdata.y` and `obsdata.yerr` only.  One after the other these are
+small pools, each bound by the latency of a device call; together they are the large batch
+the kernels were built for.  The host side of the sampler never sees observed data and the forward kernels do not
+either: only the likelihood does, and it subtracts the row of the station a proposal's chain belongs to
+(bh_likelihood_sets, bh_eval_set_observations).  A model's forward row and likelihood do not depend on the batch
+it is in, so a station's chains are bit for bit the chains of a `ChainPool` of that station alone.
+
+    pool = StationPool({'ST1': joint1, 'ST2': joint2, ...}, initparams, priors, chains_per_station=8,
+                       random_seeds=[11, 12, ...]).run()
+    pool.station('ST2').posterior()          # the interface of a ChainPool, restricted to the station's chains
+    pool.save()                              # one directory per station, each what a single-station pool writes
+
+What may differ between stations is deliberately little: per-station periods, time axes, slowness or priors would
+need per-row descriptors in the forward kernels and per-chain configurations in the sampler.
+"""
+import inspect
+import os
+
+import numpy as np
+
+from . import _lib
+from .chains import DEFAULT_INITPARAMS, DEFAULT_PRIORS, ChainPool, GpuEvaluator, _CallEvaluator, noise_priors
+
+_COV_NAMES = {_lib.COV_NOCORR: 'NOCORR (no yerr)', _lib.COV_NOCORR_SCALED: 'NOCORR_SCALED (yerr given)',
+              _lib.COV_EXP: 'EXP', _lib.COV_GAUSS: 'GAUSS'}
+
+
+def _plugin_params(target):
+    p = target.moddata.plugin
+    return type(p).__name__, dict(getattr(p, 'modelparams', None) or {})
+
+
+def check_stations(names, joints):
+    """All stations share the row layout (targets, their order, x axes, plugin parameters) and the covariance model
+    of each target (after set_target_covariance): ValueError naming the station and the property otherwise."""
+    first, name0 = joints[0], names[0]
+    for name, joint in zip(names[1:], joints[1:]):
+        who = "station %r differs from station %r: " % (name, name0)
+        if joint.ntargets != first.ntargets:
+            raise ValueError(who + "number of targets (%d, %d)" % (joint.ntargets, first.ntargets))
+        if bool(joint.use_mfma) != bool(first.use_mfma):
+            raise ValueError(who + "use_mfma")
+        for t, (a, b) in enumerate(zip(joint.targets, first.targets)):
+            what = who + "target %d " % t
+            if a.ref != b.ref or a.noiseref != b.noiseref:
+                raise ValueError(what + "ref (%r, %r)" % (a.ref, b.ref))
+            ax, bx = np.asarray(a.obsdata.x), np.asarray(b.obsdata.x)
+            if ax.shape != bx.shape or not np.array_equal(ax, bx):
+                raise ValueError(what + "(%s) x axis (periods / times); per-station axes are not supported" % a.ref)
+            if np.asarray(a.obsdata.y).shape != ax.shape:
+                raise ValueError(what + "(%s) y does not have the length of x" % a.ref)
+            (acls, apar), (bcls, bpar) = _plugin_params(a), _plugin_params(b)
+            if acls != bcls:
+                raise ValueError(what + "(%s) forward plugin (%s, %s)" % (a.ref, acls, bcls))
+            for key in sorted(set(apar) | set(bpar)):
+                if key not in apar or key not in bpar or apar[key] != bpar[key]:
+                    raise ValueError(what + "(%s) plugin parameter %r (%r, %r); per-station plugin parameters are "
+                                     "not supported" % (a.ref, key, apar.get(key), bpar.get(key)))
+            if a.covmodel != b.covmodel:
+                raise ValueError(what + "(%s) covariance model (%s, %s): yerr must be usable at every station or at "
+                                 "none" % (a.ref, _COV_NAMES[a.covmodel], _COV_NAMES[b.covmodel]))
+            if a.covmodel == _lib.COV_GAUSS and (
+                    not np.array_equal(a.valuation.corr_inv, b.valuation.corr_inv)
+                    or a.valuation.logcorr_det != b.valuation.logcorr_det):
+                raise ValueError(what + "(%s) fixed noise correlation matrix" % a.ref)
+
+
+def observation_tables(joints):
+    """yobs[nsets, row], set_scale[nsets, row], set_logdet[nsets, ntargets] of stations that passed check_stations, from
+    each station's own batch_layout() (so every number is the one a single-station plan uploads); the two tables of
+    the yerr-scaled targets are None when no target has that covariance model."""
+    yobs, scale, logdet = [], [], []
+    for joint in joints:                    # one layout at a time: each carries its dense R^-1 (323 KB at n = 201)
+        bl = joint.batch_layout()
+        desc, row = bl['desc'], bl['layout'].row
+        yobs.append(bl['yobs'])
+        sc, ld = np.ones(row), np.zeros(len(desc))
+        for t in range(len(desc)):
+            if desc[t].cov == _lib.COV_NOCORR_SCALED:
+                d = desc[t]
+                sc[d.off:d.off + d.n] = bl['aux'][d.aux_off:d.aux_off + d.n]
+                ld[t] = d.logdet_extra
+        scale.append(sc)
+        logdet.append(ld)
+    if not any(d.cov == _lib.COV_NOCORR_SCALED for d in desc):
+        return np.stack(yobs), None, None
+    return np.stack(yobs), np.stack(scale), np.stack(logdet)
+
+
+class StationGpuEvaluator(GpuEvaluator):
+    """GpuEvaluator whose evaluation plans carry one observation set per station: a plan is built from the first
+    station's layout and given every station's observed data and the station of each of its group's chains."""
+    per_chain = True
+
+    def __init__(self, joints, station_of_chain, device=None):
+        GpuEvaluator.__init__(self, joints[0], device)
+        self.joints, self.station_of_chain = list(joints), np.asarray(station_of_chain, dtype=np.int32)
+        self._tables = None
+
+    def buffers(self, rows, Lmax, ntargets, chains):
+        if self._tables is None:            # (after the pool has chosen the covariance models)
+            self._tables = observation_tables(self.joints)
+        packed, nlay, noise, chain = GpuEvaluator.buffers(self, rows, Lmax, ntargets)
+        yobs, scale, logdet = self._tables
+        self._plans[packed.ctypes.data].set_observations(yobs, self.station_of_chain[chains[0]:chains[1]], scale, logdet)
+        return packed, nlay, noise, chain
+
+
+class StationCallEvaluator(_CallEvaluator):
+    """Adapter for a plain function (packed, nlay, noise, station[B]) -> (logL, misfits)."""
+
+    def __init__(self, fn, station_of_chain):
+        _CallEvaluator.__init__(self, fn)
+        self.station_of_chain = np.asarray(station_of_chain, dtype=np.int32)
+
+    def submit(self, group, packed, nlay, noise):
+        n = packed.shape[0]
+        return self.fn(packed, nlay, noise, self.station_of_chain[group.first + group.chain[:n]])
+
+
+def _takes_station(fn):
+    try:
+        params = [p for p in inspect.signature(fn).parameters.values()
+                  if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]
+    except (TypeError, ValueError):
+        return False
+    return len(params) >= 4
+
+
+class StationView(ChainPool):
+    """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
+    noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
+    datafits(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
+
+    def __init__(self, pool, s):
+        inner, c = pool.pool, pool.chains_per_station
+        self._parent, self._range = inner, slice(s * c, (s + 1) * c)
+        self.lib, self.targets, self.priors = inner.lib, pool.stations[s], inner.priors
+        self.initparams = dict(inner.initparams, nchains=c, station=pool.names[s],
+                               savepath=os.path.join(inner.initparams['savepath'], str(pool.names[s])))
+        self.nchains = self.nchains_total = c
+        self.first = 0
+        self.ntargets, self.cfg = inner.ntargets, inner.cfg
+        self.iter_burnin, self.iter_main, self.iterations = inner.iter_burnin, inner.iter_main, inner.iterations
+        self.maxlayers, self.Lmax, self.nmodels = inner.maxlayers, inner.Lmax, inner.nmodels
+        self.seeds = inner.seeds[self._range]
+        for name in ('models', 'misfits', 'likes', 'noise', 'vpvs', 'iter'):
+            setattr(self, name, getattr(inner, name)[self._range])
+        self.groups = ()
+        self._closed_counters = self._closed_advance = None
+
+    def counters(self):
+        return tuple(a[self._range] for a in self._parent.counters())
+
+    def run(self, progress=None):
+        raise _lib.BayHunterAmdError("a station's chains run with their pool: StationPool.run()")
+
+    def advance(self):
+        raise _lib.BayHunterAmdError("device calls are counted for the whole pool: StationPool.advance()")
+
+
+class StationPool(object):
+    """`StationPool(stations, initparams, modelpriors, chains_per_station=..., random_seeds=...)`: ONE lock-step pool
+    of nstations * chains_per_station chains; chain s * chains_per_station + i is chain i of station s.
+
+    stations            sequence of JointTargets, or an ordered mapping name -> JointTarget (names default to
+                        'st000', 'st001', ...; they name the directories save() writes).  All share targets, x axes,
+                        plugin parameters and -- with the pool's priors -- the covariance model of every target;
+                        they differ in obsdata.y and obsdata.yerr.  Anything else: ValueError naming station and property.
+    chains_per_station  default initparams['nchains']
+    random_seeds        one per station: station s gets exactly the chain seeds of
+                        ChainPool(random_seed=random_seeds[s], nchains=chains_per_station), so a station's chains do
+                        not depend on which other stations share the pool.  A single number or None: every station
+                        draws from the next values of RandomState(random_seeds).
+    seeds               [nstations][chains_per_station] explicit chain seeds instead
+    evaluator           None: the GPU (one evaluation plan per chain group, carrying every station's observations);
+                        a function (packed, nlay, noise, station[B]) -> (logL, misfits); a function of three
+                        arguments or an object with buffers/submit/collect is passed to ChainPool as it is
+    groups, nthreads, nmodels, lookahead   as for ChainPool
+    shard               not supported yet (stations would have to be sharded whole): ValueError
+
+    `pool.pool` is the ChainPool of all chains; `station(s)` (index or name) a StationView."""
+
+    def __init__(self, stations, initparams=None, modelpriors=None, chains_per_station=None, random_seeds=None,
+                 seeds=None, evaluator=None, groups=None, nthreads=None, shard=None, nmodels=None, lookahead=None,
+                 device=None):
+        if shard is not None:
+            raise ValueError("StationPool does not take shard=(rank, world) yet: give every rank a StationPool of its "
+                             "own stations")
+        if hasattr(stations, 'keys'):
+            self.names, self.stations = [k for k in stations.keys()], [stations[k] for k in stations.keys()]
+        else:
+            self.stations = list(stations)
+            self.names = ['st%03d' % s for s in range(len(self.stations))]
+        if not self.stations:
+            raise ValueError("no station")
+        if len(set(self.names)) != len(self.names):
+            raise ValueError("station names must be unique")
+        S = self.nstations = len(self.stations)
+        ip = dict(initparams or {})
+        if seeds is not None:
+            seeds = np.asarray(seeds)
+            if seeds.ndim != 2 or seeds.shape[0] != S:
+                raise ValueError("seeds: [nstations][chains_per_station]")
+            if chains_per_station is not None and int(chains_per_station) != seeds.shape[1]:
+                raise ValueError("seeds: [nstations][chains_per_station]")
+            chains_per_station = seeds.shape[1]
+        if chains_per_station is None:
+            chains_per_station = ip.get('nchains', DEFAULT_INITPARAMS['nchains'])
+        c = self.chains_per_station = int(chains_per_station)
+        if c < 1:
+            raise ValueError("chains_per_station < 1")
+        if seeds is None:
+            if random_seeds is None or np.ndim(random_seeds) == 0:
+                rstate = np.random.RandomState(random_seeds)
+                seeds = [[rstate.randint(1000) for _ in range(c)] for _ in range(S)]
+            else:
+                if len(random_seeds) != S:
+                    raise ValueError("random_seeds: one per station")
+                seeds = []
+                for rs in random_seeds:             # ChainPool's own draw (src/mcmcOptimizer.py:133-137)
+                    rstate = np.random.RandomState(rs)
+                    seeds.append([rstate.randint(1000) for _ in range(c)])
+            seeds = np.asarray(seeds)
+        self.station_of_chain = np.repeat(np.arange(S, dtype=np.int32), c)
+        # the covariance model of every station's targets, chosen like ChainPool chooses the first station's
+        priors = dict(DEFAULT_PRIORS)
+        priors.update(modelpriors or {})
+        first = self.stations[0]
+        for name, joint in zip(self.names, self.stations):
+            if joint.ntargets != first.ntargets:
+                raise ValueError("station %r differs from station %r: number of targets (%d, %d)"
+                                 % (name, self.names[0], joint.ntargets, first.ntargets))
+        np_ = noise_priors(priors, first.targets)
+        corrfix, corr = [bool(p[0][0]) for p in np_], [p[0][1] for p in np_]
+        rcond = ip.get('rcond', DEFAULT_INITPARAMS['rcond'])
+        for joint in self.stations[1:]:
+            joint.set_target_covariance(corrfix, corr, rcond)
+        first.set_target_covariance(corrfix, corr, rcond)
+        check_stations(self.names, self.stations)
+        if evaluator is None:
+            evaluator = StationGpuEvaluator(self.stations, self.station_of_chain, device)
+        elif not hasattr(evaluator, 'submit') and _takes_station(evaluator):
+            evaluator = StationCallEvaluator(evaluator, self.station_of_chain)
+        self.pool = ChainPool(first, initparams=ip, modelpriors=modelpriors, nchains=S * c, seeds=seeds.reshape(-1),
+                              evaluator=evaluator, groups=groups, nthreads=nthreads, nmodels=nmodels,
+                              lookahead=lookahead)
+        self.evaluator = self.pool.evaluator
+
+    # -- the pool of all chains -----------------------------------------------------------------
+    def run(self, progress=None):
+        self.pool.run(progress)
+        return self
+
+    def close(self):
+        self.pool.close()
+
+    @property
+    def closed(self):
+        return self.pool.closed
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    @property
+    def nchains(self):
+        return self.pool.nchains
+
+    @property
+    def seconds(self):
+        return self.pool.seconds
+
+    @property
+    def evaluated(self):
+        return self.pool.evaluated
+
+    def advance(self):
+        return self.pool.advance()
+
+    def counters(self):
+        return self.pool.counters()
+
+    # -- per station ------------------------------------------------------------------------------
+    def station(self, s):
+        """The chains of station `s` (index or name) as a ChainPool-like view."""
+        if not isinstance(s, (int, np.integer)) or isinstance(s, bool):
+            if s not in self.names:
+                raise KeyError("no station %r" % (s,))
+            s = self.names.index(s)
+        if not 0 <= s < self.nstations:
+            raise IndexError("station %d of %d" % (s, self.nstations))
+        return StationView(self, int(s))
+
+    def save(self, savepath=None):
+        """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone
+        writes (data/c%03d_... numbered from 0, data/<station name>_config.pkl with the station's targets).
+        -> number of .npy files written."""
+        savepath = savepath or self.pool.initparams['savepath']
+        written = 0
+        for s, name in enumerate(self.names):
+            written += self.station(s).save(os.path.join(savepath, str(name)))
+        return written

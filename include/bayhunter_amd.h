@@ -234,6 +234,26 @@ int bh_likelihood_stage(int stages, int B, int ntargets, const bh_like_target *t
                         const double *noise, const double *aux, double *logL, double *misfits,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* Observation sets: the same likelihood for rows that are compared with DIFFERENT observed data -- the chains of
+ * many stations (or nodes of a dispersion map) in one batch.  All sets share the targets, their columns and their
+ * covariance models; they differ in the observed values and their errors:
+ *   obs_id[B]                  int32, the set of each row (NULL: every row takes set 0; required with nsets > 1)
+ *   yobs[nsets][set_stride]    a set's observed data laid out like an output row (set_stride >= off + n of every target)
+ *   set_scale[nsets][set_stride]  scaled_err of the BH_COV_NOCORR_SCALED targets, in the targets' own columns
+ *   set_logdet[nsets][ntargets]   log(prod(scaled_err)) of those targets (other entries are not read)
+ * set_scale and set_logdet come together; they are required when nsets > 1 and a target is BH_COV_NOCORR_SCALED, and
+ * when they are NULL such a target takes aux + aux_off and logdet_extra as in bh_likelihood_stage.  The dense R^-1 of
+ * a BH_COV_GAUSS target depends on the fixed correlation and n only: `aux` holds ONE copy for all sets.
+ * A row's result is bit for bit what bh_likelihood_stage gives for it with its own set's yobs: a model's likelihood
+ * depends neither on the batch it is in nor on the sets of its neighbours.  A row whose obs_id is outside
+ * [0, nsets) gets the failed-model result (logL = -1e15, misfits 1e15); nothing is read out of bounds for it.
+ * bh_likelihood_stage(...) = bh_likelihood_sets(..., nsets = 1, obs_id = NULL, yobs, out_stride, NULL, NULL, ...). */
+int bh_likelihood_sets(int stages, int B, int ntargets, const bh_like_target *targets, const double *out,
+                       int out_stride, const int *err, int nflags, int nsets, const int *obs_id, const double *yobs,
+                       int set_stride, const double *set_scale, const double *set_logdet, const double *noise,
+                       const double *aux, double *logL, double *misfits, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 /* ---- single-model drop-ins (host pointers, synchronous) --------------------------------- */
 /* Same argument list as the f2py wrapper of `subroutine surfdisp96`; model arrays are real*4 with
  * at least nlayer valid entries, t/cg real*8 with at least kmax entries.  *err as the reference. */
@@ -395,7 +415,8 @@ int  bh_chains_draw(bh_chain_pool *pool, int chain, int kind, double a, double b
  *     bh_chains_accept(pool, results, results + count); }
  *
  * Staging layout (max_models rows each): packed [rows][4][Lmax] doubles (h, vp, vs, rho: model_stride =
- * 4*Lmax), noise [rows][2*ntargets], nlay [rows] int32, chain [rows] int32 (not sent to the device).
+ * 4*Lmax), noise [rows][2*ntargets], nlay [rows] int32, chain [rows] int32 (not sent to the device; with
+ * bh_eval_set_observations the set of each row's chain is).
  * results: logL[count] followed by misfits[count][ntargets+1] of the last submission.
  * row / out_off / off describe one output row exactly as for bh_swd_batch, bh_rf_batch and
  * bh_likelihood_batch; periods, yobs[row] and aux[naux] are HOST arrays, copied once.  A dispersion target
@@ -430,6 +451,16 @@ int  bh_eval_buffers(bh_eval_plan *plan, double **packed, int **nlay, double **n
                      double **results);
 int  bh_eval_submit(bh_eval_plan *plan, int count);
 int  bh_eval_wait(bh_eval_plan *plan, int *count);   /* blocks until the last submission has landed */
+/* Observation sets for a plan (bh_likelihood_sets): the chains behind the plan belong to `nsets` stations.
+ * yobs[nsets][row], set_scale[nsets][row], set_logdet[nsets][ntargets] as for bh_likelihood_sets with set_stride = row
+ * (set_scale / set_logdet may both be NULL when no target is BH_COV_NOCORR_SCALED); set_of_chain[nchains] is the set
+ * of each chain that bh_chains_propose may name in chain[].  HOST arrays, copied once; they replace the yobs of
+ * bh_eval_create.  Callable once, between bh_eval_create and the first bh_eval_submit.  From then on bh_eval_submit
+ * maps chain[k] -> set for every row of the batch (with a look-ahead a chain has several rows, each with its own
+ * chain[k]), uploads one int per row with the batch and the likelihood subtracts each row's own set.  All arguments
+ * are checked before the first device call. */
+int  bh_eval_set_observations(bh_eval_plan *plan, int nsets, const double *yobs, const double *set_scale,
+                              const double *set_logdet, const int *set_of_chain, int nchains);
 /* How many plans take turns on the device (a pool's chain groups; default 1): passed on as bh_swd_hint's second
  * argument with every submission. */
 int  bh_eval_set_concurrency(bh_eval_plan *plan, int plans_in_flight);
