@@ -137,7 +137,8 @@ BH_DEV cd operator/(cd x, cd y)
 BH_DEV cd rdiv(double x, cd y) { return mk(x, 0.0) / y; }
 // Fast reciprocal / square root for the tolerance-checked receiver-function recursion: hardware
 // seed (v_rcp_f64 / v_rsq_f64) + Newton steps, ~1 ulp, half the instructions of the IEEE sequences.
-// Arguments there are well scaled (1e-6..1e6) and non-zero.
+// Arguments there are well scaled (1e-6..1e6) and non-zero: fsqrt has no select for a zero or negative
+// argument (it is only asked for |z| of a slowness, which cannot vanish; a NaN stays a NaN).
 #if defined(BH_HOSTSIM)
 BH_DEV double frcp(double x) { return 1.0 / x; }
 BH_DEV double fsqrt(double x) { return sqrt(x); }
@@ -156,11 +157,33 @@ BH_DEV double fsqrt(double x)
     double r = __builtin_fma(-h, g, 0.5);
     g = __builtin_fma(g, r, g);
     h = __builtin_fma(h, r, h);
-    double d = __builtin_fma(-g, g, x);
-    g = __builtin_fma(d, h, g);
-    return (x > 0.0) ? g : ((x == 0.0) ? 0.0 : __builtin_nan(""));
+    return __builtin_fma(__builtin_fma(-g, g, x), h, g);
 }
 #endif
+
+// Products of the receiver-function recursion as explicit multiply-add chains.  Left to contraction, a sum
+// of two complex products becomes two contracted halves and a separate add (five instructions per
+// component instead of four); written out, a product is 2 mul + 2 fma and every further term 4 fma.  The
+// first factor may be real (the interface coefficients of a stack without post-critical waves).
+BH_DEV cd cmul(cd a, cd b)
+{
+    return mk(__builtin_fma(a.re, b.re, -(a.im * b.im)), __builtin_fma(a.re, b.im, a.im * b.re));
+}
+BH_DEV cd cmul(double a, cd b) { return mk(a * b.re, a * b.im); }
+BH_DEV cd cmadd(cd acc, cd a, cd b)               // acc + a*b
+{
+    return mk(__builtin_fma(a.re, b.re, __builtin_fma(-a.im, b.im, acc.re)),
+              __builtin_fma(a.re, b.im, __builtin_fma(a.im, b.re, acc.im)));
+}
+BH_DEV cd cmadd(cd acc, double a, cd b) { return mk(__builtin_fma(a, b.re, acc.re), __builtin_fma(a, b.im, acc.im)); }
+BH_DEV cd cmsub(cd acc, cd a, cd b)               // acc - a*b
+{
+    return mk(__builtin_fma(-a.re, b.re, __builtin_fma(a.im, b.im, acc.re)),
+              __builtin_fma(-a.re, b.im, __builtin_fma(-a.im, b.re, acc.im)));
+}
+BH_DEV cd cmsub(cd acc, double a, cd b) { return mk(__builtin_fma(-a, b.re, acc.re), __builtin_fma(-a, b.im, acc.im)); }
+BH_DEV cd cmadd(double acc, cd a, cd b) { return cmadd(mk(acc, 0.0), a, b); }
+BH_DEV cd cmadd(double acc, double a, cd b) { return mk(__builtin_fma(a, b.re, acc), a * b.im); }
 
 // 1/z = conj(z)/|z|^2: one real reciprocal instead of Smith's three divisions
 BH_DEV cd crecip(cd z)
@@ -244,37 +267,12 @@ BH_DEV cm2 operator+(const cm2 &x, const cm2 &y)
     return r;
 }
 
-// real 2x2 times / plus complex 2x2: the interface coefficient matrices of a model are real when no
-// wave is post-critical anywhere in the stack (the teleseismic case), and a complex product with a
-// zero imaginary part is the real one
+// real 2x2: the interface coefficient matrices of a model are real when no wave is post-critical anywhere
+// in the stack (the teleseismic case), and a complex product with a zero imaginary part is the real one
+// (cmul / cmadd / cmsub with a real first factor)
 struct rm2 {
     double c11, c12, c21, c22;
 };
-BH_DEV cm2 operator*(const rm2 &x, const cm2 &y)
-{
-    cm2 r;
-    r.c11 = y.c11 * x.c11 + y.c21 * x.c12;
-    r.c12 = y.c12 * x.c11 + y.c22 * x.c12;
-    r.c21 = y.c11 * x.c21 + y.c21 * x.c22;
-    r.c22 = y.c12 * x.c21 + y.c22 * x.c22;
-    return r;
-}
-BH_DEV cm2 operator*(const cm2 &x, const rm2 &y)
-{
-    cm2 r;
-    r.c11 = x.c11 * y.c11 + x.c12 * y.c21;
-    r.c12 = x.c11 * y.c12 + x.c12 * y.c22;
-    r.c21 = x.c21 * y.c11 + x.c22 * y.c21;
-    r.c22 = x.c21 * y.c12 + x.c22 * y.c22;
-    return r;
-}
-BH_DEV cm2 operator+(const rm2 &x, const cm2 &y)
-{
-    cm2 r;
-    r.c11 = mk(x.c11 + y.c11.re, y.c11.im); r.c12 = mk(x.c12 + y.c12.re, y.c12.im);
-    r.c21 = mk(x.c21 + y.c21.re, y.c21.im); r.c22 = mk(x.c22 + y.c22.re, y.c22.im);
-    return r;
-}
 
 #if !defined(BH_HOSTSIM)
 #pragma clang fp contract(off)

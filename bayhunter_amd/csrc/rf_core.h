@@ -52,11 +52,19 @@ struct RfLaunch {
 
 // LDS block of one model, in doubles.  The FFT buffer [0, 2*nsamp) overlays the spectrum and -- once
 // P3 is over -- the parameter/coefficient region.
-// doubles between the coefficient blocks of consecutive interfaces: 32 used + 2, so that the lanes of
-// phase 2 (one per interface) do not all store into the same banks (32 doubles = one bank row)
-enum { RF_COEF = 34 };
+// One record of RF_REC doubles per layer: the layer's parameters, then rd, td, ru, tu of the interface
+// above it.  Phase 3 walks the stack with one pointer and reads everything of a (frequency, layer) step at
+// constant offsets from it (all lanes of a model the same addresses: broadcasts).  41 doubles are used;
+// with 42 the lanes of phases 1 and 2 (one per layer) store ten 8-byte banks apart, none onto another's
+// for the first sixteen layers.
+enum { RF_REC = 42,
+       RF_P_D = 0, RF_P_IVP2 = 1, RF_P_IVS2 = 2,      // thickness, 1/vp^2, 1/vs^2: every step of phase 3
+       RF_P_AP = 3, RF_P_AS = 4,                      // 1/(pi qp), 1/(pi qs)
+       RF_P_VP = 5, RF_P_VS = 6, RF_P_RHO = 7,        // phase 2 only
+       RF_P_REAL = 8,                                 // interface coefficients real?
+       RF_P_COEF = 9 };                               // rd, td, ru, tu: 4 x 8 doubles
 struct RfLayout {
-    int L, off_par, off_coef, off_sc, per_model;
+    int L, off_par, off_sc, per_model;
 };
 BH_HD RfLayout rf_layout(int Lmax, int nsamp)
 {
@@ -64,11 +72,9 @@ BH_HD RfLayout rf_layout(int Lmax, int nsamp)
     int nfreq = nsamp / 2 + 1;
     lo.L = Lmax;
     // the spectrum occupies elements 0 .. n/2 of the (swizzled, rf_swz) FFT buffer: element n/2 may
-    // land anywhere in its 16-element row, so the parameters start behind that row
-    lo.off_par = 2 * (nfreq + 15);     // [9][L]: d, vp, vs, rho, 1/(pi qp), 1/(pi qs), 1/vp^2, 1/vs^2,
-                                       //         interface coefficients real?
-    lo.off_coef = lo.off_par + 9 * Lmax; // [L][RF_COEF]: rd, td, ru, tu of interface i (above layer i)
-    lo.off_sc = lo.off_coef + RF_COEF * Lmax; // 16 scalars
+    // land anywhere in its 16-element row, so the layer records start behind that row
+    lo.off_par = 2 * (nfreq + 15);              // [L][RF_REC]
+    lo.off_sc = lo.off_par + RF_REC * Lmax;     // 16 scalars
     int need = lo.off_sc + 16;
     lo.per_model = need > 2 * nsamp ? need : 2 * nsamp;
     // A wave of phase 3 that straddles two models reads the same offsets of both blocks.  With a block
@@ -100,13 +106,6 @@ BH_DEV rm2 ld_m2(const double *p, const rm2 *)          // the real parts of a s
     rm2 m;
     m.c11 = p[0]; m.c12 = p[2]; m.c21 = p[4]; m.c22 = p[6];
     return m;
-}
-BH_DEV cm2 to_cm2(const cm2 &m) { return m; }
-BH_DEV cm2 to_cm2(const rm2 &m)
-{
-    cm2 r;
-    r.c11 = mk(m.c11, 0.); r.c12 = mk(m.c12, 0.); r.c21 = mk(m.c21, 0.); r.c22 = mk(m.c22, 0.);
-    return r;
 }
 BH_DEV cm2 cm2_zero()
 {
@@ -144,17 +143,17 @@ BH_DEV void rf_phase1_layer(double *S, const RfLayout &lo, int nlay, int i, cons
         zb = R * log(q);
         thick = zb - z;
     }
-    double *par = S + lo.off_par;
-    par[0 * lo.L + i] = thick;
-    par[1 * lo.L + i] = lvp;
-    par[2 * lo.L + i] = lvs;
-    par[3 * lo.L + i] = lrh;
+    double *par = S + lo.off_par + RF_REC * i;
+    par[RF_P_D] = thick;
+    par[RF_P_VP] = lvp;
+    par[RF_P_VS] = lvs;
+    par[RF_P_RHO] = lrh;
     // Q enters every frequency only through 1/(pi Q) and 1/(2 Q) = (pi/2) / (pi Q) (Mueller 1985
     // eq. 132, greens.cpp:539-540): keep the reciprocal, and 1/v^2 for the shared-Q form of phase 3
-    par[4 * lo.L + i] = frcp(BH_PI * (qp ? qp[i] : 500.0));      // rfmini_modrf.py:119-120
-    par[5 * lo.L + i] = frcp(BH_PI * (qs ? qs[i] : 225.0));
-    par[6 * lo.L + i] = frcp(lvp * lvp);
-    par[7 * lo.L + i] = frcp(lvs * lvs);
+    par[RF_P_AP] = frcp(BH_PI * (qp ? qp[i] : 500.0));      // rfmini_modrf.py:119-120
+    par[RF_P_AS] = frcp(BH_PI * (qs ? qs[i] : 225.0));
+    par[RF_P_IVP2] = frcp(lvp * lvp);
+    par[RF_P_IVS2] = frcp(lvs * lvs);
 }
 
 // ---- P2: interface coefficients ---------------------------------------------------------------------
@@ -243,24 +242,25 @@ BH_DEV cm2 rf_displacement2(double p, double vp, double vs)
 BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int i,
                                 double vp0_in, double vs0_in)
 {
-    const double *par = S + lo.off_par;
-    double *coef = S + lo.off_coef + RF_COEF * i;
+    double *lay = S + lo.off_par;                       // layer k: lay + RF_REC * k
+    double *rec = lay + RF_REC * i, *coef = rec + RF_P_COEF;
     cm2 rd = cm2_zero(), td = cm2_zero(), ru = cm2_zero(), tu = cm2_zero();
     double u = P.slowness;
     if (i == 0) {
-        rf_coeffs(u, par[1 * lo.L], par[2 * lo.L], ru);
+        rf_coeffs(u, lay[RF_P_VP], lay[RF_P_VS], ru);
         // per-model scalars
         double *sc = S + lo.off_sc;
-        st_cm2(sc + RF_SC_H2, rf_displacement2(u, par[1 * lo.L], par[2 * lo.L]));
+        st_cm2(sc + RF_SC_H2, rf_displacement2(u, lay[RF_P_VP], lay[RF_P_VS]));
         double t0 = 0.;                         // greens.cpp:510-526 (includes half-space d = -1)
-        const double *v = par + (P.waveno == 0 ? 1 : 2) * lo.L;
-        for (int k = 0; k < nlay; k++) t0 += par[k] * sqrt(1. / (v[k] * v[k]) - P.p2);
+        const double *v = lay + (P.waveno == 0 ? RF_P_VP : RF_P_VS);
+        for (int k = 0; k < nlay; k++)
+            t0 += lay[RF_REC * k + RF_P_D] * sqrt(1. / (v[RF_REC * k] * v[RF_REC * k]) - P.p2);
         sc[RF_SC_T0] = t0;
         // one Q for all layers (what BayHunter passes): the complex velocity factor is then the same
         // for every layer of a frequency
         bool uniform = true;
         for (int k = 1; k < nlay - 1; k++)
-            uniform = uniform && par[4 * lo.L + k] == par[4 * lo.L] && par[5 * lo.L + k] == par[5 * lo.L];
+            uniform = uniform && lay[RF_REC * k + RF_P_AP] == lay[RF_P_AP] && lay[RF_REC * k + RF_P_AS] == lay[RF_P_AS];
         sc[RF_SC_UNIFORM_Q] = uniform ? 1.0 : 0.0;
         // rotation velocities: wrap.cpp:13,73-74 with rfmini_modrf.py:125-130
         double sigma = P.sigma;
@@ -279,8 +279,8 @@ BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P
         sc[RF_SC_M22] = (1. - 2. * vst * vst * pp * pp) / (vst * b);
         sc[RF_SC_DECOMP] = (double)dec;
     } else {
-        rf_coeffm(u, par[1 * lo.L + i - 1], par[2 * lo.L + i - 1], par[3 * lo.L + i - 1],
-                  par[1 * lo.L + i], par[2 * lo.L + i], par[3 * lo.L + i], rd, td, ru, tu);
+        rf_coeffm(u, rec[RF_P_VP - RF_REC], rec[RF_P_VS - RF_REC], rec[RF_P_RHO - RF_REC],
+                  rec[RF_P_VP], rec[RF_P_VS], rec[RF_P_RHO], rd, td, ru, tu);
     }
     st_cm2(coef, rd); st_cm2(coef + 8, td); st_cm2(coef + 16, ru); st_cm2(coef + 24, tu);
     const cm2 *four[4] = {&rd, &td, &ru, &tu};
@@ -288,7 +288,7 @@ BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P
     for (int k = 0; k < 4; k++)
         real = real && four[k]->c11.im == 0. && four[k]->c12.im == 0. && four[k]->c21.im == 0. &&
                four[k]->c22.im == 0.;
-    S[lo.off_par + 8 * lo.L + i] = real ? 1.0 : 0.0;
+    rec[RF_P_REAL] = real ? 1.0 : 0.0;
 }
 
 // ---- P3: one frequency of one model (greens.cpp:528-585 + compute_rf :377-395) ----------------------
@@ -313,65 +313,94 @@ BH_DEV RfFreq rf_freq_load(const double *BH_RESTRICT ftab, int j)
 #if !defined(BH_HOSTSIM)
 #pragma clang fp contract(fast)
 #endif
+// One layer of the top-down recursion (greens.cpp:196-224, 829-845) for the phase factors e11, e22 of the
+// layer, the interface matrices ci above and cn below it.  With E = diag(e11, e22):
+//     nt = ru + td (nb q)'            reflection seen from the top of the layer ((nb q)' of the layer above)
+//     nb = E nt E                     ... from its bottom
+//     q  = (I - rd nb)^-1 tu          transmission through the interface below
+//     g  = g' E q
+// carried as m = E nt and t = E q: then nb = m E, nb q = m t and g = g' t, and the reciprocal determinant
+// goes into t's two row factors (e11 / det, e22 / det) instead of into the four entries of the inverse --
+// fifteen complex products of phase factors per layer become fourteen, none of them a square of e, and the
+// state that lives across the next layer's square roots and exponentials is m, t and g.
+// FIRST: the layer under the free surface, nt = ru (real in the real-coefficient path) and g = t.
+template <class M, bool FIRST>
+BH_DEV void rf_layer_step(const double *ci, const double *cn, cd e11, cd e22, cm2 &m, cm2 &t, cm2 &g)
+{
+    const M ru = ld_m2(ci + 16, (const M *)nullptr);
+    if (FIRST) {
+        m.c11 = cmul(ru.c11, e11); m.c12 = cmul(ru.c12, e11);
+        m.c21 = cmul(ru.c21, e22); m.c22 = cmul(ru.c22, e22);
+    } else {
+        const M td = ld_m2(ci + 8, (const M *)nullptr);
+        cm2 w;                                                   // nb q of the layer above
+        w.c11 = cmadd(cmul(m.c11, t.c11), m.c12, t.c21); w.c12 = cmadd(cmul(m.c11, t.c12), m.c12, t.c22);
+        w.c21 = cmadd(cmul(m.c21, t.c11), m.c22, t.c21); w.c22 = cmadd(cmul(m.c21, t.c12), m.c22, t.c22);
+        cm2 nt;
+        nt.c11 = cmadd(cmadd(ru.c11, td.c11, w.c11), td.c12, w.c21);
+        nt.c12 = cmadd(cmadd(ru.c12, td.c11, w.c12), td.c12, w.c22);
+        nt.c21 = cmadd(cmadd(ru.c21, td.c21, w.c11), td.c22, w.c21);
+        nt.c22 = cmadd(cmadd(ru.c22, td.c21, w.c12), td.c22, w.c22);
+        m.c11 = cmul(e11, nt.c11); m.c12 = cmul(e11, nt.c12);
+        m.c21 = cmul(e22, nt.c21); m.c22 = cmul(e22, nt.c22);
+    }
+    cm2 nb;
+    nb.c11 = cmul(m.c11, e11); nb.c12 = cmul(m.c12, e22); nb.c21 = cmul(m.c21, e11); nb.c22 = cmul(m.c22, e22);
+    const M rd = ld_m2(cn, (const M *)nullptr), tu = ld_m2(cn + 24, (const M *)nullptr);
+    cm2 x;                                                       // I - rd nb
+    x.c11 = cmsub(cmsub(mk(1., 0.), rd.c11, nb.c11), rd.c12, nb.c21);
+    x.c12 = cmsub(cmsub(mk(0., 0.), rd.c11, nb.c12), rd.c12, nb.c22);
+    x.c21 = cmsub(cmsub(mk(0., 0.), rd.c21, nb.c11), rd.c22, nb.c21);
+    x.c22 = cmsub(cmsub(mk(1., 0.), rd.c21, nb.c12), rd.c22, nb.c22);
+    const cd qi = crecip(cmsub(cmul(x.c11, x.c22), x.c12, x.c21));
+    const cd p1 = cmul(qi, e11), p2 = cmul(qi, e22);
+    cm2 a;                                                       // adj(x) tu, tu as the first (real) factor
+    a.c11 = cmsub(cmul(tu.c11, x.c22), tu.c21, x.c12); a.c12 = cmsub(cmul(tu.c12, x.c22), tu.c22, x.c12);
+    a.c21 = cmsub(cmul(tu.c21, x.c11), tu.c11, x.c21); a.c22 = cmsub(cmul(tu.c22, x.c11), tu.c12, x.c21);
+    t.c11 = cmul(p1, a.c11); t.c12 = cmul(p1, a.c12); t.c21 = cmul(p2, a.c21); t.c22 = cmul(p2, a.c22);
+    if (FIRST) {
+        g = t;
+    } else {
+        cm2 gn;
+        gn.c11 = cmadd(cmul(g.c11, t.c11), g.c12, t.c21); gn.c12 = cmadd(cmul(g.c11, t.c12), g.c12, t.c22);
+        gn.c21 = cmadd(cmul(g.c21, t.c11), g.c22, t.c21); gn.c22 = cmadd(cmul(g.c21, t.c12), g.c22, t.c22);
+        g = gn;
+    }
+}
+
 template <class M>
 BH_DEV cd rf_phase3_body(const double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int j,
                          const RfFreq &F, cd *zr_r, cd *zr_z)
 {
-    const double *par = S + lo.off_par;
-    const double *coef = S + lo.off_coef;
+    const double *lay = S + lo.off_par;                 // the record of layer i; the next one's coefficients
     const double *sc = S + lo.off_sc;
     const double w = P.dw * j;
     const double lgw = F.lgw;
-    cm2 nb = cm2_zero(), q = cm2_zero(), g = cm2_zero();
+    cm2 m = cm2_zero(), tq = cm2_zero(), g = cm2_zero();
     // complex velocity v (1 + ln(w/wref)/(pi Q) + i/(2 Q)), Mueller (1985) eq. 132: 1/v_c^2 =
     // (1/v^2) * 1/f^2 with f the bracket; with one Q for all layers f is a per-frequency constant
     const bool uniform = sc[RF_SC_UNIFORM_Q] != 0.0;
     cd gp, gs;
     {
-        const double ap = par[4 * lo.L], as = par[5 * lo.L];
+        const double ap = lay[RF_P_AP], as = lay[RF_P_AS];
         cd fp = mk(1. + lgw * ap, ap * (0.5 * BH_PI)), fs = mk(1. + lgw * as, as * (0.5 * BH_PI));
         gp = crecip(fp * fp);
         gs = crecip(fs * fs);
     }
-    for (int i = 0; i < nlay - 1; i++) {        // reference layer index i+1 = 1 .. nlay-1
-        const double wd = w * par[i];               // exp(-i w d * slowness): (-i wd)(a + ib) = wd b - i wd a
+    for (int i = 0; i < nlay - 1; i++, lay += RF_REC) {        // reference layer index i+1 = 1 .. nlay-1
+        const double wd = w * lay[RF_P_D];              // exp(-i w d * slowness): (-i wd)(a + ib) = wd b - i wd a
         if (!uniform && i > 0) {                // this layer has its own Q
-            const double ap = par[4 * lo.L + i], as = par[5 * lo.L + i];
+            const double ap = lay[RF_P_AP], as = lay[RF_P_AS];
             cd fp = mk(1. + lgw * ap, ap * (0.5 * BH_PI)), fs = mk(1. + lgw * as, as * (0.5 * BH_PI));
             gp = crecip(fp * fp);
             gs = crecip(fs * fs);
         }
-        cd plc = csqrt_fast(gp * par[6 * lo.L + i] - P.p2);         // Q finite -> im != 0
-        cd slc = csqrt_fast(gs * par[7 * lo.L + i] - P.p2);
-#if defined(BH_RF_OLD_CEXP)                        // (A/B switch: the general complex product and the clamped exp)
-        cd e11 = cexp_(mk(0., -wd) * plc), e22 = cexp_(mk(0., -wd) * slc);
-#else
+        cd plc = csqrt_fast(gp * lay[RF_P_IVP2] - P.p2);         // Q finite -> im != 0
+        cd slc = csqrt_fast(gs * lay[RF_P_IVS2] - P.p2);
         cd e11 = cexp_bounded(mk(wd * plc.im, -(wd * plc.re))), e22 = cexp_bounded(mk(wd * slc.im, -(wd * slc.re)));
-#endif
-        const double *ci = coef + RF_COEF * i, *cn = coef + RF_COEF * (i + 1);
-        cm2 nt;
-        if (i == 0) nt = to_cm2(ld_m2(ci + 16, (const M *)nullptr));                   // nt = ru[1]
-        else nt = ld_m2(ci + 16, (const M *)nullptr) + (ld_m2(ci + 8, (const M *)nullptr) * nb) * q;     // ru + td*nb*q
-        {   // nb = e*nt*e, greens.cpp:829-845
-            cd e12 = e11 * e22, e11s = e11 * e11, e22s = e22 * e22;
-            nb.c11 = nt.c11 * e11s; nb.c12 = nt.c12 * e12; nb.c21 = nt.c21 * e12; nb.c22 = nt.c22 * e22s;
-        }
-        {   // q = inv(I - rd[i+1]*nb) * tu[i+1]
-            cm2 x = ld_m2(cn, (const M *)nullptr) * nb;
-            x.c11 = mk(1., 0.) - x.c11; x.c12 = mk(0., 0.) - x.c12;
-            x.c21 = mk(0., 0.) - x.c21; x.c22 = mk(1., 0.) - x.c22;
-            cd qi = crecip(x.c11 * x.c22 - x.c12 * x.c21);
-            cm2 inv;
-            inv.c11 = qi * x.c22; inv.c12 = (-qi) * x.c12; inv.c21 = (-qi) * x.c21; inv.c22 = qi * x.c11;
-            q = inv * ld_m2(cn + 24, (const M *)nullptr);
-        }
-        if (i == 0) {                                             // g = e*q
-            g.c11 = e11 * q.c11; g.c12 = e11 * q.c12; g.c21 = e22 * q.c21; g.c22 = e22 * q.c22;
-        } else {                                                  // g = (g*e)*q
-            cm2 ge;
-            ge.c11 = g.c11 * e11; ge.c12 = g.c12 * e22; ge.c21 = g.c21 * e11; ge.c22 = g.c22 * e22;
-            g = ge * q;
-        }
+        const double *ci = lay + RF_P_COEF, *cn = ci + RF_REC;
+        if (i == 0) rf_layer_step<M, true>(ci, cn, e11, e22, m, tq, g);
+        else rf_layer_step<M, false>(ci, cn, e11, e22, m, tq, g);
     }
     cm2 t = ld_cm2(sc + RF_SC_H2) * g;                            // t = 2*h*g[nlay-1]
     cd cr, cz;
@@ -408,9 +437,9 @@ BH_DEV cd rf_phase3_task(const double *S, const RfLayout &lo, const RfLaunch &P,
 {
     // all interface matrices of this model real (no post-critical wave anywhere): half the
     // multiplications in the products with rd, td, ru, tu
-    const double *flag = S + lo.off_par + 8 * lo.L;
+    const double *flag = S + lo.off_par + RF_P_REAL;
     bool real = true;
-    for (int i = 0; i < nlay; i++) real = real && flag[i] != 0.0;
+    for (int i = 0; i < nlay; i++) real = real && flag[RF_REC * i] != 0.0;
     return real ? rf_phase3_body<rm2>(S, lo, P, nlay, j, F, zr_r, zr_z)
                 : rf_phase3_body<cm2>(S, lo, P, nlay, j, F, zr_r, zr_z);
 }
