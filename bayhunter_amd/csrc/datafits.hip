@@ -5,38 +5,27 @@
 // Y[nrows, stride] (ForwardEngine's `out`, first ncols columns), is reduced per column over rows that each
 // carry an integer weight, without expanding them.
 //
-//   mask    one wave per row: the row's weight, or 0 when any of its err flags is non-zero or any of its
-//           ncols values is NaN (excluded); weighted totals of included / excluded rows, negative weights
-//   scan    per column: min / max (order-preserving integer keys, integer atomics), Σ w·y (per-block slab
-//           reduced in a fixed order)
-//   finish  Σ w·(y - mean)² (slab), the histogram over per-column edges, and up to 16 exact weighted order
-//           statistics: an 8-bit radix select over the 64-bit keys, one pass per digit.  Ranks whose prefixes
-//           still agree share one digit histogram ("group"); a block keeps kGroups groups of its kCols columns
-//           in LDS and the groups beyond that are spread over blockIdx.z
+// carry an integer weight, without expanding them.  The shared parts of that weighted column reduction are in
+// stats_core.h / stats_host.h (keys, slabs, the scan / finish hand-over, the radix select); this file has what
+// is its own:
 //
-// Layout: a block is kCols columns (blockIdx.y) x 32 row lanes; 8 lanes of a wave read 64 contiguous bytes
-// of a row.  The grid width depends on nrows only, so the slab order -- and every result -- is the same
-// from one call to the next.  No floating-point atomics.
-#include <hip/hip_runtime.h>
-#include <cmath>
+//   mask    before the scan, one wave per row: the row's weight, or 0 when any of its err flags is non-zero
+//           or any of its ncols values is NaN (excluded); weighted totals of included / excluded rows,
+//           negative weights
+//   layout  a block is kCols columns (blockIdx.y) x 32 row lanes; 8 lanes of a wave read 64 contiguous bytes
+//           of a row
+//   finish  Σ w·(y - mean)² and the histogram over per-column edges in one pass, then the select's passes for
+//           up to 16 ranks over the 64-bit keys: a block keeps kGroups groups of its kCols columns in LDS and
+//           the groups beyond that are spread over blockIdx.z
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <new>
-#include <vector>
-#include "../../include/bayhunter_amd.h"
-#include "posterior_core.h"
-
-namespace bh { int fail_arg_(const char *what); int fail_hip_(int e, const char *what); }
+#include "stats_host.h"
 
 namespace {
 
-#define DF_HIP(call)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) return bh::fail_hip_((int)e_, #call);          \
-    } while (0)
-
-typedef unsigned long long u64;
+using bh::u64;
 constexpr int kThreads = 256;
 constexpr int kCols = 8;                        // columns per blockIdx.y
 constexpr int kRowLanes = kThreads / kCols;     // rows a block reads at once
@@ -228,53 +217,19 @@ __global__ __launch_bounds__(kThreads) void df_kernel(FitArgs a)
     }
 }
 
-// Σ over blocks in block order: one thread per column
-__global__ void df_reduce_kernel(const double *slab, int G, int ncols, double *out)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncols) return;
-    double s = 0.0;
-    for (int g = 0; g < G; g++) s = s + slab[(size_t)g * ncols + c];
-    out[c] = s;
-}
-
-__global__ void df_fill_kernel(u64 *p, long long n, u64 v)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
-bool ascending(const double *v, int n)
-{
-    for (int i = 0; i < n; i++)
-        if (!(v[i] == v[i]) || (i && !(v[i - 1] < v[i]))) return false;
-    return true;
-}
-
 }  // namespace
 
-struct bh_datafits {
-    int ncols = 0, nerr = 0, G = 1, scanned = 0;
+struct bh_datafits : bh::ColumnStats {           // n: the columns
+    int nerr = 0;
     const double *Y = nullptr;
     const int *w = nullptr, *err = nullptr;
     long long nrows = 0, stride = 0;
-    hipStream_t st = nullptr;
-    u64 total = 0;
     // device
     int *wk = nullptr;
-    double *slab = nullptr, *red = nullptr, *dmean = nullptr;
-    u64 *kmin = nullptr, *kmax = nullptr, *cnt = nullptr;
+    u64 *cnt = nullptr;
 };
 
 namespace {
-
-void df_free(bh_datafits *p)
-{
-    void *bufs[] = {p->wk, p->slab, p->red, p->dmean, p->kmin, p->kmax, p->cnt};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    delete p;
-}
 
 FitArgs base_args(const bh_datafits *p)
 {
@@ -283,7 +238,7 @@ FitArgs base_args(const bh_datafits *p)
     a.Y = p->Y;
     a.nrows = p->nrows;
     a.stride = p->stride;
-    a.ncols = p->ncols;
+    a.ncols = p->n;
     a.wk = p->wk;
     a.slab = p->slab;
     return a;
@@ -292,20 +247,9 @@ FitArgs base_args(const bh_datafits *p)
 template <int MODE>
 int launch(bh_datafits *p, const FitArgs &a, int gz, size_t lds)
 {
-    dim3 grid((unsigned)p->G, (unsigned)((p->ncols + kCols - 1) / kCols), (unsigned)gz);
+    dim3 grid((unsigned)p->G, (unsigned)((p->n + kCols - 1) / kCols), (unsigned)gz);
     hipLaunchKernelGGL((df_kernel<MODE>), grid, dim3(kThreads), lds, p->st, a);
-    DF_HIP(hipGetLastError());
-    return BH_OK;
-}
-
-int reduce_slab(bh_datafits *p, std::vector<double> &out)
-{
-    hipLaunchKernelGGL(df_reduce_kernel, dim3((unsigned)((p->ncols + 255) / 256)), dim3(256), 0, p->st,
-                       (const double *)p->slab, p->G, p->ncols, p->red);
-    DF_HIP(hipGetLastError());
-    out.assign(p->ncols, 0.0);
-    DF_HIP(hipMemcpyAsync(out.data(), p->red, sizeof(double) * p->ncols, hipMemcpyDeviceToHost, p->st));
-    DF_HIP(hipStreamSynchronize(p->st));
+    STATS_HIP(hipGetLastError());
     return BH_OK;
 }
 
@@ -328,30 +272,23 @@ int bh_datafits_create(const double *Y, long long nrows, long long stride, int n
         bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
         return BH_ERR_NO_DEVICE;
     }
-    bh_datafits *p = new (std::nothrow) bh_datafits;
+    std::unique_ptr<bh_datafits> p(new (std::nothrow) bh_datafits);
     if (!p) return bh::fail_arg_("out of memory");
     p->Y = Y;
     p->nrows = nrows;
     p->stride = stride;
-    p->ncols = ncols;
+    p->n = ncols;
     p->w = weights;
     p->err = err;
     p->nerr = err ? nerr : 0;
     p->st = (hipStream_t)stream;
     long long g = (nrows + kRowLanes - 1) / kRowLanes;
     p->G = (int)(g < kMaxBlocksX ? g : kMaxBlocksX);
-    auto bail = [&](hipError_t e, const char *what) { df_free(p); return bh::fail_hip_((int)e, what); };
-    hipError_t e;
-#define DF_ALLOC(ptr, bytes) if ((e = hipMalloc((void **)&(ptr), (bytes))) != hipSuccess) return bail(e, "hipMalloc(" #ptr ")")
-    DF_ALLOC(p->wk, sizeof(int) * (size_t)nrows);
-    DF_ALLOC(p->slab, sizeof(double) * (size_t)p->G * ncols);
-    DF_ALLOC(p->red, sizeof(double) * ncols);
-    DF_ALLOC(p->dmean, sizeof(double) * ncols);
-    DF_ALLOC(p->kmin, sizeof(u64) * ncols);
-    DF_ALLOC(p->kmax, sizeof(u64) * ncols);
-    DF_ALLOC(p->cnt, sizeof(u64) * 3);
-#undef DF_ALLOC
-    *fits = p;
+    int rc = p->alloc_columns();
+    if (rc) return rc;
+    STATS_HIP(p->bufs.alloc(p->wk, (size_t)nrows));
+    STATS_HIP(p->bufs.alloc(p->cnt, 3));
+    *fits = p.release();
     return BH_OK;
 }
 
@@ -359,7 +296,7 @@ void bh_datafits_destroy(bh_datafits *fits)
 {
     if (fits) {
         (void)hipStreamSynchronize(fits->st);
-        df_free(fits);
+        delete fits;
     }
 }
 
@@ -367,49 +304,31 @@ int bh_datafits_scan(bh_datafits *p, long long *total, long long *excluded, doub
                      double *mean)
 {
     if (!p) return bh::fail_arg_("fits is NULL");
-    const int N = p->ncols;
-    p->scanned = 0;
-    DF_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 3, p->st));
+    int rc = p->begin_scan();
+    if (rc) return rc;
+    STATS_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 3, p->st));
     {
         long long waves = p->nrows;
         long long blocks = (waves + kThreads / 64 - 1) / (kThreads / 64);
         hipLaunchKernelGGL(df_mask_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kThreads), 0, p->st,
-                           p->Y, p->nrows, p->stride, p->ncols, p->w, p->err, p->nerr, p->wk, p->cnt);
-        DF_HIP(hipGetLastError());
+                           p->Y, p->nrows, p->stride, p->n, p->w, p->err, p->nerr, p->wk, p->cnt);
+        STATS_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(df_fill_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, p->st, p->kmin, (long long)N, ~0ull);
-    hipLaunchKernelGGL(df_fill_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, p->st, p->kmax, (long long)N, 0ull);
-    DF_HIP(hipGetLastError());
     FitArgs a = base_args(p);
     a.kmin = p->kmin;
     a.kmax = p->kmax;
-    int rc = launch<MODE_SCAN>(p, a, 1, 0);
+    rc = launch<MODE_SCAN>(p, a, 1, 0);
     if (rc) return rc;
-    u64 cnt[3];
-    std::vector<u64> kmn(N), kmx(N);
-    DF_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
-    DF_HIP(hipMemcpyAsync(kmn.data(), p->kmin, sizeof(u64) * N, hipMemcpyDeviceToHost, p->st));
-    DF_HIP(hipMemcpyAsync(kmx.data(), p->kmax, sizeof(u64) * N, hipMemcpyDeviceToHost, p->st));
+    u64 cnt[3];                                    // included, excluded weight; rows with a negative weight
+    STATS_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
     std::vector<double> sum;
-    rc = reduce_slab(p, sum);                      // synchronises the stream
+    rc = p->reduce_slab(sum);                      // synchronises the stream
     if (rc) return rc;
-    if (cnt[2]) return bh::fail_arg_("bh_datafits_scan: negative weight");
-    if (excluded) *excluded = (long long)cnt[1];
-    if (total) *total = (long long)cnt[0];
-    if (cnt[0] == 0) return bh::fail_arg_("bh_datafits_scan: empty selection (no included row with a positive weight)");
-    if (cnt[0] > (1ull << 53)) return bh::fail_arg_("bh_datafits_scan: weight total above 2^53");
-    p->total = cnt[0];
-    std::vector<double> mu(N);
-    for (int c = 0; c < N; c++) mu[c] = sum[c] / (double)cnt[0];
-    DF_HIP(hipMemcpyAsync(p->dmean, mu.data(), sizeof(double) * N, hipMemcpyHostToDevice, p->st));
-    DF_HIP(hipStreamSynchronize(p->st));
-    p->scanned = 1;
-    for (int c = 0; c < N; c++) {
-        if (vmin) vmin[c] = bh::post_unkey64(kmn[c]);
-        if (vmax) vmax[c] = bh::post_unkey64(kmx[c]);
-        if (mean) mean[c] = mu[c];
+    if (!cnt[2]) {                                 // reported for an empty selection too: all of it may be excluded
+        if (excluded) *excluded = (long long)cnt[1];
+        if (total) *total = (long long)cnt[0];
     }
-    return BH_OK;
+    return p->end_scan("bh_datafits_scan", cnt[0], cnt[2], sum, vmin, vmax, mean);
 }
 
 int bh_datafits_finish(bh_datafits *p, const long long *ranks, int nranks, double *order_stats,
@@ -425,122 +344,65 @@ int bh_datafits_finish(bh_datafits *p, const long long *ranks, int nranks, doubl
         if (nedges < 2 || nsets < 1 || !eset || !hist)
             return bh::fail_arg_("bh_datafits_finish: edges need nedges >= 2, nsets >= 1, eset and hist");
         for (int s = 0; s < nsets; s++)
-            if (!ascending(edges + (size_t)s * nedges, nedges)) return bh::fail_arg_("bh_datafits_finish: edges must be ascending");
+            if (!bh::ascending(edges + (size_t)s * nedges, nedges)) return bh::fail_arg_("bh_datafits_finish: edges must be ascending");
     }
     if (!p) return bh::fail_arg_("fits is NULL");
     if (!p->scanned) return bh::fail_arg_("bh_datafits_finish before a successful bh_datafits_scan");
-    const int N = p->ncols;
+    const int N = p->n;
     for (int i = 0; i < nranks; i++)
         if ((u64)ranks[i] >= p->total) return bh::fail_arg_("bh_datafits_finish: rank >= the weight total");
     if (want_hist)
         for (int c = 0; c < N; c++)
             if (eset[c] < 0 || eset[c] >= nsets) return bh::fail_arg_("bh_datafits_finish: edge set out of range");
 
-    struct Guard {
-        std::vector<void *> b;
-        ~Guard() { for (void *x : b) if (x) (void)hipFree(x); }
-    } guard;
+    bh::DevBufs tmp;
     const int nb = nedges - 1;
-    FitArgs a = base_args(p);
-    a.mean = p->dmean;
     if (stdev || want_hist) {
+        FitArgs a = base_args(p);
+        a.mean = p->dmean;
         size_t lds = 0;
         if (want_hist) {
             double *ded = nullptr;
             int *dset = nullptr;
-            u64 *dh = nullptr;
-            DF_HIP(hipMalloc((void **)&ded, sizeof(double) * (size_t)nsets * nedges));
-            guard.b.push_back(ded);
-            DF_HIP(hipMalloc((void **)&dset, sizeof(int) * N));
-            guard.b.push_back(dset);
-            DF_HIP(hipMalloc((void **)&dh, sizeof(u64) * (size_t)N * nb));
-            guard.b.push_back(dh);
-            DF_HIP(hipMemcpyAsync(ded, edges, sizeof(double) * (size_t)nsets * nedges, hipMemcpyHostToDevice, p->st));
-            DF_HIP(hipMemcpyAsync(dset, eset, sizeof(int) * N, hipMemcpyHostToDevice, p->st));
-            DF_HIP(hipMemsetAsync(dh, 0, sizeof(u64) * (size_t)N * nb, p->st));
+            STATS_HIP(tmp.alloc(ded, (size_t)nsets * nedges));
+            STATS_HIP(tmp.alloc(dset, N));
+            STATS_HIP(tmp.alloc(a.hist, (size_t)N * nb));
+            STATS_HIP(hipMemcpyAsync(ded, edges, sizeof(double) * (size_t)nsets * nedges, hipMemcpyHostToDevice, p->st));
+            STATS_HIP(hipMemcpyAsync(dset, eset, sizeof(int) * N, hipMemcpyHostToDevice, p->st));
+            STATS_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * (size_t)N * nb, p->st));
             a.edges = ded;
             a.nedges = nedges;
             a.eset = dset;
-            a.hist = dh;
             a.do_hist = 1;
             a.hist_lds = (size_t)kCols * nb * sizeof(u64) <= (size_t)kHistLdsBytes;
             lds = a.hist_lds ? (size_t)kCols * nb * sizeof(u64) : 0;
         }
         int rc = launch<MODE_FINISH>(p, a, 1, lds);
+        if (!rc && stdev) rc = p->read_stdev(stdev);                // either one synchronises the stream
+        if (!rc && want_hist) rc = bh::read_hist(a.hist, (size_t)N * nb, hist, p->st);
         if (rc) return rc;
-        std::vector<double> sq;
-        rc = reduce_slab(p, sq);                   // synchronises the stream
-        if (rc) return rc;
-        if (stdev)
-            for (int c = 0; c < N; c++) stdev[c] = std::sqrt(sq[c] / (double)p->total);
-        if (want_hist) {
-            std::vector<u64> h((size_t)N * nb);
-            DF_HIP(hipMemcpyAsync(h.data(), a.hist, sizeof(u64) * h.size(), hipMemcpyDeviceToHost, p->st));
-            DF_HIP(hipStreamSynchronize(p->st));
-            for (size_t i = 0; i < h.size(); i++) hist[i] = (long long)h[i];
-        }
     }
     if (!nranks) return BH_OK;
 
-    // radix select: per (rank, column) the prefix found so far and the rank left within it
-    const size_t RN = (size_t)nranks * N;
-    std::vector<u64> pfx(RN, 0), rr(RN);
-    for (int i = 0; i < nranks; i++)
-        for (int c = 0; c < N; c++) rr[(size_t)i * N + c] = (u64)ranks[i];
-    int *dgb = nullptr, *dng = nullptr;
-    u64 *dgp = nullptr, *ddig = nullptr;
-    DF_HIP(hipMalloc((void **)&dgb, sizeof(int) * N));
-    guard.b.push_back(dgb);
-    DF_HIP(hipMalloc((void **)&dng, sizeof(int) * N));
-    guard.b.push_back(dng);
-    DF_HIP(hipMalloc((void **)&dgp, sizeof(u64) * RN));
-    guard.b.push_back(dgp);
-    DF_HIP(hipMalloc((void **)&ddig, sizeof(u64) * 256 * RN));
-    guard.b.push_back(ddig);
-    std::vector<int> gb(N), ngr(N), grp(RN);        // grp: the group (slot) of each (rank, column)
-    std::vector<u64> gp(RN), dig;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        // groups: distinct prefixes of the column's ranks
-        int slots = 0, maxg = 0;
-        for (int c = 0; c < N; c++) {
-            gb[c] = slots;
-            int n = 0;
-            for (int i = 0; i < nranks; i++) {
-                const u64 v = pfx[(size_t)i * N + c];
-                int j = 0;
-                while (j < n && gp[slots + j] != v) j++;
-                if (j == n) gp[slots + n++] = v;
-                grp[(size_t)i * N + c] = slots + j;
-            }
-            ngr[c] = n;
-            slots += n;
-            maxg = n > maxg ? n : maxg;
-        }
-        DF_HIP(hipMemcpyAsync(dgb, gb.data(), sizeof(int) * N, hipMemcpyHostToDevice, p->st));
-        DF_HIP(hipMemcpyAsync(dng, ngr.data(), sizeof(int) * N, hipMemcpyHostToDevice, p->st));
-        DF_HIP(hipMemcpyAsync(dgp, gp.data(), sizeof(u64) * slots, hipMemcpyHostToDevice, p->st));
-        DF_HIP(hipMemsetAsync(ddig, 0, sizeof(u64) * 256 * (size_t)slots, p->st));
-        FitArgs r = base_args(p);
-        r.shift = shift;
-        r.gbase = dgb;
-        r.ngroups = dng;
-        r.gpfx = dgp;
-        r.digits = ddig;
-        int rc = launch<MODE_RADIX>(p, r, (maxg + kGroups - 1) / kGroups, sizeof(u64) * kCols * kGroups * 256);
+    uint64_t rk[kMaxRanks];
+    for (int i = 0; i < nranks; i++) rk[i] = (uint64_t)ranks[i];
+    bh::DeviceSelect sel(N, nranks, 64, rk);
+    int rc = sel.alloc(tmp);
+    if (rc) return rc;
+    FitArgs r = base_args(p);
+    r.gbase = sel.dgbase;
+    r.ngroups = sel.dngroups;
+    r.gpfx = sel.dgpfx;
+    r.digits = sel.ddigits;
+    while (!sel.done()) {
+        rc = sel.begin_pass(p->st);
+        r.shift = sel.shift;
+        if (!rc) rc = launch<MODE_RADIX>(p, r, (sel.maxgroups + kGroups - 1) / kGroups, sizeof(u64) * kCols * kGroups * 256);
+        if (!rc) rc = sel.end_pass(p->st);
         if (rc) return rc;
-        dig.resize((size_t)slots * 256);
-        DF_HIP(hipMemcpyAsync(dig.data(), ddig, sizeof(u64) * dig.size(), hipMemcpyDeviceToHost, p->st));
-        DF_HIP(hipStreamSynchronize(p->st));
-        for (size_t i = 0; i < RN; i++) {
-            const u64 *h = &dig[(size_t)grp[i] * 256];
-            u64 left = rr[i], cum = 0;
-            int b = 0;
-            for (; b < 255 && cum + h[b] <= left; b++) cum += h[b];
-            pfx[i] = (pfx[i] << 8) | (u64)b;
-            rr[i] = left - cum;
-        }
     }
-    for (size_t i = 0; i < RN; i++) order_stats[i] = bh::post_unkey64(pfx[i]);
+    for (int i = 0; i < nranks; i++)
+        for (int c = 0; c < N; c++) order_stats[(size_t)i * N + c] = bh::post_unkey64(sel.key(i, c));
     return BH_OK;
 }
 

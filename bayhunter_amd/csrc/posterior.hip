@@ -3,37 +3,27 @@
 // The reference reaches the posterior through ModelMatrix.get_singlemodels (src/Models.py:160-226) and
 // PlotFromStorage._plot_bestmodels_hist (src/Plotting.py:462-536): every model interpolated onto a depth
 // grid in a Python loop, rows repeated once per iteration they stayed current.  Here every row carries an
-// integer weight and is walked on the device (posterior_core.h); nothing is expanded.
+// integer weight and is walked on the device (posterior_core.h); nothing is expanded.  The depths are the
+// columns of the weighted column reduction whose shared parts are in stats_core.h / stats_host.h (keys, slabs,
+// the scan / finish hand-over, the radix select); this file has what is the posterior's own:
 //
-//   scan    per depth: min / max (order-preserving integer keys, integer atomics), Σ w·v (per-block slab
-//           reduced in a fixed order); per row (blocks of the first depth tile only): weight total, the
-//           layer-count histogram, the interface-depth histogram, the first argmin of the misfit
-//   finish  Σ w·(v - mean)² (slab, fixed order), one 2-D (depth bin, Vs bin) histogram over edges the
-//           caller computed, and the median as an exact weighted radix select: 8-bit digits of the
-//           order-preserving keys (32-bit keys for float32 rows, 64-bit for float64), one pass per digit,
-//           per-depth digit histograms for the two middle order statistics in LDS, added across blocks
-//
-// No floating-point atomics: a run is bit-identical to the next one.  Integer counts are 64 bit.
-#include <hip/hip_runtime.h>
-#include <cmath>
+//   the walk   a thread per row, kTile depths of the ascending grid per block in registers
+//   scan       besides the columns' min / max / Σ w·v, per row (blocks of the first depth tile only): the
+//              weight total, the layer-count histogram, the interface-depth histogram, the first argmin of
+//              the misfit
+//   finish     Σ w·(v - mean)², one 2-D (depth bin, Vs bin) histogram over edges the caller computed, and the
+//              median: the select's two middle ranks, over 32-bit keys for float32 rows (4 passes) and 64-bit
+//              for float64; the first digit pass shares the row walk with the sums and the histogram
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <new>
-#include <vector>
-#include "../../include/bayhunter_amd.h"
 #include "posterior_core.h"
-
-namespace bh { int fail_arg_(const char *what); int fail_hip_(int e, const char *what); }
+#include "stats_host.h"
 
 namespace {
 
-#define PO_HIP(call)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) return bh::fail_hip_((int)e_, #call);          \
-    } while (0)
-
-typedef unsigned long long u64;
+using bh::u64;
 constexpr int kThreads = 256;
 constexpr int kTile = 8;              // depths per blockIdx.y: acc / min / max / prefixes stay in registers
 constexpr int kMaxBlocksX = 1024;     // fixed, so that the slab reduction order depends on nrows only
@@ -64,9 +54,9 @@ struct PostArgs {
     const int *dbin; int ndb;          // depth bin of every grid depth (-1: outside), ndb bins
     u64 *hist;                         // [ndb][nve - 1]
     int shift;                         // radix digit (key >> shift) & 255
-    const u64 *pfx;                    // [D][2] prefixes of the two middle order statistics
-    const int *split;                  // [D] the two prefixes differ
-    u64 *digits;                       // [D][2][256]
+    const int *gbase, *ngroups;        // [D] the select's groups of each depth (one or two), stats_core.h
+    const u64 *gpfx;                   // [slots] their prefixes
+    u64 *digits;                       // [slots][256]
     int off_radix, off_hist, off_nlay, off_if;   // u64 offsets into the dynamic LDS
 };
 
@@ -131,9 +121,9 @@ __global__ __launch_bounds__(kThreads) void post_kernel(PostArgs a)
         p0[j] = p1[j] = 0;
         sp[j] = false;
         if (do_radix && valid[j]) {
-            p0[j] = a.pfx[2 * d];
-            p1[j] = a.pfx[2 * d + 1];
-            sp[j] = a.split[d] != 0;
+            p0[j] = a.gpfx[a.gbase[d]];
+            sp[j] = a.ngroups[d] > 1;
+            if (sp[j]) p1[j] = a.gpfx[a.gbase[d] + 1];
         }
     }
     // zero the block's LDS histograms
@@ -274,70 +264,35 @@ __global__ __launch_bounds__(kThreads) void post_kernel(PostArgs a)
     }
     if (do_radix) {
         for (int i = tid; i < kTile * 2 * 256; i += kThreads) {
-            const int j = i / 512;
-            if (d0 + j < a.D && lds[a.off_radix + i])
-                atomicAdd(&a.digits[(size_t)(d0 + j) * 512 + (i % 512)], lds[a.off_radix + i]);
+            const int d = d0 + i / 512, t = (i / 256) % 2;
+            if (d < a.D && lds[a.off_radix + i] && t < a.ngroups[d])
+                atomicAdd(&a.digits[(size_t)(a.gbase[d] + t) * 256 + (i % 256)], lds[a.off_radix + i]);
         }
     }
 }
 
-// Σ over blocks in block order: one thread per depth
-__global__ void post_reduce_kernel(const double *slab, int G, int D, double *out)
-{
-    const int d = blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= D) return;
-    double s = 0.0;
-    for (int g = 0; g < G; g++) s = s + slab[(size_t)g * D + d];
-    out[d] = s;
-}
-
-__global__ void post_fill_kernel(u64 *p, long long n, u64 v)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
-bool ascending(const double *v, int n)
-{
-    for (int i = 0; i < n; i++)
-        if (!(v[i] == v[i]) || (i && !(v[i - 1] < v[i]))) return false;
-    return true;
-}
-
 }  // namespace
 
-struct bh_posterior {
-    int fp64 = 0, width = 0, D = 0, nif = 0, maxn = 0, G = 1, scanned = 0;
+struct bh_posterior : bh::ColumnStats {          // n: the depths
+    int fp64 = 0, width = 0, nif = 0, maxn = 0;
     const void *rows = nullptr;
     long long nrows = 0, stride = 0;
     const int *w = nullptr;
     const double *misfit = nullptr;
-    hipStream_t st = nullptr;
-    u64 total = 0;
-    std::vector<double> mean;
     // device
-    double *dep = nullptr, *ifedges = nullptr, *slab = nullptr, *red = nullptr, *dmean = nullptr;
-    u64 *kmin = nullptr, *kmax = nullptr, *cnt = nullptr, *nlay = nullptr, *ifhist = nullptr, *mfkey = nullptr;
+    double *dep = nullptr, *ifedges = nullptr;
+    u64 *cnt = nullptr, *nlay = nullptr, *ifhist = nullptr, *mfkey = nullptr;
     long long *mfrow = nullptr;
 };
 
 namespace {
 
-void post_free(bh_posterior *p)
-{
-    void *bufs[] = {p->dep, p->ifedges, p->slab, p->red, p->dmean, p->kmin, p->kmax, p->cnt, p->nlay,
-                    p->ifhist, p->mfkey, p->mfrow};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
-    delete p;
-}
-
 template <typename T, int MODE>
 int launch(bh_posterior *p, PostArgs &a, size_t lds_bytes)
 {
-    dim3 grid((unsigned)p->G, (unsigned)((p->D + kTile - 1) / kTile));
+    dim3 grid((unsigned)p->G, (unsigned)((p->n + kTile - 1) / kTile));
     hipLaunchKernelGGL((post_kernel<T, MODE>), grid, dim3(kThreads), lds_bytes, p->st, a);
-    PO_HIP(hipGetLastError());
+    STATS_HIP(hipGetLastError());
     return BH_OK;
 }
 
@@ -355,24 +310,13 @@ PostArgs base_args(const bh_posterior *p)
     a.nrows = p->nrows;
     a.stride = p->stride;
     a.width = p->width;
-    a.D = p->D;
+    a.D = p->n;
     a.w = p->w;
     a.misfit = p->misfit;
     a.dep = p->dep;
     a.slab = p->slab;
     a.maxn = p->maxn;
     return a;
-}
-
-int reduce_slab(bh_posterior *p, std::vector<double> &out)
-{
-    hipLaunchKernelGGL(post_reduce_kernel, dim3((unsigned)((p->D + 255) / 256)), dim3(256), 0, p->st,
-                       (const double *)p->slab, p->G, p->D, p->red);
-    PO_HIP(hipGetLastError());
-    out.assign(p->D, 0.0);
-    PO_HIP(hipMemcpyAsync(out.data(), p->red, sizeof(double) * p->D, hipMemcpyDeviceToHost, p->st));
-    PO_HIP(hipStreamSynchronize(p->st));
-    return BH_OK;
 }
 
 }  // namespace
@@ -388,15 +332,15 @@ int bh_posterior_create(const void *rows, int fp64, long long nrows, long long s
     if (!rows || nrows < 1) return bh::fail_arg_("bh_posterior_create: no rows (empty selection)");
     if (nrows > (1ll << 32)) return bh::fail_arg_("bh_posterior_create: more than 2^32 rows (the weight total could overflow)");
     if (width < 2 || width > 2 * BH_MAX_LAYERS + 2 || stride < width) return bh::fail_arg_("bh_posterior_create: width / stride");
-    if (!dep || ndep < 1 || !ascending(dep, ndep)) return bh::fail_arg_("bh_posterior_create: the depth grid must be ascending");
-    if (nifedges && (nifedges < 2 || !ifedges || !ascending(ifedges, nifedges)))
+    if (!dep || ndep < 1 || !bh::ascending(dep, ndep)) return bh::fail_arg_("bh_posterior_create: the depth grid must be ascending");
+    if (nifedges && (nifedges < 2 || !ifedges || !bh::ascending(ifedges, nifedges)))
         return bh::fail_arg_("bh_posterior_create: interface edges must be ascending");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
         return BH_ERR_NO_DEVICE;
     }
-    bh_posterior *p = new (std::nothrow) bh_posterior;
+    std::unique_ptr<bh_posterior> p(new (std::nothrow) bh_posterior);
     if (!p) return bh::fail_arg_("out of memory");
     p->fp64 = fp64 ? 1 : 0;
     p->rows = rows;
@@ -405,36 +349,27 @@ int bh_posterior_create(const void *rows, int fp64, long long nrows, long long s
     p->width = width;
     p->w = weights;
     p->misfit = misfits;
-    p->D = ndep;
+    p->n = ndep;
     p->nif = nifedges;
     p->maxn = width / 2;
     p->st = (hipStream_t)stream;
     long long g = (nrows + kThreads - 1) / kThreads;
     p->G = (int)(g < kMaxBlocksX ? g : kMaxBlocksX);
-    auto bail = [&](hipError_t e, const char *what) { post_free(p); return bh::fail_hip_((int)e, what); };
-    hipError_t e;
-#define PO_ALLOC(ptr, bytes) if ((e = hipMalloc((void **)&(ptr), (bytes))) != hipSuccess) return bail(e, "hipMalloc(" #ptr ")")
-    PO_ALLOC(p->dep, sizeof(double) * ndep);
-    PO_ALLOC(p->slab, sizeof(double) * (size_t)p->G * ndep);
-    PO_ALLOC(p->red, sizeof(double) * ndep);
-    PO_ALLOC(p->dmean, sizeof(double) * ndep);
-    PO_ALLOC(p->kmin, sizeof(u64) * ndep);
-    PO_ALLOC(p->kmax, sizeof(u64) * ndep);
-    PO_ALLOC(p->cnt, sizeof(u64) * 2);
-    PO_ALLOC(p->nlay, sizeof(u64) * (p->maxn + 1));
-    PO_ALLOC(p->mfkey, sizeof(u64) * p->G);
-    PO_ALLOC(p->mfrow, sizeof(long long) * p->G);
+    int rc = p->alloc_columns();
+    if (rc) return rc;
+    STATS_HIP(p->bufs.alloc(p->dep, ndep));
+    STATS_HIP(p->bufs.alloc(p->cnt, 2));
+    STATS_HIP(p->bufs.alloc(p->nlay, p->maxn + 1));
+    STATS_HIP(p->bufs.alloc(p->mfkey, p->G));
+    STATS_HIP(p->bufs.alloc(p->mfrow, p->G));
+    STATS_HIP(hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st));
     if (nifedges) {
-        PO_ALLOC(p->ifedges, sizeof(double) * nifedges);
-        PO_ALLOC(p->ifhist, sizeof(u64) * (nifedges - 1));
+        STATS_HIP(p->bufs.alloc(p->ifedges, nifedges));
+        STATS_HIP(p->bufs.alloc(p->ifhist, nifedges - 1));
+        STATS_HIP(hipMemcpyAsync(p->ifedges, ifedges, sizeof(double) * nifedges, hipMemcpyHostToDevice, p->st));
     }
-#undef PO_ALLOC
-    if ((e = hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st)) != hipSuccess)
-        return bail(e, "hipMemcpyAsync(dep)");
-    if (nifedges && (e = hipMemcpyAsync(p->ifedges, ifedges, sizeof(double) * nifedges, hipMemcpyHostToDevice, p->st)) != hipSuccess)
-        return bail(e, "hipMemcpyAsync(ifedges)");
-    if ((e = hipStreamSynchronize(p->st)) != hipSuccess) return bail(e, "hipStreamSynchronize");
-    *post = p;
+    STATS_HIP(hipStreamSynchronize(p->st));
+    *post = p.release();
     return BH_OK;
 }
 
@@ -442,7 +377,7 @@ void bh_posterior_destroy(bh_posterior *post)
 {
     if (post) {
         (void)hipStreamSynchronize(post->st);
-        post_free(post);
+        delete post;
     }
 }
 
@@ -450,13 +385,11 @@ int bh_posterior_scan(bh_posterior *p, long long *total, double *vmin, double *v
                       long long *nlayers, long long *ifhist, long long *argmin)
 {
     if (!p) return bh::fail_arg_("post is NULL");
-    const int D = p->D;
-    hipLaunchKernelGGL(post_fill_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, p->st, p->kmin, (long long)D, ~0ull);
-    hipLaunchKernelGGL(post_fill_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, p->st, p->kmax, (long long)D, 0ull);
-    PO_HIP(hipGetLastError());
-    PO_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2, p->st));
-    PO_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (p->maxn + 1), p->st));
-    if (p->nif) PO_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (p->nif - 1), p->st));
+    int rc = p->begin_scan();
+    if (rc) return rc;
+    STATS_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2, p->st));
+    STATS_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (p->maxn + 1), p->st));
+    if (p->nif) STATS_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (p->nif - 1), p->st));
     PostArgs a = base_args(p);
     a.flags = F_ROWS;
     a.kmin = p->kmin;
@@ -471,38 +404,23 @@ int bh_posterior_scan(bh_posterior *p, long long *total, double *vmin, double *v
     a.off_nlay = 0;
     a.off_if = p->maxn + 1;
     const size_t lds = sizeof(u64) * (size_t)(p->maxn + 1 + (p->nif > 1 ? p->nif - 1 : 0));
-    int rc = run<MODE_SCAN>(p, a, lds);
+    rc = run<MODE_SCAN>(p, a, lds);
     if (rc) return rc;
-    u64 cnt[2];
-    std::vector<u64> kmn(D), kmx(D), nl(p->maxn + 1), ih(p->nif > 1 ? p->nif - 1 : 0), mk(p->G);
+    u64 cnt[2];                                    // weight total, rows with a negative weight
+    std::vector<u64> nl(p->maxn + 1), ih(p->nif > 1 ? p->nif - 1 : 0), mk(p->G);
     std::vector<long long> mr(p->G);
-    PO_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
-    PO_HIP(hipMemcpyAsync(kmn.data(), p->kmin, sizeof(u64) * D, hipMemcpyDeviceToHost, p->st));
-    PO_HIP(hipMemcpyAsync(kmx.data(), p->kmax, sizeof(u64) * D, hipMemcpyDeviceToHost, p->st));
-    PO_HIP(hipMemcpyAsync(nl.data(), p->nlay, sizeof(u64) * nl.size(), hipMemcpyDeviceToHost, p->st));
-    if (!ih.empty()) PO_HIP(hipMemcpyAsync(ih.data(), p->ifhist, sizeof(u64) * ih.size(), hipMemcpyDeviceToHost, p->st));
+    STATS_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
+    STATS_HIP(hipMemcpyAsync(nl.data(), p->nlay, sizeof(u64) * nl.size(), hipMemcpyDeviceToHost, p->st));
+    if (!ih.empty()) STATS_HIP(hipMemcpyAsync(ih.data(), p->ifhist, sizeof(u64) * ih.size(), hipMemcpyDeviceToHost, p->st));
     if (p->misfit) {
-        PO_HIP(hipMemcpyAsync(mk.data(), p->mfkey, sizeof(u64) * p->G, hipMemcpyDeviceToHost, p->st));
-        PO_HIP(hipMemcpyAsync(mr.data(), p->mfrow, sizeof(long long) * p->G, hipMemcpyDeviceToHost, p->st));
+        STATS_HIP(hipMemcpyAsync(mk.data(), p->mfkey, sizeof(u64) * p->G, hipMemcpyDeviceToHost, p->st));
+        STATS_HIP(hipMemcpyAsync(mr.data(), p->mfrow, sizeof(long long) * p->G, hipMemcpyDeviceToHost, p->st));
     }
     std::vector<double> sum;
-    rc = reduce_slab(p, sum);                      // synchronises the stream
+    rc = p->reduce_slab(sum);                      // synchronises the stream
+    if (!rc) rc = p->end_scan("bh_posterior_scan", cnt[0], cnt[1], sum, vmin, vmax, mean);
     if (rc) return rc;
-    if (cnt[1]) return bh::fail_arg_("bh_posterior_scan: negative weight");
-    if (cnt[0] == 0) return bh::fail_arg_("bh_posterior_scan: empty selection (no row with a positive weight)");
-    if (cnt[0] > (1ull << 53)) return bh::fail_arg_("bh_posterior_scan: weight total above 2^53");
-    p->total = cnt[0];
-    p->mean.resize(D);
-    for (int d = 0; d < D; d++) p->mean[d] = sum[d] / (double)cnt[0];
-    PO_HIP(hipMemcpyAsync(p->dmean, p->mean.data(), sizeof(double) * D, hipMemcpyHostToDevice, p->st));
-    PO_HIP(hipStreamSynchronize(p->st));
-    p->scanned = 1;
-    if (total) *total = (long long)cnt[0];
-    for (int d = 0; d < D; d++) {
-        if (vmin) vmin[d] = bh::post_unkey64(kmn[d]);
-        if (vmax) vmax[d] = bh::post_unkey64(kmx[d]);
-        if (mean) mean[d] = p->mean[d];
-    }
+    if (total) *total = (long long)p->total;
     if (nlayers)
         for (size_t i = 0; i < nl.size(); i++) nlayers[i] = (long long)nl[i];
     if (ifhist)
@@ -522,9 +440,9 @@ int bh_posterior_finish(bh_posterior *p, const double *vedges, int nvedges, cons
 {
     if (!p) return bh::fail_arg_("post is NULL");
     if (!p->scanned) return bh::fail_arg_("bh_posterior_finish before bh_posterior_scan");
-    const int D = p->D;
+    const int D = p->n;
     const bool want_hist = vedges != nullptr;
-    if (want_hist && (nvedges < 2 || !ascending(vedges, nvedges) || !dbin || ndbins < 1 || !hist))
+    if (want_hist && (nvedges < 2 || !bh::ascending(vedges, nvedges) || !dbin || ndbins < 1 || !hist))
         return bh::fail_arg_("bh_posterior_finish: Vs edges must be ascending, depth bins and histogram given");
     bool tile_fits = true;            // a depth tile's bins fit kTile rows of the LDS histogram
     if (want_hist)
@@ -537,109 +455,64 @@ int bh_posterior_finish(bh_posterior *p, const double *vedges, int nvedges, cons
             if (hi >= 0 && hi - lo >= kTile) tile_fits = false;
         }
     const int nvb = nvedges - 1;
-    double *dve = nullptr;
-    int *ddb = nullptr, *dsplit = nullptr;
-    u64 *dhist = nullptr, *dpfx = nullptr, *ddig = nullptr;
-    struct Guard {
-        std::vector<void *> b;
-        ~Guard() { for (void *x : b) if (x) (void)hipFree(x); }
-    } guard;
+    bh::DevBufs tmp;
     PostArgs a = base_args(p);
     a.mean = p->dmean;
-    size_t lds = 0;
     if (want_hist) {
-        PO_HIP(hipMalloc((void **)&dve, sizeof(double) * nvedges));
-        guard.b.push_back(dve);
-        PO_HIP(hipMalloc((void **)&ddb, sizeof(int) * D));
-        guard.b.push_back(ddb);
-        PO_HIP(hipMalloc((void **)&dhist, sizeof(u64) * (size_t)ndbins * nvb));
-        guard.b.push_back(dhist);
-        PO_HIP(hipMemcpyAsync(dve, vedges, sizeof(double) * nvedges, hipMemcpyHostToDevice, p->st));
-        PO_HIP(hipMemcpyAsync(ddb, dbin, sizeof(int) * D, hipMemcpyHostToDevice, p->st));
-        PO_HIP(hipMemsetAsync(dhist, 0, sizeof(u64) * (size_t)ndbins * nvb, p->st));
+        double *dve = nullptr;
+        int *ddb = nullptr;
+        STATS_HIP(tmp.alloc(dve, nvedges));
+        STATS_HIP(tmp.alloc(ddb, D));
+        STATS_HIP(tmp.alloc(a.hist, (size_t)ndbins * nvb));
+        STATS_HIP(hipMemcpyAsync(dve, vedges, sizeof(double) * nvedges, hipMemcpyHostToDevice, p->st));
+        STATS_HIP(hipMemcpyAsync(ddb, dbin, sizeof(int) * D, hipMemcpyHostToDevice, p->st));
+        STATS_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * (size_t)ndbins * nvb, p->st));
         a.flags |= F_HIST;
         a.vedges = dve;
         a.nve = nvedges;
         a.dbin = ddb;
         a.ndb = ndbins;
-        a.hist = dhist;
         if (!tile_fits || (size_t)kTile * nvb * sizeof(u64) > (size_t)kHistLdsBytes) a.flags |= F_HIST_GLOBAL;
     }
-    const int keybits = p->fp64 ? 64 : 32;
-    std::vector<u64> pfx(2 * (size_t)D, 0), rr(2 * (size_t)D), dig((size_t)D * 512);
-    std::vector<int> split(D, 0);
+    // the median: the select's ranks are the two middle order statistics (0-based), at most two groups a depth
+    const uint64_t mid[2] = {(p->total - 1) / 2, p->total / 2};
+    bh::DeviceSelect sel(D, median ? 2 : 0, p->fp64 ? 64 : 32, mid);
     if (median) {
-        PO_HIP(hipMalloc((void **)&dpfx, sizeof(u64) * 2 * D));
-        guard.b.push_back(dpfx);
-        PO_HIP(hipMalloc((void **)&dsplit, sizeof(int) * D));
-        guard.b.push_back(dsplit);
-        PO_HIP(hipMalloc((void **)&ddig, sizeof(u64) * 512 * (size_t)D));
-        guard.b.push_back(ddig);
-        for (int d = 0; d < D; d++) {              // 0-based ranks of the two middle order statistics
-            rr[2 * d] = (p->total - 1) / 2;
-            rr[2 * d + 1] = p->total / 2;
-        }
+        int rc = sel.alloc(tmp);
+        if (rc) return rc;
         a.flags |= F_RADIX;
-        a.pfx = dpfx;
-        a.split = dsplit;
-        a.digits = ddig;
+        a.gbase = sel.dgbase;
+        a.ngroups = sel.dngroups;
+        a.gpfx = sel.dgpfx;
+        a.digits = sel.ddigits;
     }
     if (stdev) a.flags |= F_SQ;
     // LDS: radix digits first, then the histogram tile
     a.off_radix = 0;
     a.off_hist = median ? kTile * 2 * 256 : 0;
-    lds = sizeof(u64) * (size_t)(a.off_hist + ((a.flags & F_HIST) && !(a.flags & F_HIST_GLOBAL) ? kTile * nvb : 0));
-    int shift = keybits - 8;
-    bool first = true;
-    while (first || (median && shift >= 0)) {
-        a.shift = median ? shift : 0;
-        if (median) {
-            PO_HIP(hipMemcpyAsync(dpfx, pfx.data(), sizeof(u64) * 2 * D, hipMemcpyHostToDevice, p->st));
-            PO_HIP(hipMemcpyAsync(dsplit, split.data(), sizeof(int) * D, hipMemcpyHostToDevice, p->st));
-            PO_HIP(hipMemsetAsync(ddig, 0, sizeof(u64) * 512 * (size_t)D, p->st));
-        }
-        int rc = run<MODE_FINISH>(p, a, lds);
+    size_t lds = sizeof(u64) * (size_t)(a.off_hist + ((a.flags & F_HIST) && !(a.flags & F_HIST_GLOBAL) ? kTile * nvb : 0));
+    for (bool first = true; first || (median && !sel.done()); first = false) {
+        int rc = median ? sel.begin_pass(p->st) : BH_OK;
+        a.shift = median ? sel.shift : 0;
+        if (!rc) rc = run<MODE_FINISH>(p, a, lds);
+        if (!rc && first && stdev) rc = p->read_stdev(stdev);
+        if (!rc && first && want_hist) rc = bh::read_hist(a.hist, (size_t)ndbins * nvb, hist, p->st);
         if (rc) return rc;
-        if (first && stdev) {
-            std::vector<double> sq;
-            rc = reduce_slab(p, sq);
-            if (rc) return rc;
-            for (int d = 0; d < D; d++) stdev[d] = std::sqrt(sq[d] / (double)p->total);
-        }
-        if (first && want_hist) {
-            std::vector<u64> h((size_t)ndbins * nvb);
-            PO_HIP(hipMemcpyAsync(h.data(), dhist, sizeof(u64) * h.size(), hipMemcpyDeviceToHost, p->st));
-            PO_HIP(hipStreamSynchronize(p->st));
-            for (size_t i = 0; i < h.size(); i++) hist[i] = (long long)h[i];
-        }
         a.flags &= ~(F_SQ | F_HIST | F_HIST_GLOBAL);   // later passes: digits only
         lds = sizeof(u64) * (size_t)(kTile * 2 * 256);
-        first = false;
         if (!median) break;
-        PO_HIP(hipMemcpyAsync(dig.data(), ddig, sizeof(u64) * dig.size(), hipMemcpyDeviceToHost, p->st));
-        PO_HIP(hipStreamSynchronize(p->st));
-        for (int d = 0; d < D; d++) {
-            for (int t = 0; t < 2; t++) {
-                const u64 *h = &dig[(size_t)d * 512 + (split[d] ? t : 0) * 256];
-                u64 r = rr[2 * d + t], c = 0;
-                int b = 0;
-                for (; b < 255 && c + h[b] <= r; b++) c += h[b];
-                pfx[2 * d + t] = (pfx[2 * d + t] << 8) | (u64)b;
-                rr[2 * d + t] = r - c;
-            }
-            split[d] = pfx[2 * d] != pfx[2 * d + 1];
-        }
-        shift -= 8;
+        rc = sel.end_pass(p->st);
+        if (rc) return rc;
     }
     if (median)
         for (int d = 0; d < D; d++) {
             double lo, hi;
-            if (keybits == 32) {
-                lo = (double)bh::post_unkey32((uint32_t)pfx[2 * d]);
-                hi = (double)bh::post_unkey32((uint32_t)pfx[2 * d + 1]);
+            if (p->fp64) {
+                lo = bh::post_unkey64(sel.key(0, d));
+                hi = bh::post_unkey64(sel.key(1, d));
             } else {
-                lo = bh::post_unkey64(pfx[2 * d]);
-                hi = bh::post_unkey64(pfx[2 * d + 1]);
+                lo = (double)bh::post_unkey32((uint32_t)sel.key(0, d));
+                hi = (double)bh::post_unkey32((uint32_t)sel.key(1, d));
             }
             median[d] = (lo + hi) / 2.0;          // np.median: mean of the two middle values
         }

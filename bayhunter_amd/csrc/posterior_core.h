@@ -9,10 +9,11 @@
 //
 // The walk never holds the layer list in an array: it reads vs / z from the row as it crosses an
 // interface, so nothing lands in private memory through a dynamic index.  Compiled with g++ under
-// BH_HOSTSIM by tests/hostsim/posterior_sim.cpp (test infrastructure only).
+// BH_HOSTSIM by tests/hostsim/posterior_sim.cpp (test infrastructure only).  Keys and binning: stats_core.h.
 #pragma once
 #include <stdint.h>
 #include "bh_common.h"
+#include "stats_core.h"
 
 // member functions (BH_HD is `static inline` in the host build)
 #if defined(BH_HOSTSIM)
@@ -23,32 +24,6 @@
 
 namespace bh {
 
-// order-preserving unsigned keys: a < b  <=>  key(a) < key(b) for every non-NaN value (-0 < +0)
-BH_HD uint64_t post_key64(double v)
-{
-    union { double d; uint64_t u; } c;
-    c.d = v;
-    return (c.u >> 63) ? ~c.u : (c.u | 0x8000000000000000ull);
-}
-BH_HD double post_unkey64(uint64_t k)
-{
-    union { double d; uint64_t u; } c;
-    c.u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return c.d;
-}
-BH_HD uint32_t post_key32(float v)
-{
-    union { float f; uint32_t u; } c;
-    c.f = v;
-    return (c.u >> 31) ? ~c.u : (c.u | 0x80000000u);
-}
-BH_HD float post_unkey32(uint32_t k)
-{
-    union { float f; uint32_t u; } c;
-    c.u = (k >> 31) ? (k & 0x7fffffffu) : ~k;
-    return c.f;
-}
-
 // Leading non-NaN values of a row (the layout stores them first): 2 * nuclei, 0 for an all-NaN row.
 template <typename T>
 BH_HD int post_row_count(const T *row, int width)
@@ -56,21 +31,6 @@ BH_HD int post_row_count(const T *row, int width)
     int c = 0;
     while (c < width && row[c] == row[c]) c++;
     return c;
-}
-
-// Bin of v among ascending edges[0..ne): i with edges[i] <= v < edges[i+1], the last bin closed on the
-// right, -1 outside (NaN included) -- numpy's searchsorted(side='right') - 1 with its last-edge fix.
-BH_HD int post_bin(const double *edges, int ne, double v)
-{
-    if (!(v >= edges[0]) || !(v <= edges[ne - 1])) return -1;
-    if (v == edges[ne - 1]) return ne - 2;
-    int lo = 0, hi = ne;              // first index with edges[i] > v lies in (lo, hi]
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (edges[mid] <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
 }
 
 // The merge of an ascending depth grid with a row's interfaces.  n nuclei, vs at row[k], z_vnoi at

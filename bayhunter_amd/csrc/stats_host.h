@@ -1,0 +1,190 @@
+// stats_host.h -- the host scaffolding of the weighted column reductions (posterior.hip, datafits.hip).
+//
+// Both reduce n columns (depths there, samples of the modelled data here) over rows with integer weights in a
+// scan pass and a finish pass: min / max over order-preserving keys, Σ through a per-block slab that one thread
+// per column adds in block order, histograms over host-made edges, order statistics by radix select
+// (stats_core.h).  Only the way a block reads a value differs, and that stays in the two files; what surrounds
+// it is here: the error macro, the owner of device buffers, the fill and slab kernels, the select's device
+// side, and the part of a handle that carries a scan over to its finish.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <string>
+#include <vector>
+#include "../../include/bayhunter_amd.h"
+#include "stats_core.h"
+
+namespace bh { int fail_arg_(const char *what); int fail_hip_(int e, const char *what); }
+
+#define STATS_HIP(call)                                                      \
+    do {                                                                     \
+        hipError_t e_ = (call);                                              \
+        if (e_ != hipSuccess) return bh::fail_hip_((int)e_, #call);          \
+    } while (0)
+
+namespace bh {
+
+typedef unsigned long long u64;
+
+// owns what it allocates: a handle's buffers for the handle's life, a call's for the call
+class DevBufs {
+    std::vector<void *> bufs_;
+public:
+    DevBufs() = default;
+    DevBufs(const DevBufs &) = delete;
+    DevBufs &operator=(const DevBufs &) = delete;
+    ~DevBufs() { for (void *b : bufs_) (void)hipFree(b); }
+    template <typename T>
+    hipError_t alloc(T *&ptr, size_t count)
+    {
+        bufs_.push_back(nullptr);
+        hipError_t e = hipMalloc(&bufs_.back(), sizeof(T) * count);
+        ptr = (T *)bufs_.back();
+        return e;
+    }
+};
+
+static __global__ void stats_fill_kernel(u64 *p, int n, u64 v)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) p[i] = v;
+}
+
+// Σ over blocks in block order: one thread per column
+static __global__ void stats_reduce_kernel(const double *slab, int G, int n, double *out)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    double s = 0.0;
+    for (int g = 0; g < G; g++) s = s + slab[(size_t)g * n + c];
+    out[c] = s;
+}
+
+inline bool ascending(const double *v, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (!(v[i] == v[i]) || (i && !(v[i - 1] < v[i]))) return false;
+    return true;
+}
+
+// a device histogram into the caller's: synchronises
+inline int read_hist(const u64 *dhist, size_t count, long long *hist, hipStream_t st)
+{
+    std::vector<u64> h(count);
+    STATS_HIP(hipMemcpyAsync(h.data(), dhist, sizeof(u64) * count, hipMemcpyDeviceToHost, st));
+    STATS_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i < count; i++) hist[i] = (long long)h[i];
+    return BH_OK;
+}
+
+// The select with its device side: what a pass's kernel reads (the groups) and what it adds to (digits[slots][256]).
+// A pass is begin_pass, the caller's kernel at digit `shift`, end_pass; until done().
+struct DeviceSelect : RadixSelect {
+    int *dgbase = nullptr, *dngroups = nullptr;
+    u64 *dgpfx = nullptr, *ddigits = nullptr;
+    std::vector<uint64_t> dig;
+    using RadixSelect::RadixSelect;
+
+    int alloc(DevBufs &bufs)
+    {
+        STATS_HIP(bufs.alloc(dgbase, ncols));
+        STATS_HIP(bufs.alloc(dngroups, ncols));
+        STATS_HIP(bufs.alloc(dgpfx, pfx.size()));
+        STATS_HIP(bufs.alloc(ddigits, 256 * pfx.size()));
+        return BH_OK;
+    }
+    int begin_pass(hipStream_t st)
+    {
+        plan();
+        STATS_HIP(hipMemcpyAsync(dgbase, gbase.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
+        STATS_HIP(hipMemcpyAsync(dngroups, ngroups.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
+        STATS_HIP(hipMemcpyAsync(dgpfx, gpfx.data(), sizeof(u64) * slots, hipMemcpyHostToDevice, st));
+        STATS_HIP(hipMemsetAsync(ddigits, 0, sizeof(u64) * 256 * (size_t)slots, st));
+        return BH_OK;
+    }
+    int end_pass(hipStream_t st)             // synchronises
+    {
+        dig.resize((size_t)slots * 256);
+        STATS_HIP(hipMemcpyAsync(dig.data(), ddigits, sizeof(u64) * dig.size(), hipMemcpyDeviceToHost, st));
+        STATS_HIP(hipStreamSynchronize(st));
+        advance(dig.data());
+        return BH_OK;
+    }
+};
+
+// The part of a handle both reductions share: n columns, G blocks along the rows (a function of the row count
+// only, so that the slab order is fixed), and what a successful scan leaves for the finish.
+struct ColumnStats {
+    int n = 0, G = 1, scanned = 0;
+    hipStream_t st = nullptr;
+    u64 total = 0;                     // weight total of the scan
+    DevBufs bufs;
+    double *slab = nullptr, *red = nullptr, *dmean = nullptr;    // [G][n], [n], [n]
+    u64 *kmin = nullptr, *kmax = nullptr;                        // [n]
+
+    int alloc_columns()
+    {
+        STATS_HIP(bufs.alloc(slab, (size_t)G * n));
+        STATS_HIP(bufs.alloc(red, n));
+        STATS_HIP(bufs.alloc(dmean, n));
+        STATS_HIP(bufs.alloc(kmin, n));
+        STATS_HIP(bufs.alloc(kmax, n));
+        return BH_OK;
+    }
+    // a scan starts: whatever an earlier one left is void until this one has succeeded
+    int begin_scan()
+    {
+        scanned = 0;
+        hipLaunchKernelGGL(stats_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kmin, n, ~0ull);
+        hipLaunchKernelGGL(stats_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kmax, n, 0ull);
+        STATS_HIP(hipGetLastError());
+        return BH_OK;
+    }
+    // the slab of the pass just launched, added up: synchronises
+    int reduce_slab(std::vector<double> &out)
+    {
+        hipLaunchKernelGGL(stats_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                           (const double *)slab, G, n, red);
+        STATS_HIP(hipGetLastError());
+        out.assign(n, 0.0);
+        STATS_HIP(hipMemcpyAsync(out.data(), red, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        STATS_HIP(hipStreamSynchronize(st));
+        return BH_OK;
+    }
+    // a scan ends, with its counts and reduce_slab's Σ w·v on the host: the total or an error (`who` names the
+    // entry point), the mean to the device for the finish, min / max back from their keys
+    int end_scan(const char *who, u64 included, u64 negative, const std::vector<double> &sum, double *vmin,
+                 double *vmax, double *mean)
+    {
+        const char *bad = negative ? "negative weight"
+                          : included == 0 ? "empty selection (no included row with a positive weight)"
+                          : included > (1ull << 53) ? "weight total above 2^53" : nullptr;
+        if (bad) return bh::fail_arg_((std::string(who) + ": " + bad).c_str());
+        total = included;
+        std::vector<double> mu(n);
+        std::vector<u64> kmn(n), kmx(n);
+        for (int c = 0; c < n; c++) mu[c] = sum[c] / (double)included;
+        STATS_HIP(hipMemcpyAsync(dmean, mu.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+        STATS_HIP(hipMemcpyAsync(kmn.data(), kmin, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
+        STATS_HIP(hipMemcpyAsync(kmx.data(), kmax, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
+        STATS_HIP(hipStreamSynchronize(st));
+        scanned = 1;
+        for (int c = 0; c < n; c++) {
+            if (vmin) vmin[c] = bh::post_unkey64(kmn[c]);
+            if (vmax) vmax[c] = bh::post_unkey64(kmx[c]);
+            if (mean) mean[c] = mu[c];
+        }
+        return BH_OK;
+    }
+    // the finish pass's slab of Σ w·(v - mean)² -> population std: synchronises
+    int read_stdev(double *stdev)
+    {
+        std::vector<double> sq;
+        int rc = reduce_slab(sq);
+        if (rc) return rc;
+        for (int c = 0; c < n; c++) stdev[c] = std::sqrt(sq[c] / (double)total);
+        return BH_OK;
+    }
+};
+
+}  // namespace bh

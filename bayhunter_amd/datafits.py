@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .posterior import _to_device, _torch_device
+from .posterior import _Handle, _to_device, _torch_device, pool_rows
 
 DEFAULT_Q = (2.5, 16, 50, 84, 97.5)
 CHUNK = 65536                     # rows per layers_from_voronoi call: bounds the packed-model temporaries
@@ -56,16 +56,14 @@ def _layers(models, dev):
     return vsn.contiguous(), zv.contiguous(), n.to(torch.int32)
 
 
-class _Fits(object):
+class _Fits(_Handle):
     """One bh_datafits handle over a device matrix."""
 
     def __init__(self, Y, ncols, weights, err, stream):
-        self.lib = _lib.load()
         self.ncols = ncols
-        self.h = C.c_void_p()
-        _lib.check(self.lib.bh_datafits_create(
-            Y.data_ptr(), Y.shape[0], Y.stride(0), ncols, None if weights is None else weights.data_ptr(),
-            None if err is None else err.data_ptr(), 0 if err is None else err.shape[1], stream, C.byref(self.h)))
+        _Handle.__init__(
+            self, 'datafits', Y.data_ptr(), Y.shape[0], Y.stride(0), ncols, None if weights is None else
+            weights.data_ptr(), None if err is None else err.data_ptr(), 0 if err is None else err.shape[1], stream)
 
     def scan(self):
         N = self.ncols
@@ -87,11 +85,6 @@ class _Fits(object):
             self.h, ranks.ctypes.data if ranks.size else None, ranks.size, ost.ctypes.data if ranks.size else None,
             edges.ctypes.data, edges.shape[1], edges.shape[0], eset.ctypes.data, hist.ctypes.data, std.ctypes.data))
         return ost, hist, std
-
-    def close(self):
-        if self.h:
-            self.lib.bh_datafits_destroy(self.h)
-            self.h = C.c_void_p()
 
 
 def forward_matrix(targets, models, vpvs, mantle=None, device=None):
@@ -142,8 +135,7 @@ def _summarize(targets, models, vpvs, weights, misfits, mantle, q, nbins, device
     ncols = eng.ncols
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        f = _Fits(Y, ncols, w, err, stream)
-        try:
+        with _Fits(Y, ncols, w, err, stream) as f:
             s = f.scan()
             W = s['total']
             virt, lo, hi = percentile_ranks(q, W)
@@ -160,8 +152,6 @@ def _summarize(targets, models, vpvs, weights, misfits, mantle, q, nbins, device
                 edges[t] = np.linspace(tmin, tmax, int(nbins) + 1)
                 eset[a:b] = t
             ost, hist, std = f.finish(ranks, edges, eset)
-        finally:
-            f.close()
         picked = None if pick is None else Y[torch.as_tensor(np.asarray(pick, dtype=np.int64), device=dev)].cpu().numpy()
         best = None
         if misfits is not None:
@@ -216,16 +206,7 @@ def best_rows(ci, w, misfits):
 
 def pool_datafits(pool, selection='weighted', dev=0.05, exclude_outliers=True, q=DEFAULT_Q, nbins=100, device=None):
     """ChainPool.datafits: summarize() over the rows ChainPool.posterior uses, plus each chain's best fit."""
-    from .posterior import pool_outliers, pool_selection
-    ci, ri, w = pool_selection(pool, selection)
-    if exclude_outliers and ci.size:
-        out = pool_outliers(pool, dev) - pool.first
-        keep = ~np.isin(ci, out)
-        ci, ri, w = ci[keep], ri[keep], w[keep]
-    if ci.size == 0:
-        raise ValueError("empty selection: no main-phase rows")
-    if w.max() > np.iinfo(np.int32).max:
-        raise ValueError("a weight above 2^31 - 1")
+    ci, ri, w = pool_rows(pool, selection, dev, exclude_outliers)
     mis = pool.misfits[ci, ri, -1].astype(np.float64)
     pick = best_rows(ci, w, mis)
     res = _summarize(pool.targets, pool.models[ci, ri], pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32),

@@ -82,21 +82,40 @@ def _torch_device(device):
     return torch.device(device)
 
 
-class _Grid(object):
+class _Handle(object):
+    """A library handle of bh_<kind>_create(*args, &handle): destroyed by close(), or on leaving its `with` block."""
+
+    def __init__(self, kind, *args):
+        self.lib = _lib.load()
+        self.h = C.c_void_p()
+        self._destroy = getattr(self.lib, 'bh_%s_destroy' % kind)
+        _lib.check(getattr(self.lib, 'bh_%s_create' % kind)(*(args + (C.byref(self.h),))))
+
+    def close(self):
+        if self.h:
+            self._destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class _Grid(_Handle):
     """One bh_posterior handle: the rows on one depth grid."""
 
     def __init__(self, rows, weights, misfits, dep, ifedges, stream):
-        self.lib = _lib.load()
         self.dep = np.ascontiguousarray(dep, dtype=np.float64)
         self.ifedges = None if ifedges is None else np.ascontiguousarray(ifedges, dtype=np.float64)
         self.width = rows.shape[1]
-        self.h = C.c_void_p()
         nif = 0 if self.ifedges is None else self.ifedges.size
-        _lib.check(self.lib.bh_posterior_create(
-            rows.data_ptr(), int(rows.dtype.itemsize == 8), rows.shape[0], rows.stride(0), self.width,
-            None if weights is None else weights.data_ptr(), None if misfits is None else misfits.data_ptr(),
-            self.dep.ctypes.data, self.dep.size, None if not nif else self.ifedges.ctypes.data, nif,
-            stream, C.byref(self.h)))
+        _Handle.__init__(
+            self, 'posterior', rows.data_ptr(), int(rows.dtype.itemsize == 8), rows.shape[0], rows.stride(0),
+            self.width, None if weights is None else weights.data_ptr(),
+            None if misfits is None else misfits.data_ptr(), self.dep.ctypes.data, self.dep.size,
+            None if not nif else self.ifedges.ctypes.data, nif, stream)
 
     def scan(self):
         D = self.dep.size
@@ -119,11 +138,6 @@ class _Grid(object):
                                                 hist.ctypes.data, None if std is None else std.ctypes.data,
                                                 None if median is None else median.ctypes.data))
         return hist, std, median
-
-    def close(self):
-        if self.h:
-            self.lib.bh_posterior_destroy(self.h)
-            self.h = C.c_void_p()
 
 
 def _to_device(a, dtype, dev):
@@ -172,9 +186,7 @@ def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, dev
         raise ValueError("dep_int: at least two depths (they are the mode histogram's depth edges)")
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        ga = _Grid(rows, w, mf, dep_int, depbins, stream)
-        gb = None
-        try:
+        with _Grid(rows, w, mf, dep_int, depbins, stream) as ga:
             s = ga.scan()
             # (5) mode: int((max - min) / 0.025) Vs bins over linspace(min, max), depth edges dep_int
             vmin, vmax = s['vmin'].min(), s['vmax'].max()
@@ -183,16 +195,12 @@ def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, dev
                 raise ValueError("`bins[0]` must be positive, when an integer (all Vs values within 0.025 km/s)")
             vedges = np.linspace(vmin, vmax, vsbins + 1)
             mhist, std, median = ga.finish(vedges, bin_index(dep_int, dep_int), dep_int.size - 1, True)
-            # the density of _plot_bestmodels_hist on its half-step grid
-            gb = _Grid(rows, w, None, dep2, None, stream)
+        # the density of _plot_bestmodels_hist on its half-step grid
+        with _Grid(rows, w, None, dep2, None, stream) as gb:
             s2 = gb.scan()
             vmin2, vmax2 = s2['vmin'].min(), s2['vmax'].max()
             vsb = np.arange(vs_round(vmin2) - 2 * VS_INTERVAL, vs_round(vmax2) + 3 * VS_INTERVAL, VS_INTERVAL)
             h2, _, _ = gb.finish(vsb, bin_index(dep2, depbins), depbins.size - 1, False)
-        finally:
-            ga.close()
-            if gb is not None:
-                gb.close()
     mean = s['mean']
     vs_center = (vedges[:-1] + vedges[1:]) / 2.
     dep_center = (dep_int[:-1] + dep_int[1:]) / 2.
@@ -264,8 +272,9 @@ def pool_outliers(pool, dev=0.05):
     return (chains[(1 - scores) > dev] + pool.first).astype(np.int64)
 
 
-def pool_posterior(pool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None):
-    """ChainPool.posterior: summarize() over the pool's main-phase rows (see ChainPool.posterior)."""
+def pool_rows(pool, selection='weighted', dev=0.05, exclude_outliers=True):
+    """The rows ChainPool.posterior and ChainPool.datafits summarize: pool_selection without the outlier chains
+    -> (ci, ri, w).  ValueError when nothing is left or a weight does not fit the device's int32."""
     ci, ri, w = pool_selection(pool, selection)
     if exclude_outliers and ci.size:
         out = pool_outliers(pool, dev) - pool.first
@@ -275,6 +284,12 @@ def pool_posterior(pool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True
         raise ValueError("empty selection: no main-phase rows")
     if w.max() > np.iinfo(np.int32).max:
         raise ValueError("a weight above 2^31 - 1")
+    return ci, ri, w
+
+
+def pool_posterior(pool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None):
+    """ChainPool.posterior: summarize() over the pool's main-phase rows (see ChainPool.posterior)."""
+    ci, ri, w = pool_rows(pool, selection, dev, exclude_outliers)
     if dep_int is None:
         dep_int = models2d_dep_int(pool.priors['z'], depint)
     res = summarize(pool.models[ci, ri], w.astype(np.int32), dep_int=dep_int, device=device)

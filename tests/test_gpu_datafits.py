@@ -199,6 +199,28 @@ def test_lifecycle_with_own_stream(lib):
     lib.bh_datafits_destroy(h)
 
 
+def test_finish_is_refused_after_a_failed_rescan(lib):
+    from bayhunter_amd import _lib
+    import torch
+    rs = np.random.RandomState(7)
+    Y = torch.from_numpy(rs.normal(0, 1, (3000, 20))).cuda()
+    w = torch.ones(3000, dtype=torch.int32, device='cuda')
+    h = C.c_void_p()
+    _lib.check(lib.bh_datafits_create(Y.data_ptr(), 3000, 20, 20, w.data_ptr(), None, 0, None, C.byref(h)))
+    try:
+        std = np.zeros(20)
+        _lib.check(lib.bh_datafits_scan(h, None, None, None, None, None))
+        _lib.check(lib.bh_datafits_finish(h, None, 0, None, None, 0, 0, None, None, std.ctypes.data))
+        w[17] = -1                                             # the caller's tensor: the handle reads it at every scan
+        torch.cuda.synchronize()
+        assert lib.bh_datafits_scan(h, None, None, None, None, None) == _lib.BH_ERR_ARG
+        assert b'negative' in lib.bh_last_error()
+        assert lib.bh_datafits_finish(h, None, 0, None, None, 0, 0, None, None, std.ctypes.data) == _lib.BH_ERR_ARG
+        assert b'before' in lib.bh_last_error()
+    finally:
+        lib.bh_datafits_destroy(h)
+
+
 def test_pool_datafits(lib, tmp_path):
     from chain_scenario import CASES as CH, make_pool
     from bayhunter_amd.chains import GpuEvaluator

@@ -141,3 +141,27 @@ def test_lifecycle_with_own_stream(lib):
                                        dep.size, None, 0, None, C.byref(h)))
     assert lib.bh_posterior_scan(h, None, None, None, None, None, None, None) == _lib.BH_ERR_ARG
     lib.bh_posterior_destroy(h)
+
+
+def test_finish_is_refused_after_a_failed_rescan(lib):
+    from bayhunter_amd import _lib
+    import torch
+    rs = np.random.RandomState(4)
+    rows = torch.from_numpy(random_rows(rs, 3000)).cuda()
+    w = torch.ones(3000, dtype=torch.int32, device='cuda')
+    dep = np.linspace(0, 80, 41)
+    h = C.c_void_p()
+    _lib.check(lib.bh_posterior_create(rows.data_ptr(), 1, 3000, rows.stride(0), rows.shape[1], w.data_ptr(), None,
+                                       dep.ctypes.data, dep.size, None, 0, None, C.byref(h)))
+    try:
+        med = np.zeros(dep.size)
+        _lib.check(lib.bh_posterior_scan(h, None, None, None, None, None, None, None))
+        _lib.check(lib.bh_posterior_finish(h, None, 0, None, 0, None, None, med.ctypes.data))
+        w[17] = -1                                             # the caller's tensor: the handle reads it at every scan
+        torch.cuda.synchronize()
+        assert lib.bh_posterior_scan(h, None, None, None, None, None, None, None) == _lib.BH_ERR_ARG
+        assert b'negative' in lib.bh_last_error()
+        assert lib.bh_posterior_finish(h, None, 0, None, 0, None, None, med.ctypes.data) == _lib.BH_ERR_ARG
+        assert b'before' in lib.bh_last_error()
+    finally:
+        lib.bh_posterior_destroy(h)

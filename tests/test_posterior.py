@@ -3,6 +3,8 @@
 * the numpy restatement (tests/posterior_ref.py) equals the reference's own results
   (tests/golden/posterior.npz, made by tests/golden/make_golden_posterior.py);
 * the device's per-row core (posterior_core.h), compiled with g++, equals the restatement on every row and depth;
+* the host side of the radix select (stats_core.h), compiled with g++ and fed numpy's digit histograms, finds
+  the order statistics numpy's sort finds;
 * the pool's 'weighted' / 'saved' selections are the rows weighted() / save() produce, and
   ChainPool.outliers is get_outliers on the files save() writes;
 * the C ABI refuses bad arguments, and no posterior kernel uses scratch.
@@ -81,8 +83,8 @@ def test_restatement_outliers_equal_reference_golden(gold, tmp_path):
 def psim():
     d = os.path.join(ROOT, 'tests', 'hostsim')
     so = os.path.join(d, 'libposterior_sim.so')
-    srcs = [os.path.join(d, 'posterior_sim.cpp'), os.path.join(ROOT, 'bayhunter_amd', 'csrc', 'posterior_core.h'),
-            os.path.join(ROOT, 'bayhunter_amd', 'csrc', 'bh_common.h')]
+    srcs = [os.path.join(d, 'posterior_sim.cpp')] + [os.path.join(ROOT, 'bayhunter_amd', 'csrc', h)
+                                                     for h in ('posterior_core.h', 'stats_core.h', 'bh_common.h')]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.run(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-o', so, srcs[0]],
                        check=True)
@@ -146,6 +148,140 @@ def test_core_binning_and_keys(psim):
     k, back = np.zeros(x.size, dtype=np.uint64), np.zeros(x.size)
     psim.ps_keys(C.c_void_p(x.ctypes.data), C.c_long(x.size), C.c_void_p(k.ctypes.data), C.c_void_p(back.ctypes.data))
     assert np.array_equal(back.view(np.uint64), x.view(np.uint64)) and np.array_equal(x[np.argsort(k)], np.sort(x))
+
+
+def sim_select(psim, Y, w, ranks):
+    """The 0-based `ranks` of every weighted column of Y (float64: 64-bit keys, float32: 32-bit) through
+    bh::RadixSelect, numpy standing in for the device: per pass, the digit histograms of each group's keys.
+    -> (values [ranks, columns], the columns' group counts of every pass)"""
+    Y = np.ascontiguousarray(Y)
+    R, N = Y.shape
+    bits = 8 * Y.dtype.itemsize
+    K, back = np.zeros(Y.size, dtype=np.uint64 if bits == 64 else np.uint32), np.zeros(Y.size, dtype=Y.dtype)
+    (psim.ps_keys if bits == 64 else psim.ps_keys32)(C.c_void_p(Y.ctypes.data), C.c_long(Y.size),
+                                                     C.c_void_p(K.ctypes.data), C.c_void_p(back.ctypes.data))
+    K = K.reshape(R, N).astype(np.uint64)
+    w = np.asarray(w).astype(np.uint64)
+    ranks = np.ascontiguousarray(ranks, dtype=np.uint64)
+    n = ranks.size
+    psim.ps_sel_new.restype = C.c_void_p
+    sel = C.c_void_p(psim.ps_sel_new(C.c_int(N), C.c_int(n), C.c_int(bits), C.c_void_p(ranks.ctypes.data)))
+    gbase, ngroups, slot = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32), np.zeros((n, N), dtype=np.int32)
+    gpfx = np.zeros(n * N, dtype=np.uint64)
+    slots, maxg = C.c_int(0), C.c_int(0)
+    trace = []
+    try:
+        while True:
+            shift = psim.ps_sel_plan(sel, C.c_void_p(gbase.ctypes.data), C.c_void_p(ngroups.ctypes.data),
+                                     C.c_void_p(gpfx.ctypes.data), C.c_void_p(slot.ctypes.data), C.byref(slots),
+                                     C.byref(maxg))
+            if shift < 0:
+                break
+            assert slots.value == ngroups.sum() and maxg.value == ngroups.max() and 1 <= ngroups.min()
+            assert np.array_equal(gbase, np.cumsum(ngroups) - ngroups)
+            for c in range(N):                                  # distinct prefixes, first occurrence in rank order
+                u, first = np.unique(slot[:, c], return_index=True)
+                assert np.array_equal(u, gbase[c] + np.arange(ngroups[c])) and np.all(np.diff(first) > 0)
+                assert np.unique(gpfx[u]).size == u.size
+            trace.append(ngroups.copy())
+            digits = np.zeros((slots.value, 256), dtype=np.uint64)
+            for c in range(N):
+                whole = shift + 8 >= bits                       # first digit: every key matches the empty prefix
+                hi = np.zeros(R, dtype=np.uint64) if whole else K[:, c] >> np.uint64(shift + 8)
+                dig = ((K[:, c] >> np.uint64(shift)) & np.uint64(255)).astype(np.int64)
+                for t in range(ngroups[c]):
+                    m = hi == gpfx[gbase[c] + t]
+                    np.add.at(digits[gbase[c] + t], dig[m], w[m])
+            psim.ps_sel_advance(sel, C.c_void_p(digits.ctypes.data))
+        keys = np.zeros((n, N), dtype=np.uint64)
+        psim.ps_sel_keys(sel, C.c_void_p(keys.ctypes.data))
+    finally:
+        psim.ps_sel_free(sel)
+    assert len(trace) == bits // 8
+    out = np.zeros((n, N), dtype=Y.dtype)
+    for i in range(n):
+        for c in range(N):
+            at = np.nonzero((K[:, c] == keys[i, c]) & (w > 0))[0]
+            assert at.size, 'rank %d of column %d: the key found is no key of the column' % (ranks[i], c)
+            out[i, c] = Y[at[0], c]
+    return out, trace
+
+
+def sorted_order_stats(Y, w, ranks):
+    """numpy's answer: the sorted values, the cumulative sum of their weights, searchsorted(side='right')"""
+    out = np.zeros((len(ranks), Y.shape[1]), dtype=Y.dtype)
+    for c in range(Y.shape[1]):
+        o = np.argsort(Y[:, c], kind='stable')
+        cum = np.cumsum(np.asarray(w, dtype=np.int64)[o])
+        out[:, c] = Y[o[np.searchsorted(cum, np.asarray(ranks, dtype=np.int64), side='right')], c]
+    return out
+
+
+def select_ranks(rs, W, nranks):
+    """ranks 0 and W - 1 first (one rank: the upper median), then the two medians, then random ones"""
+    if nranks == 1:
+        return np.array([W // 2], dtype=np.int64)
+    if nranks == 2:
+        return np.array([(W - 1) // 2, W // 2], dtype=np.int64)
+    return np.r_[0, W - 1, (W - 1) // 2, W // 2, rs.randint(0, W, nranks - 4, dtype=np.int64)]
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+@pytest.mark.parametrize('nranks', [1, 2, 16])
+def test_select_equals_numpy_sort(psim, dtype, nranks):
+    rs = np.random.RandomState(100 + nranks)
+    R, N = 700, 5
+    Y = rs.normal(0, 3, (R, N))
+    Y[:, 1] = np.round(Y[:, 1], 1)                       # duplicated values, -0.0 among them
+    Y[:50, 2] = np.where(rs.rand(50) < .5, 0.0, -0.0)
+    Y[:, 3] = -np.abs(Y[:, 3]) * 1e-3
+    Y[:, 4] = rs.choice([-1e300, -2.5, 1e-310, 7.0, np.inf] if dtype == np.float64 else [-1e30, -2.5, 1e-40, 7.0, np.inf], R)
+    Y = Y.astype(dtype)
+    w = rs.randint(0, 9, R)
+    W = int(w.sum())
+    for ranks in (select_ranks(rs, W, nranks), np.array([0, W - 1] * 8, dtype=np.int64)[:nranks]):
+        got, _ = sim_select(psim, Y, w, ranks)
+        assert np.array_equal(got, np.sort(np.repeat(Y, w, axis=0), axis=0)[ranks])
+        assert np.array_equal(got, sorted_order_stats(Y, w, ranks))
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+def test_select_groups_and_signed_zeros(psim, dtype):
+    # one value: every rank stays in one group to the end
+    Y = np.full((40, 2), 2.75, dtype=dtype)
+    w = np.arange(40) % 4
+    ranks = np.arange(16, dtype=np.int64) * 3
+    got, trace = sim_select(psim, Y, w, ranks)
+    assert np.array_equal(got, np.full((16, 2), 2.75)) and all((t == 1).all() for t in trace)
+    # 16 values that differ in the first digit of their keys (sign and leading exponent bits): 16 groups from
+    # the second pass on, in rank order
+    step = 16 if dtype == np.float64 else 2
+    v = np.r_[-(2.0 ** (step * np.arange(7, -1, -1.0))), 2.0 ** (step * np.arange(-4, 4.0))].astype(dtype)
+    assert np.all(np.diff(v) > 0)
+    Y = np.stack((v, v[::-1]), axis=1)
+    ranks = np.array([5, 0, 15, 9, 1, 2, 3, 4, 6, 7, 8, 10, 11, 12, 13, 14], dtype=np.int64)
+    got, trace = sim_select(psim, Y, np.ones(16, dtype=np.int64), ranks)
+    assert np.array_equal(got, np.stack((v[ranks], v[ranks]), axis=1))
+    assert (trace[0] == 1).all() and all((t == 16).all() for t in trace[1:])
+    # -0 sorts before +0 (the keys' order): numpy's sort cannot tell them apart, the select does
+    Y = np.array([[0.0], [-0.0], [1.0], [-1.0]], dtype=dtype)
+    got, _ = sim_select(psim, Y, [3, 2, 1, 1], np.arange(7))
+    assert np.array_equal(got[:, 0], [-1, 0, 0, 0, 0, 0, 1])
+    assert np.array_equal(np.signbit(got[:, 0]), [True, True, True, False, False, False, False])
+
+
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+def test_select_with_a_weight_total_above_2_to_32(psim, dtype):
+    rs = np.random.RandomState(21)
+    R = 3000
+    Y = np.round(rs.normal(0, 1, (R, 3)), 2).astype(dtype)      # ties across many rows
+    w = rs.randint(1, 2 ** 31 - 1, R, dtype=np.int64)
+    W = int(w.sum())
+    assert W > 2 ** 32
+    for nranks in (2, 16):
+        ranks = select_ranks(rs, W, nranks)
+        got, _ = sim_select(psim, Y, w, ranks)
+        assert np.array_equal(got, sorted_order_stats(Y, w, ranks))
 
 
 @pytest.fixture(scope='module')
