@@ -37,7 +37,8 @@ using std::sqrt;
 // denormal, overflowing or non-finite operands; for the normal-range operands of the period
 // equation the quotient is exactly q1 = fma(rem, r, q0).  Recip keeps the refined reciprocal so that
 // the quotients by one divisor (three by rho, five by the normalisation factor of normc) share it:
-// 5 + 3 instructions per quotient instead of 11.  Bit-identical to `/` there
+// 5 instructions per reciprocal (one of them v_rcp_f64) + 3 per quotient instead of 11 per quotient
+// (divisors that are a root or an exact square get their reciprocal cheaper still, below).  Bit-identical to `/` there
 // (bh_selftest / tests/test_gpu_parity.py::test_division_selftest); a zero numerator yields +0 where
 // IEEE gives -0 for -0/b, non-finite operands may yield NaN where IEEE gives Inf/0.
 // The host replay uses the plain operator.
@@ -68,19 +69,66 @@ BH_DEV double xdiv(double a, double b) { return qdiv(a, recip_of(b)); }
 // IEEE square root for arguments that are zero or in the normal range (no denormals, no Inf): the
 // compiler's own sequence (v_rsq, one coupled Newton step, two residual corrections) without its
 // 2^256 range scaling.  Bit-identical to sqrt() there (bh_selftest_division).
+//
+// The coupled step carries h ~ 1/(2 sqrt(x)) next to g ~ sqrt(x), so a quotient by the root needs no
+// v_rcp_f64 of its own: xsqrt_recip_nz returns Recip{g, r} with r = 2h after STEPS Newton corrections
+// against the rounded root g (2 fma each).  With r = (1/b)(1 + d), qdiv's result before its final rounding
+// is (a/b)(1 - d^2) whatever q0's rounding was: a quotient moves only when a/b lies within d^2 of a rounding
+// boundary, about 2 d^2 / 2^-53 of all quotients.  Measured on 2^26 + 2^24 random operands (exponents
+// +-40 / +-300; two quotients each) against `/` and sqrt(), with the largest |1 - b r|:
+//     STEPS  mismatches  max |1 - b r|     expected mismatches per quotient
+//     0      0           38.3 x 2^-53      ~3e-13: none in the sample, one per ~10^3 steps of the headline
+//                                          workload (3e9 such quotients a step).  Not shipped.
+//     1      0            1.00 x 2^-53     that of recip_of itself (1.00 x 2^-53 in the same run).  Shipped.
+//     2      0            1.00 x 2^-53     no better than 1
+// _nz: no select for x == 0 (g and r are NaN there).  For the layer steps of the period equations: a
+// root vanishes only when wvno equals the layer's wavenumber, and that branch reads neither the root
+// nor its product with the thickness (swd_var, swd_love_layer; tests/test_gpu_recip_reuse.py).
+// recip_sq: the Recip of b*b from the Recip of b, for a b whose square is exact (an fp32 value widened
+// to fp64): the product of the reciprocals (|1 - b r| up to 2.99 x 2^-53, 0 mismatches in the sample) and
+// one correction for the same reason as above.
+// Per quotient by a root 3 + 3 instructions, by the square 3 + 3, instead of 5 + 3 with a v_rcp_f64 each.
 #if defined(BH_HOSTSIM)
 BH_DEV double xsqrt(double x) { return sqrt(x); }
+BH_DEV Recip xsqrt_recip_nz(double x) { return recip_of(sqrt(x)); }
+BH_DEV Recip recip_sq(const Recip &R) { return recip_of(R.b * R.b); }
 #else
-BH_DEV double xsqrt(double x)
+BH_DEV void xsqrt_gh(double x, double &g, double &h)
 {
     const double y = __builtin_amdgcn_rsq(x);
-    double g = x * y, h = y * 0.5;
+    g = x * y; h = y * 0.5;
     const double r = __builtin_fma(-h, g, 0.5);
     g = __builtin_fma(g, r, g);
     h = __builtin_fma(h, r, h);
     g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
     g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
+}
+BH_DEV double xsqrt(double x)
+{
+    double g, h;
+    xsqrt_gh(x, g, h);
     return (x == 0.0) ? x : g;
+}
+enum { BH_ROOT_RECIP_STEPS = 1 };
+template <int STEPS>
+BH_DEV Recip xsqrt_recip_nz_steps(double x)
+{
+    Recip R;
+    double h;
+    xsqrt_gh(x, R.b, h);
+    double r = h + h;
+    for (int i = 0; i < STEPS; i++) r = __builtin_fma(r, __builtin_fma(-R.b, r, 1.0), r);
+    R.r = r;
+    return R;
+}
+BH_DEV Recip xsqrt_recip_nz(double x) { return xsqrt_recip_nz_steps<BH_ROOT_RECIP_STEPS>(x); }
+BH_DEV Recip recip_sq(const Recip &R)
+{
+    Recip S;
+    S.b = R.b * R.b;
+    const double r = R.r * R.r;
+    S.r = __builtin_fma(r, __builtin_fma(-S.b, r, 1.0), r);
+    return S;
 }
 #endif
 

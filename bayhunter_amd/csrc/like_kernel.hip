@@ -355,6 +355,17 @@ __global__ void division_selftest_kernel(long n, unsigned seed, int max_exp, uns
         if (__double_as_longlong(q2) != __double_as_longlong(r2)) nbad++;
         const double sa = fabs(a);
         if (__double_as_longlong(xsqrt(sa)) != __double_as_longlong(sqrt(sa))) nbad++;
+        // the root's by-product reciprocal (sa > 0: the guard-free form) and the squared reciprocal of a
+        // divisor with a 24-bit mantissa (an fp32 value, whose square is exact) against the IEEE operators
+        const Recip S = xsqrt_recip_nz(sa);
+        const double root = sqrt(sa);
+        if (__double_as_longlong(S.b) != __double_as_longlong(root)) nbad++;
+        if (__double_as_longlong(qdiv(b, S)) != __double_as_longlong(b / root)) nbad++;
+        if (__double_as_longlong(qdiv(c, S)) != __double_as_longlong(c / root)) nbad++;
+        const double b24 = __longlong_as_double(__double_as_longlong(b) & ~0x1fffffffLL);
+        const Recip Q = recip_sq(recip_of(b24));
+        if (__double_as_longlong(qdiv(a, Q)) != __double_as_longlong(a / (b24 * b24))) nbad++;
+        if (__double_as_longlong(qdiv(c, Q)) != __double_as_longlong(c / (b24 * b24))) nbad++;
     }
     if (i == 0 && (xsqrt(0.0) != 0.0)) nbad++;
     if (nbad) atomicAdd(bad, nbad);

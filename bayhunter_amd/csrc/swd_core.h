@@ -25,15 +25,18 @@ struct VarProd {
     double a0, cpcq, cpy, cpz, cqw, cqx, xy, xz, wy, wz;
 };
 
-// surfdisp96.f:874-991.  Returns w and cosp through pointers (needed by the water-layer tail).
-BH_DEV void swd_var(double p, double q, double ra, double rb, double wvno, double xka, double xkb,
-                    double dpth, double *w_out, double *cosp_out, VarProd &o)
+// surfdisp96.f:874-991.  Returns w and cosp through pointers (needed by the water-layer tail).  The roots
+// ra, rb come with their reciprocals (by-products of the roots in the layer loop); a root that vanishes
+// is only passed through the branch that does not read it.
+BH_DEV void swd_var(double p, double q, const Recip &by_ra, const Recip &by_rb, double wvno, double xka,
+                    double xkb, double dpth, double *w_out, double *cosp_out, VarProd &o)
 {
+    const double ra = by_ra.b, rb = by_rb.b;
     double w, x, y, z, cosp, cosq, sinp, sinq, fac;
     double pex = 0.0, sex = 0.0;
     if (wvno < xka) {
         bh_sincos(p, &sinp, &cosp);
-        w = xdiv(sinp, ra);
+        w = qdiv(sinp, by_ra);
         x = -ra * sinp;
     } else if (wvno == xka) {
         cosp = 1.0; w = dpth; x = 0.0;
@@ -43,12 +46,12 @@ BH_DEV void swd_var(double p, double q, double ra, double rb, double wvno, doubl
         if (p < 16) fac = bh_exp_bounded(-2.0 * p);
         cosp = (1.0 + fac) * 0.5;
         sinp = (1.0 - fac) * 0.5;
-        w = xdiv(sinp, ra);
+        w = qdiv(sinp, by_ra);
         x = ra * sinp;
     }
     if (wvno < xkb) {
         bh_sincos(q, &sinq, &cosq);
-        y = xdiv(sinq, rb);
+        y = qdiv(sinq, by_rb);
         z = -rb * sinq;
     } else if (wvno == xkb) {
         cosq = 1.0; y = dpth; z = 0.0;
@@ -58,7 +61,7 @@ BH_DEV void swd_var(double p, double q, double ra, double rb, double wvno, doubl
         if (q < 16) fac = bh_exp_bounded(-2.0 * q);
         cosq = (1.0 + fac) * 0.5;
         sinq = (1.0 - fac) * 0.5;
-        y = xdiv(sinq, rb);
+        y = qdiv(sinq, by_rb);
         z = rb * sinq;
     }
     double exa = pex + sex;
@@ -89,7 +92,7 @@ BH_DEV void swd_dnka(Dunkin &a, double wvno2, double gam, double gammk, double r
     a.c12 = qdiv(wvno2 * v.cpy - v.cqx, by_rho);
     a.c13 = qdiv(-(twgm1 * a0pq + gammk * v.xz + wvno2 * gamm1 * v.wy), by_rho);
     a.c14 = qdiv(v.cpz - wvno2 * v.cqw, by_rho);
-    a.c15 = xdiv(-(two * wvno2 * a0pq + v.xz + wvno2 * wvno2 * v.wy), rho2);
+    a.c15 = qdiv(-(two * wvno2 * a0pq + v.xz + wvno2 * wvno2 * v.wy), recip_sq(by_rho));   // by rho2: exact square
     a.c21 = (gmgmk * v.cpz - gm1sq * v.cqw) * rho;
     a.c22 = v.cpcq;
     a.c23 = gammk * v.cpz - gamm1 * v.cqw;
@@ -139,14 +142,14 @@ BH_DEV void swd_ray_layer_matrix(const Lay &lay, int i0, double wvno, double wvn
     double gammk = 2.0 * t * t;
     double gam = gammk * wvno2;
     double wvnop = wvno + xka, wvnom = fabs(wvno - xka);
-    double ra = xsqrt(wvnop * wvnom);
+    const Recip by_ra = xsqrt_recip_nz(wvnop * wvnom);
     wvnop = wvno + xkb; wvnom = fabs(wvno - xkb);
-    double rb = xsqrt(wvnop * wvnom);
+    const Recip by_rb = xsqrt_recip_nz(wvnop * wvnom);
     double dpth = (double)lay.d(i0);
     double rho1 = (double)lay.rho(i0);
-    double p = ra * dpth, q = rb * dpth, w, cosp;
+    double p = by_ra.b * dpth, q = by_rb.b * dpth, w, cosp;
     VarProd v;
-    swd_var(p, q, ra, rb, wvno, xka, xkb, dpth, &w, &cosp, v);
+    swd_var(p, q, by_ra, by_rb, wvno, xka, xkb, dpth, &w, &cosp, v);
     swd_dnka(a, wvno2, gam, gammk, rho1, v);
 }
 
@@ -184,7 +187,7 @@ BH_DEV double swd_ray_water(const Lay &lay, double wvno, double omega, const dou
     double rho1 = (double)lay.rho(0);
     double p = ra * dpth, znul = 1.0e-05, w, cosp;
     VarProd v;
-    swd_var(p, znul, ra, znul, wvno, xka, znul, dpth, &w, &cosp, v);
+    swd_var(p, znul, recip_of(ra), recip_of(znul), wvno, xka, znul, dpth, &w, &cosp, v);
     double w0 = -rho1 * w;
     return cosp * e[0] + w0 * e[1];
 }
@@ -221,11 +224,12 @@ BH_DEV void swd_love_layer(const Lay &lay, int i0, double wvno, double omega, Lo
     o.xmu = rho1 * beta1 * beta1;
     double xkb = xdiv(omega, beta1);
     double wvnop = wvno + xkb, wvnom = fabs(wvno - xkb);
-    double rb = xsqrt(wvnop * wvnom);
+    const Recip by_rb = xsqrt_recip_nz(wvnop * wvnom);      // (rb == 0 only in the branch that does not read it)
+    const double rb = by_rb.b;
     double q = dm * rb, sinq, fac;
     if (wvno < xkb) {
         bh_sincos(q, &sinq, &o.cosq);
-        o.y = xdiv(sinq, rb);
+        o.y = qdiv(sinq, by_rb);
         o.z = -rb * sinq;
     } else if (wvno == xkb) {
         o.cosq = 1.0; o.y = dm; o.z = 0.0;
@@ -234,7 +238,7 @@ BH_DEV void swd_love_layer(const Lay &lay, int i0, double wvno, double omega, Lo
         if (q < 16) fac = bh_exp_bounded(-2.0 * q);
         o.cosq = (1.0 + fac) * 0.5;
         sinq = (1.0 - fac) * 0.5;
-        o.y = xdiv(sinq, rb);
+        o.y = qdiv(sinq, by_rb);
         o.z = rb * sinq;
     }
 }

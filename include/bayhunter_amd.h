@@ -285,7 +285,9 @@ int synrf_cwrap(int nsamp, double fsamp, double tshift, double p, double a, doub
 /* ---- self-test --------------------------------------------------------------------------- */
 /* The surface-wave kernels divide with a shared-reciprocal form of the compiler's own IEEE sequence
  * (bh_common.h, Recip/qdiv).  This runs n pseudo-random fp64 quotients a/b with exponents in
- * [-max_exp, max_exp] on the device both ways and counts bitwise differences (expected: 0). */
+ * [-max_exp, max_exp] on the device both ways and counts bitwise differences (expected: 0).  The same
+ * count covers the lean square root, quotients by a root through the root's own by-product reciprocal
+ * and quotients by an exact square through the squared reciprocal. */
 int bh_selftest_division(long n, unsigned seed, int max_exp, long *mismatches);
 
 /* ---- lock-step chain pool (host side of the sampler) ------------------------------------ */
