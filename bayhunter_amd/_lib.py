@@ -172,6 +172,7 @@ _SIGS = {
     "bh_eval_wait": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "bh_eval_set_concurrency": (C.c_int, [_vp, C.c_int]),
     "bh_eval_set_observations": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
+    "bh_eval_set_rf_slowness": (C.c_int, [_vp, C.c_int, _vp]),
     "bh_forward_batch": (C.c_int, [C.c_int] * 3 + [_vp] * 5 + [C.c_int, C.POINTER(SwdTarget), _vp, C.c_int,
                                    C.POINTER(EvalInterp), C.c_int, C.POINTER(RfParams), _vp, C.c_double, C.c_int, _vp,
                                    C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
@@ -198,6 +199,8 @@ _SIGS = {
     "bh_rf_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(RfParams)]),
     "bh_rf_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               C.POINTER(RfParams), _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "bh_rf_batch_sets": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   C.POINTER(RfParams), C.c_int, _vp, _vp, _vp, C.c_int, _vp, C.c_size_t, _vp]),
     "bh_voronoi_to_layers": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.POINTER(ModelPriors),
                                        _vp, _vp, _vp]),
     "bh_likelihood_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(LikeTarget)]),

@@ -778,7 +778,8 @@ static int rf_launch_common(int B, int Lmax, int model_stride, const int *nlay, 
                             const double *vs, const double *rho, const double *qp, const double *qs,
                             const bh_rf_params *par, double sigma, int depth_input, double *out,
                             int out_stride, void *stream, double *out_fz = nullptr,
-                            double *out_fr = nullptr)
+                            double *out_fr = nullptr, const double *set_p = nullptr, const int *set_id = nullptr,
+                            int nsets = 0)
 {
     if (!par) return fail_arg("par is NULL");
     if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return fail_arg("B/Lmax out of range");
@@ -798,6 +799,7 @@ static int rf_launch_common(int B, int Lmax, int model_stride, const int *nlay, 
     A.P.depth_input = depth_input;
     A.P.M = (out_fz && out_fr) ? 1 : pick_rf_M(B, Lmax, n);
     A.out_fz = out_fz; A.out_fr = out_fr;
+    A.set_p = set_p; A.set_id = set_id; A.nsets = nsets;   // per-row slowness (bh_rf_batch_sets), or null / 0
     rc = get_twiddles(n, &A.tw);
     if (rc) return rc;
     FreqTablePin pin;                              // held until the launch below has been queued
@@ -816,6 +818,21 @@ int bh_rf_batch(int B, int Lmax, int model_stride, const int *nlay, const double
 {
     return rf_launch_common(B, Lmax, model_stride, nlay, h, vp, vs, rho, qp, qs, par, std::nan(""), 0,
                             out, out_stride, stream);
+}
+
+int bh_rf_batch_sets(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                     const double *vs, const double *rho, const double *qp, const double *qs, const bh_rf_params *par,
+                     int nsets, const double *set_p, const int *set_id, double *out, int out_stride, void *, size_t,
+                     void *stream)
+{
+    if (nsets < 1) return fail_arg("bh_rf_batch_sets: nsets < 1");
+    if (!set_p) return fail_arg("bh_rf_batch_sets: set_p is NULL");
+    if (nsets > 1 && !set_id) return fail_arg("bh_rf_batch_sets: set_id is NULL but nsets > 1");
+    if (!par) return fail_arg("par is NULL");
+    bh_rf_params q = *par;
+    q.p = 0.0;                 // ignored: every row takes its set's
+    return rf_launch_common(B, Lmax, model_stride, nlay, h, vp, vs, rho, qp, qs, &q, std::nan(""), 0, out, out_stride,
+                            stream, nullptr, nullptr, set_p, set_id, nsets);
 }
 
 int bh_voronoi_to_layers(int B, int Lmax, const int *nlay, const double *vs_nuclei,

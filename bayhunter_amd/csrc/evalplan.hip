@@ -13,6 +13,7 @@
 #include <cstring>                     // (before rocprim: its texture iterator calls the host memset)
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <new>
 #include <string>
@@ -96,6 +97,7 @@ struct bh_eval_plan {
     int nsets = 1;
     double *set_scale = nullptr, *set_logdet = nullptr;
     std::vector<int> set_of_chain;
+    double *rf_set_p = nullptr;   // [nrf][nsets] ray parameters per set (bh_eval_set_rf_slowness), or null: rf[i].p
     bool submitted = false;       // a batch has been submitted: the observations are fixed from then on
     int last_count = 0;           // models of the submission `done` belongs to (set once `done` is recorded)
     bool failed = false;          // the last submission returned an error: nothing to wait for, no results
@@ -108,7 +110,7 @@ static void plan_free(bh_eval_plan *p)
     (void)hipSetDevice(p->dev);
     if (p->st) (void)hipStreamSynchronize(p->st);
     if (p->side) (void)hipStreamSynchronize(p->side);
-    void *dptr[] = {p->dblock, p->periods, p->obsx, p->yobs, p->aux, p->set_scale, p->set_logdet, p->out, p->dres, p->err, p->keys,
+    void *dptr[] = {p->dblock, p->periods, p->obsx, p->yobs, p->aux, p->set_scale, p->set_logdet, p->rf_set_p, p->out, p->dres, p->err, p->keys,
                     p->keys_out, p->iota, p->order, p->sort_tmp, p->like_ws, p->swd_ws};
     for (void *d : dptr)
         if (d) (void)hipFree(d);
@@ -262,11 +264,16 @@ int bh_eval_buffers(bh_eval_plan *p, double **packed, int **nlay, double **noise
     return BH_OK;
 }
 
-int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
-                     const double *vs, const double *rho, int nswd, const bh_swd_target *swd, const double *periods,
-                     int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
-                     double mean_layers, int concurrent_calls, double *out, int out_stride, int *err, void *workspace,
-                     size_t workspace_bytes, void *stream, void *rf_stream)
+}  // extern "C"
+
+// bh_forward_batch, and the plan's forward stage with per-set ray parameters: rf_set_p [nrf][nsets] and set_id [B]
+// (DEVICE; bh_eval_set_rf_slowness) send every receiver-function target through bh_rf_batch_sets.
+static int forward_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                         const double *vs, const double *rho, int nswd, const bh_swd_target *swd, const double *periods,
+                         int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
+                         double mean_layers, int concurrent_calls, double *out, int out_stride, int *err, void *workspace,
+                         size_t workspace_bytes, void *stream, void *rf_stream, int nsets, const double *rf_set_p,
+                         const int *set_id)
 {
     if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return bh::fail_arg_("B/Lmax out of range");
     if (model_stride < Lmax) return bh::fail_arg_("model_stride < Lmax");
@@ -296,12 +303,30 @@ int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const d
                            nlay, Lmax, err);
         EP_HIP(hipGetLastError());
     }
-    for (int i = 0; i < nrf; i++)
-        if ((rc = bh_rf_batch(B, Lmax, model_stride, nlay, h, vp, vs, rho, nullptr, nullptr, rf + i, out, out_stride,
-                              nullptr, 0, rf_stream)))
-            return rc;
+    for (int i = 0; i < nrf; i++) {
+        rc = rf_set_p ? bh_rf_batch_sets(B, Lmax, model_stride, nlay, h, vp, vs, rho, nullptr, nullptr, rf + i, nsets,
+                                         rf_set_p + (size_t)i * nsets, set_id, out, out_stride, nullptr, 0, rf_stream)
+                      : bh_rf_batch(B, Lmax, model_stride, nlay, h, vp, vs, rho, nullptr, nullptr, rf + i, out, out_stride,
+                                    nullptr, 0, rf_stream);
+        if (rc) return rc;
+    }
     return BH_OK;
 }
+
+extern "C" {
+
+int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                     const double *vs, const double *rho, int nswd, const bh_swd_target *swd, const double *periods,
+                     int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
+                     double mean_layers, int concurrent_calls, double *out, int out_stride, int *err, void *workspace,
+                     size_t workspace_bytes, void *stream, void *rf_stream)
+{
+    return forward_batch(B, Lmax, model_stride, nlay, h, vp, vs, rho, nswd, swd, periods, ninterp, interp, nrf, rf, order,
+                         mean_layers, concurrent_calls, out, out_stride, err, workspace, workspace_bytes, stream, rf_stream,
+                         0, nullptr, nullptr);
+}
+
+}  // extern "C"
 
 // the launches of one submission; `forked` tells the caller whether the side stream was made to wait
 static int submit_batch(bh_eval_plan *p, int count, bool *forked)
@@ -361,10 +386,10 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
     }
     // the batch is ragged: the planner prices it by its mean depth, not by its deepest model (capi.hip: plan_forms)
     hipStream_t rst = overlap ? p->side : p->st;
-    if ((rc = bh_forward_batch(count, Leff, 4 * L, dnlay, h, vp, vs, rho, p->nswd, p->swd.data(), p->periods,
-                               (int)p->interp.size(), p->interp.data(), p->nrf, p->rf.data(), order,
-                               (double)layers / (double)count, p->concurrency, p->out, p->row, p->err, p->swd_ws,
-                               p->swd_bytes, p->st, rst)))
+    if ((rc = forward_batch(count, Leff, 4 * L, dnlay, h, vp, vs, rho, p->nswd, p->swd.data(), p->periods,
+                            (int)p->interp.size(), p->interp.data(), p->nrf, p->rf.data(), order,
+                            (double)layers / (double)count, p->concurrency, p->out, p->row, p->err, p->swd_ws,
+                            p->swd_bytes, p->st, rst, p->nsets, p->rf_set_p, dset)))
         return rc;
     double *logL = p->dres, *mis = p->dres + count;
     // The dense Gaussian product of a receiver-function target needs that target's columns only: it follows
@@ -391,6 +416,8 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
     EP_HIP(hipEventRecord(p->done, p->st));
     return BH_OK;
 }
+
+extern "C" {
 
 int bh_eval_submit(bh_eval_plan *p, int count)
 {
@@ -447,6 +474,38 @@ int bh_eval_set_observations(bh_eval_plan *p, int nsets, const double *yobs, con
     p->yobs = dy; p->set_scale = ds; p->set_logdet = dl;
     p->nsets = nsets;
     p->set_of_chain.assign(set_of_chain, set_of_chain + nchains);
+    return BH_OK;
+}
+
+int bh_eval_set_rf_slowness(bh_eval_plan *p, int nsets, const double *table)
+{
+    if (nsets < 1) return bh::fail_arg_("bh_eval_set_rf_slowness: nsets < 1");
+    if (!table) return bh::fail_arg_("bh_eval_set_rf_slowness: NULL pointer (p)");
+    if (!p) return bh::fail_arg_("plan is NULL");
+    if (p->nrf < 1) return bh::fail_arg_("bh_eval_set_rf_slowness: the plan has no receiver-function target");
+    if (p->submitted) return bh::fail_arg_("bh_eval_set_rf_slowness: called after bh_eval_submit");
+    if (p->rf_set_p) return bh::fail_arg_("bh_eval_set_rf_slowness: the plan has its ray parameters already");
+    if (p->set_of_chain.empty())
+        return bh::fail_arg_("bh_eval_set_rf_slowness: call bh_eval_set_observations first (it tells the plan the set of every chain)");
+    if (nsets != p->nsets)
+        return bh::fail_arg_(("bh_eval_set_rf_slowness: nsets = " + std::to_string(nsets) + ", but bh_eval_set_observations gave the plan " +
+                              std::to_string(p->nsets) + " sets").c_str());
+    std::vector<double> byrf((size_t)p->nrf * nsets);          // [nrf][nsets]: one contiguous table per target
+    for (int s = 0; s < nsets; s++)
+        for (int i = 0; i < p->nrf; i++) {
+            const double v = table[(size_t)s * p->nrf + i];
+            if (!std::isfinite(v))
+                return bh::fail_arg_(("bh_eval_set_rf_slowness: p[" + std::to_string(s) + "][" + std::to_string(i) +
+                                      "] is not finite").c_str());
+            byrf[(size_t)i * nsets + s] = v;
+        }
+    EP_HIP(hipSetDevice(p->dev));
+    double *d = nullptr;
+    if (int rc = upload(&d, byrf.data(), byrf.size())) {
+        if (d) (void)hipFree(d);
+        return rc;
+    }
+    p->rf_set_p = d;
     return BH_OK;
 }
 

@@ -48,6 +48,13 @@ struct RfArgs {
     double *out;
     double *out_fz, *out_fr;  // optional [B][nsamp] vertical / radial traces (synrf_cwrap's fz, fr)
     RfLaunch P;
+    // Per-row slowness (the per-row form, rf_kernel<false, true>; launch_rf takes it when set_p is given): row b is
+    // computed at p = set_p[set_id[b]] [s/deg] instead of the launch's P.slowness / P.p2 (rf_core.h: rf_row_slowness).
+    // set_id null: every row takes set_p[0]; an index outside 0 .. nsets-1 gives a NaN row.  Behind P, so that the
+    // uniform form's argument block is what it was.
+    const double *set_p;     // [nsets]
+    const int *set_id;       // [B] or null
+    int nsets;
 };
 
 struct ModelPriorsDev {

@@ -1013,9 +1013,12 @@ __device__ __forceinline__ void rf_block_fft(double *S, int per_model, int Mb, i
 #ifndef BH_RF_WAVES
 #define BH_RF_WAVES 4
 #endif
-template <bool ZR>
+// ROW: the per-row form -- every model at the slowness of its own set (RfArgs::set_p, set_id) instead of the launch's.
+// A second instantiation of the same source: the uniform form takes no argument, branch or register from it.
+template <bool ZR, bool ROW = false>
 __global__ __launch_bounds__(RF_T) __attribute__((amdgpu_waves_per_eu(BH_RF_WAVES, BH_RF_WAVES))) void rf_kernel(RfArgs A)
 {
+    static_assert(!(ZR && ROW), "the trace form is a single-model call: no per-row slowness");
     extern __shared__ double S[];
     const RfLaunch &P = A.P;
     const int tid = threadIdx.x;
@@ -1045,7 +1048,14 @@ __global__ __launch_bounds__(RF_T) __attribute__((amdgpu_waves_per_eu(BH_RF_WAVE
         long b = b0 + m;
         int nl = A.nlay[b];
         nl = nl < 1 ? 1 : (nl > L ? L : nl);
-        if (i < nl)
+        if (ROW) {
+            if (i < nl) {
+                bool bad_set;                       // (NaN slowness: the row comes out NaN)
+                const double u = rf_row_slowness(A.set_p, A.set_id, A.nsets, b, &bad_set);
+                rf_phase2_interface_at<true>(S + (long)m * pm, lo, P, nl, i, A.vp[b * A.mstride],
+                                             A.vs[b * A.mstride], u, u * u);
+            }
+        } else if (i < nl)
             rf_phase2_interface(S + (long)m * pm, lo, P, nl, i, A.vp[b * A.mstride],
                                 A.vs[b * A.mstride]);
     }
@@ -1061,15 +1071,15 @@ __global__ __launch_bounds__(RF_T) __attribute__((amdgpu_waves_per_eu(BH_RF_WAVE
         int nl = A.nlay[b0 + m];
         nl = nl < 1 ? 1 : (nl > L ? L : nl);
         double *Sm = S + (long)m * pm;
-        const RfFreq F = rf_freq_load(A.ftab, j);
+        const RfFreq F = ROW ? rf_freq_load_lgw(A.ftab, j) : rf_freq_load(A.ftab, j);
         if (ZR) {
             cd zr_r, zr_z;
-            cd crf = rf_phase3_task(Sm, lo, P, nl, j, F, &zr_r, &zr_z);
+            cd crf = rf_phase3_task_at<ROW>(Sm, lo, P, nl, j, F, &zr_r, &zr_z);
             rf_xst(Sm, j, crf);
             st_cd(Sm + lo.per_model + 2 * j, zr_r);
             st_cd(Sm + lo.per_model + 2 * P.nfreq + 2 * j, zr_z);
         } else {
-            cd crf = rf_phase3_task(Sm, lo, P, nl, j, F);
+            cd crf = rf_phase3_task_at<ROW>(Sm, lo, P, nl, j, F, nullptr, nullptr, A.ftab);
             rf_xst(Sm, j, crf);
         }
     }
@@ -1224,13 +1234,14 @@ hipError_t launch_rf(const RfArgs &A, hipStream_t stream)
 {
     const bool zr = A.out_fz != nullptr && A.out_fr != nullptr;
     size_t lds = rf_lds_bytes(A.P.Lmax, A.P.nsamp, A.P.M, zr);
-    static size_t lds_set[2][16] = {{0}, {0}};
-    hipError_t e = ensure_dyn_lds(zr ? (const void *)rf_kernel<true> : (const void *)rf_kernel<false>, lds,
-                                  lds_set[zr]);
+    const bool row = A.set_p != nullptr;              // per-row slowness
+    if (row && (zr || A.nsets < 1)) return hipErrorInvalidValue;
+    static size_t lds_set[3][16] = {{0}, {0}, {0}};
+    void (*kern)(RfArgs) = zr ? rf_kernel<true> : row ? rf_kernel<false, true> : rf_kernel<false>;
+    hipError_t e = ensure_dyn_lds((const void *)kern, lds, lds_set[zr ? 1 : row ? 2 : 0]);
     if (e != hipSuccess) return e;
     dim3 grid((A.B + A.P.M - 1) / A.P.M);
-    if (zr) hipLaunchKernelGGL(rf_kernel<true>, grid, dim3(RF_T), lds, stream, A);
-    else hipLaunchKernelGGL(rf_kernel<false>, grid, dim3(RF_T), lds, stream, A);
+    hipLaunchKernelGGL(kern, grid, dim3(RF_T), lds, stream, A);
     return hipGetLastError();
 }
 

@@ -86,7 +86,22 @@ BH_HD RfLayout rf_layout(int Lmax, int nsamp)
     return lo;
 }
 enum { RF_SC_H2 = 0, RF_SC_T0 = 8, RF_SC_M11 = 9, RF_SC_M12 = 10, RF_SC_M21 = 11, RF_SC_M22 = 12,
-       RF_SC_DECOMP = 13, RF_SC_UNIFORM_Q = 14 };
+       RF_SC_DECOMP = 13, RF_SC_UNIFORM_Q = 14,
+       RF_SC_P2 = 15 };                               // per-row form only: the model's own slowness^2
+
+// Per-row slowness (the per-row form of rf_kernel, kernels.h: RfArgs::set_p): row b takes the ray parameter of its
+// set from a table in s/deg, turned into s/km and squared by the two fp64 operations of rf_fill_launch
+// (rf_host.h), so that a row computed at table value x carries the constants of a uniform launch with p = x.
+// set_id null: every row takes set 0.  An index outside 0 .. nsets-1 reads nothing: *bad is set and the
+// slowness is NaN (the row comes out NaN).
+BH_DEV double rf_row_slowness(const double *BH_RESTRICT set_p, const int *BH_RESTRICT set_id, int nsets, long b,
+                              bool *bad)
+{
+    const int s = set_id ? set_id[b] : 0;
+    *bad = s < 0 || s >= nsets;
+    if (*bad) return __builtin_nan("");
+    return set_p[s] * 0.00899;                          // wrap.cpp:55,76
+}
 
 BH_DEV void st_cd(double *p, cd v) { p[0] = v.re; p[1] = v.im; }
 BH_DEV cd ld_cd(const double *p) { return mk(p[0], p[1]); }
@@ -239,14 +254,19 @@ BH_DEV cm2 rf_displacement2(double p, double vp, double vs)
     return m;
 }
 
-BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int i,
-                                double vp0_in, double vs0_in)
+// ROW (the per-row form): the model's slowness and its square are the row's own (row_u from rf_row_slowness,
+// row_u2 = row_u * row_u), which interface 0 leaves in the model's scalar block for phase 3, instead of the
+// launch's P.slowness and P.p2 -- which the uniform form reads where it always read them.
+template <bool ROW>
+BH_DEV void rf_phase2_interface_at(double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int i,
+                                   double vp0_in, double vs0_in, const double row_u, const double row_u2)
 {
     double *lay = S + lo.off_par;                       // layer k: lay + RF_REC * k
     double *rec = lay + RF_REC * i, *coef = rec + RF_P_COEF;
     cm2 rd = cm2_zero(), td = cm2_zero(), ru = cm2_zero(), tu = cm2_zero();
-    double u = P.slowness;
+    double u = ROW ? row_u : P.slowness;
     if (i == 0) {
+        if (ROW) S[lo.off_sc + RF_SC_P2] = row_u2;
         rf_coeffs(u, lay[RF_P_VP], lay[RF_P_VS], ru);
         // per-model scalars
         double *sc = S + lo.off_sc;
@@ -254,7 +274,7 @@ BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P
         double t0 = 0.;                         // greens.cpp:510-526 (includes half-space d = -1)
         const double *v = lay + (P.waveno == 0 ? RF_P_VP : RF_P_VS);
         for (int k = 0; k < nlay; k++)
-            t0 += lay[RF_REC * k + RF_P_D] * sqrt(1. / (v[RF_REC * k] * v[RF_REC * k]) - P.p2);
+            t0 += lay[RF_REC * k + RF_P_D] * sqrt(1. / (v[RF_REC * k] * v[RF_REC * k]) - (ROW ? row_u2 : P.p2));
         sc[RF_SC_T0] = t0;
         // one Q for all layers (what BayHunter passes): the complex velocity factor is then the same
         // for every layer of a frequency
@@ -270,7 +290,7 @@ BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P
         }
         double nsv = P.nsv > 0 ? P.nsv : vs0_in;
         double vpt = nsv * sqrt((1. - (sigma)) / (.5 - (sigma))), vst = nsv;
-        double pp = P.slowness;
+        double pp = ROW ? row_u : P.slowness;
         int dec = (vst > 0.01 && fabs(pp) > 0.0001) ? 1 : 0;   // greens.cpp:365
         double a = sqrt(1. / (vpt * vpt) - pp * pp), b = sqrt(1. / (vst * vst) - pp * pp);
         sc[RF_SC_M11] = -(2 * vst * vst * pp * pp - 1.) / (vpt * a);   // decomp, greens.cpp:328-333
@@ -290,6 +310,11 @@ BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P
                four[k]->c22.im == 0.;
     rec[RF_P_REAL] = real ? 1.0 : 0.0;
 }
+BH_DEV void rf_phase2_interface(double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int i,
+                                double vp0_in, double vs0_in)
+{
+    rf_phase2_interface_at<false>(S, lo, P, nlay, i, vp0_in, vs0_in, 0.0, 0.0);
+}
 
 // ---- P3: one frequency of one model (greens.cpp:528-585 + compute_rf :377-395) ----------------------
 // What a frequency needs that does not depend on the model: ln(w/wref) of the anelastic velocities
@@ -307,6 +332,14 @@ BH_DEV RfFreq rf_freq_load(const double *BH_RESTRICT ftab, int j)
     RfFreq F;
     F.lgw = ftab[RF_FTAB * j];
     F.cq = mk(ftab[RF_FTAB * j + 1], ftab[RF_FTAB * j + 2]);
+    return F;
+}
+// lgw alone, for the per-row form, which fetches cq behind the recursion (rf_phase3_body)
+BH_DEV RfFreq rf_freq_load_lgw(const double *BH_RESTRICT ftab, int j)
+{
+    RfFreq F;
+    F.lgw = ftab[RF_FTAB * j];
+    F.cq = mk(0., 0.);
     return F;
 }
 
@@ -368,12 +401,17 @@ BH_DEV void rf_layer_step(const double *ci, const double *cn, cd e11, cd e22, cm
     }
 }
 
-template <class M>
+// ROW (the per-row form): slowness^2 is the model's own, left in its scalar block by phase 2 -- one broadcast read
+// per task, like the other scalars -- instead of the launch's.  That is one more fp64 alive across the layer loop in a
+// kernel that has no register to spare (128 VGPRs, kernels.hip), so this form does not carry F.cq -- needed behind
+// the loop only -- through it: F comes from rf_freq_load_lgw and cq is fetched from ftab where it is used.
+template <class M, bool ROW>
 BH_DEV cd rf_phase3_body(const double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int j,
-                         const RfFreq &F, cd *zr_r, cd *zr_z)
+                         const RfFreq &F, cd *zr_r, cd *zr_z, const double *BH_RESTRICT ftab)
 {
     const double *lay = S + lo.off_par;                 // the record of layer i; the next one's coefficients
     const double *sc = S + lo.off_sc;
+    const double row_p2 = ROW ? sc[RF_SC_P2] : 0.0;
     const double w = P.dw * j;
     const double lgw = F.lgw;
     cm2 m = cm2_zero(), tq = cm2_zero(), g = cm2_zero();
@@ -395,8 +433,8 @@ BH_DEV cd rf_phase3_body(const double *S, const RfLayout &lo, const RfLaunch &P,
             gp = crecip(fp * fp);
             gs = crecip(fs * fs);
         }
-        cd plc = csqrt_fast(gp * lay[RF_P_IVP2] - P.p2);         // Q finite -> im != 0
-        cd slc = csqrt_fast(gs * lay[RF_P_IVS2] - P.p2);
+        cd plc = csqrt_fast(gp * lay[RF_P_IVP2] - (ROW ? row_p2 : P.p2));   // Q finite -> im != 0
+        cd slc = csqrt_fast(gs * lay[RF_P_IVS2] - (ROW ? row_p2 : P.p2));
         cd e11 = cexp_bounded(mk(wd * plc.im, -(wd * plc.re))), e22 = cexp_bounded(mk(wd * slc.im, -(wd * slc.re)));
         const double *ci = lay + RF_P_COEF, *cn = ci + RF_REC;
         if (i == 0) rf_layer_step<M, true>(ci, cn, e11, e22, m, tq, g);
@@ -427,21 +465,34 @@ BH_DEV cd rf_phase3_body(const double *S, const RfLayout &lo, const RfLaunch &P,
     if (P.waveno == 1) { cd tmp = cz; cz = cr; cr = tmp; }        // greens.cpp:369-373
     double denom = cz.re * cz.re + cz.im * cz.im;                 // real(cz*conj(cz)); no water level
     cd crf = (cr * conj(cz)) / denom;
-    const cd cq = F.cq;                                           // q exp(-(w/a)^2/4 - i w tshift), host table
+    const cd cq = ROW ? rf_freq_load(ftab, j).cq : F.cq;          // q exp(-(w/a)^2/4 - i w tshift), host table
     if (zr_r) { *zr_r = arr_r * cq; *zr_z = arr_z * cq; }       // greens.cpp:393-394 (for iftr2)
+    // crf * cq with the contraction written out: left to the compiler, the two forms fused different products of the
+    // imaginary part (the per-row form has cq arrive late) and differed in the last bit.  This is the pairing the
+    // uniform form always had; the host replay is compiled without contraction, as before.
+#if defined(BH_HOSTSIM)
     return crf * cq;
+#else
+    return cmul(crf, cq);
+#endif
 }
 
-BH_DEV cd rf_phase3_task(const double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int j,
-                         const RfFreq &F, cd *zr_r = nullptr, cd *zr_z = nullptr)
+template <bool ROW>
+BH_DEV cd rf_phase3_task_at(const double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int j,
+                            const RfFreq &F, cd *zr_r, cd *zr_z, const double *BH_RESTRICT ftab = nullptr)
 {
     // all interface matrices of this model real (no post-critical wave anywhere): half the
     // multiplications in the products with rd, td, ru, tu
     const double *flag = S + lo.off_par + RF_P_REAL;
     bool real = true;
     for (int i = 0; i < nlay; i++) real = real && flag[RF_REC * i] != 0.0;
-    return real ? rf_phase3_body<rm2>(S, lo, P, nlay, j, F, zr_r, zr_z)
-                : rf_phase3_body<cm2>(S, lo, P, nlay, j, F, zr_r, zr_z);
+    return real ? rf_phase3_body<rm2, ROW>(S, lo, P, nlay, j, F, zr_r, zr_z, ftab)
+                : rf_phase3_body<cm2, ROW>(S, lo, P, nlay, j, F, zr_r, zr_z, ftab);
+}
+BH_DEV cd rf_phase3_task(const double *S, const RfLayout &lo, const RfLaunch &P, int nlay, int j,
+                         const RfFreq &F, cd *zr_r = nullptr, cd *zr_z = nullptr)
+{
+    return rf_phase3_task_at<false>(S, lo, P, nlay, j, F, zr_r, zr_z);
 }
 
 #if !defined(BH_HOSTSIM)

@@ -31,6 +31,7 @@ class EvalPlan(object):
         self.lib = _lib.load()
         lay, desc = layout['layout'], layout['desc']
         self.rows, self.Lmax, self.T, self.row = int(max_models), int(Lmax), len(desc), int(lay.row)
+        self.nrf = len(lay.rf)
         interp = lay.interp([sp.obsx.ctypes.data for _, _, _, sp in lay.resampled])   # (copied by bh_eval_create)
         self.handle = C.c_void_p()
         _lib.check(self.lib.bh_eval_create(
@@ -72,6 +73,15 @@ class EvalPlan(object):
         _lib.check(self.lib.bh_eval_set_observations(
             self._live(), yobs.shape[0], yobs.ctypes.data, *[None if t is None else t.ctypes.data for t in tabs],
             soc.ctypes.data, soc.size))
+
+    def set_rf_slowness(self, p):
+        """Per-set ray parameters of the receiver-function targets (bh_eval_set_rf_slowness): p[nsets, nrf] in s/deg,
+        nsets that of `set_observations`, which comes first; the targets in the order of the layout's `rf`.  Once,
+        before the first submit.  Every row is then computed at the slowness of its chain's set."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != self.nrf:
+            raise ValueError("p: one row of %d ray parameters (one per receiver-function target) per observation set" % self.nrf)
+        _lib.check(self.lib.bh_eval_set_rf_slowness(self._live(), p.shape[0], p.ctypes.data))
 
     def set_concurrency(self, plans_in_flight):
         """How many plans take turns on the device (the chain groups of a pool): the library chooses its kernel

@@ -13,8 +13,19 @@ it is in, so a station's chains are bit for bit the chains of a `ChainPool` of t
     pool.station('ST2').posterior()          # the interface of a ChainPool, restricted to the station's chains
     pool.save()                              # one directory per station, each what a single-station pool writes
 
-What may differ between stations is deliberately little: per-station periods, time axes, slowness or priors would
-need per-row descriptors in the forward kernels and per-chain configurations in the sampler.
+One plugin parameter may differ between stations when the pool is told so: the ray parameter `p` of a receiver
+function, which in a real network is the mean slowness of the events stacked at each station.
+
+    StationPool(stations, ..., per_station=('p',))     # every station's RFminiModRF keeps its own modelparams['p']
+
+The receiver-function kernel then takes each row's slowness from a table indexed by the row's station
+(bh_rf_batch_sets, bh_eval_set_rf_slowness) -- the index the likelihood already uses -- and a row is bit for bit
+what the uniform kernel computes at that `p`, so the sentence above about a station's chains still holds.
+
+Everything else stays per pool.  A per-station `gauss` would need a frequency table and a count of active
+frequencies per set in the receiver-function kernel, per-station `nsv` or time axes per-row launch constants,
+per-station periods per-row descriptors in the dispersion kernels, per-station priors per-chain configurations in
+the sampler: all of these are refused.
 """
 import inspect
 import os
@@ -33,9 +44,26 @@ def _plugin_params(target):
     return type(p).__name__, dict(getattr(p, 'modelparams', None) or {})
 
 
-def check_stations(names, joints):
+PER_STATION = ('p',)         # plugin parameters of receiver-function targets that StationPool(per_station=...) takes
+
+
+def check_per_station(per_station):
+    """-> tuple of the names; ValueError for anything but the supported ones."""
+    if isinstance(per_station, str):
+        per_station = (per_station,)
+    per_station = tuple(per_station or ())
+    for key in per_station:
+        if key not in PER_STATION:
+            raise ValueError("per_station=%r: only %s of a receiver-function target may differ between stations (gauss, nsv, "
+                             "time axes and periods are per pool)" % (key, ', '.join(repr(k) for k in PER_STATION)))
+    return per_station
+
+
+def check_stations(names, joints, per_station=()):
     """All stations share the row layout (targets, their order, x axes, plugin parameters) and the covariance model
-    of each target (after set_target_covariance): ValueError naming the station and the property otherwise."""
+    of each target (after set_target_covariance): ValueError naming the station and the property otherwise.
+    per_station: plugin parameters (of PER_STATION) that the receiver-function targets need not share."""
+    per_station = check_per_station(per_station)
     first, name0 = joints[0], names[0]
     for name, joint in zip(names[1:], joints[1:]):
         who = "station %r differs from station %r: " % (name, name0)
@@ -56,6 +84,8 @@ def check_stations(names, joints):
             if acls != bcls:
                 raise ValueError(what + "(%s) forward plugin (%s, %s)" % (a.ref, acls, bcls))
             for key in sorted(set(apar) | set(bpar)):
+                if key in per_station and a.noiseref == 'rf' and key in apar and key in bpar:
+                    continue
                 if key not in apar or key not in bpar or apar[key] != bpar[key]:
                     raise ValueError(what + "(%s) plugin parameter %r (%r, %r); per-station plugin parameters are "
                                      "not supported" % (a.ref, key, apar.get(key), bpar.get(key)))
@@ -90,14 +120,24 @@ def observation_tables(joints):
     return np.stack(yobs), np.stack(scale), np.stack(logdet)
 
 
+def rf_slowness_table(joints):
+    """p[nstations, nrf]: modelparams['p'] of every station's own receiver-function plugins, in the order of the row
+    layout's receiver functions (JointTarget.batch_layout)."""
+    from .plugins import RFminiModRF
+    return np.array([[float(t.moddata.plugin.modelparams['p']) for t in joint.targets
+                      if isinstance(t.moddata.plugin, RFminiModRF)] for joint in joints], dtype=np.float64)
+
+
 class StationGpuEvaluator(GpuEvaluator):
     """GpuEvaluator whose evaluation plans carry one observation set per station: a plan is built from the first
-    station's layout and given every station's observed data and the station of each of its group's chains."""
+    station's layout and given every station's observed data and the station of each of its group's chains -- and,
+    with per_station=('p',), every station's ray parameters."""
     per_chain = True
 
-    def __init__(self, joints, station_of_chain, device=None):
+    def __init__(self, joints, station_of_chain, device=None, per_station=()):
         GpuEvaluator.__init__(self, joints[0], device)
         self.joints, self.station_of_chain = list(joints), np.asarray(station_of_chain, dtype=np.int32)
+        self.per_station = check_per_station(per_station)
         self._tables = None
 
     def buffers(self, rows, Lmax, ntargets, chains):
@@ -105,7 +145,10 @@ class StationGpuEvaluator(GpuEvaluator):
             self._tables = observation_tables(self.joints)
         packed, nlay, noise, chain = GpuEvaluator.buffers(self, rows, Lmax, ntargets)
         yobs, scale, logdet = self._tables
-        self._plans[packed.ctypes.data].set_observations(yobs, self.station_of_chain[chains[0]:chains[1]], scale, logdet)
+        plan = self._plans[packed.ctypes.data]
+        plan.set_observations(yobs, self.station_of_chain[chains[0]:chains[1]], scale, logdet)
+        if 'p' in self.per_station and plan.nrf:
+            plan.set_rf_slowness(rf_slowness_table(self.joints))
         return packed, nlay, noise, chain
 
 
@@ -179,6 +222,10 @@ class StationPool(object):
     evaluator           None: the GPU (one evaluation plan per chain group, carrying every station's observations);
                         a function (packed, nlay, noise, station[B]) -> (logL, misfits); a function of three
                         arguments or an object with buffers/submit/collect is passed to ChainPool as it is
+    per_station         () or ('p',): plugin parameters of the receiver-function targets that every station keeps
+                        for itself (the ray parameter; module docstring).  Without it stations that differ in `p`
+                        are refused like any other difference; any other name: ValueError listing what is supported.
+                        CPU evaluators get each row's station and use that station's own plugin as they always did
     groups, nthreads, nmodels, lookahead   as for ChainPool
     shard               not supported yet (stations would have to be sharded whole): ValueError
 
@@ -186,7 +233,8 @@ class StationPool(object):
 
     def __init__(self, stations, initparams=None, modelpriors=None, chains_per_station=None, random_seeds=None,
                  seeds=None, evaluator=None, groups=None, nthreads=None, shard=None, nmodels=None, lookahead=None,
-                 device=None):
+                 device=None, per_station=()):
+        self.per_station = check_per_station(per_station)
         if shard is not None:
             raise ValueError("StationPool does not take shard=(rank, world) yet: give every rank a StationPool of its "
                              "own stations")
@@ -240,9 +288,9 @@ class StationPool(object):
         for joint in self.stations[1:]:
             joint.set_target_covariance(corrfix, corr, rcond)
         first.set_target_covariance(corrfix, corr, rcond)
-        check_stations(self.names, self.stations)
+        check_stations(self.names, self.stations, self.per_station)
         if evaluator is None:
-            evaluator = StationGpuEvaluator(self.stations, self.station_of_chain, device)
+            evaluator = StationGpuEvaluator(self.stations, self.station_of_chain, device, self.per_station)
         elif not hasattr(evaluator, 'submit') and _takes_station(evaluator):
             evaluator = StationCallEvaluator(evaluator, self.station_of_chain)
         self.pool = ChainPool(first, initparams=ip, modelpriors=modelpriors, nchains=S * c, seeds=seeds.reshape(-1),

@@ -170,6 +170,20 @@ int bh_rf_batch(int B, int Lmax, int model_stride, const int *nlay, const double
                 const double *qs, /* qp/qs: [B][Lmax] (stride Lmax) or NULL */
                 const bh_rf_params *par, double *out, int out_stride,
                 void *workspace, size_t workspace_bytes, void *stream);
+/* bh_rf_batch with a ray parameter per row: row b is computed at p = set_p[set_id[b]] [s/deg] and par->p is ignored
+ * (the rows of a pool of stations, each station with the mean slowness of its own events).  set_p: DEVICE [nsets];
+ * set_id: DEVICE int[B], or NULL with nsets == 1 (every row takes set_p[0]).  Everything else a receiver function
+ * depends on (gauss, fsamp, tshift, nsv, nsamp, waveno) is the call's.  A row's result is, bit for bit, the row
+ * bh_rf_batch gives for that model with par->p = set_p[set_id[b]].  A row whose set_id is outside 0 .. nsets-1 is
+ * NaN and reads nothing of the table.  nsets < 1, a NULL table, set_id == NULL with nsets > 1 and the parameters
+ * bh_rf_batch refuses are refused before the first launch; the VALUES of the table live on the device and cannot
+ * be checked by the call: a NaN or infinite p gives that set's rows as NaN, which is what bh_rf_batch gives for
+ * such a par->p. */
+int bh_rf_batch_sets(int B, int Lmax, int model_stride, const int *nlay, const double *h,
+                     const double *vp, const double *vs, const double *rho, const double *qp,
+                     const double *qs, const bh_rf_params *par, int nsets, const double *set_p,
+                     const int *set_id, double *out, int out_stride,
+                     void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- Voronoi nuclei -> layered models + prior checks (device pointers) ------------------- */
 /* The step in front of the forward path: Model.get_vp_vs_h (src/Models.py:26-52) and
@@ -463,6 +477,15 @@ int  bh_eval_wait(bh_eval_plan *plan, int *count);   /* blocks until the last su
  * are checked before the first device call. */
 int  bh_eval_set_observations(bh_eval_plan *plan, int nsets, const double *yobs, const double *set_scale,
                               const double *set_logdet, const int *set_of_chain, int nchains);
+/* Per-station ray parameters for a plan with observation sets: p[nsets][nrf] [s/deg], HOST, copied once -- the slowness
+ * of receiver-function target i (the order of bh_eval_create's rf[]) at set s is p[s * nrf + i]; rf[i].p is ignored
+ * from then on.  Callable once, after bh_eval_set_observations (whose nsets it must equal) and before the first
+ * bh_eval_submit; non-finite values and a plan without receiver-function targets are refused.  The forward stage then
+ * runs every receiver function as bh_rf_batch_sets with the set index bh_eval_submit uploads per row for the
+ * likelihood (one array for both).  A plan without this call computes every row at rf[i].p, as before.  The table
+ * belongs to the plan and goes with it in bh_eval_destroy.  What else a receiver function depends on (gauss, nsv,
+ * the time axis) and the periods of a dispersion target stay per plan. */
+int  bh_eval_set_rf_slowness(bh_eval_plan *plan, int nsets, const double *p);
 /* How many plans take turns on the device (a pool's chain groups; default 1): passed on as bh_swd_hint's second
  * argument with every submission. */
 int  bh_eval_set_concurrency(bh_eval_plan *plan, int plans_in_flight);

@@ -25,6 +25,9 @@ def kernel_resources(source='kernels.hip'):
         field = lambda k: int(re.search(r'\.amdhsa_%s (\d+)' % k, m.group(2)).group(1))
         name = re.sub(r'^_ZN2bh\d+', '', m.group(1))
         name = re.sub(r'ENS_\d+\w+E$|EvNS_\d+\w+E$', '', name).replace('ILb0EE', '<false>').replace('ILb1EE', '<true>')
+        # rf_kernel<ZR, ROW>: the uniform forms keep the names they had with one parameter, the per-row form is
+        # 'rf_kernel<false, true>'
+        name = name.replace('ILb0ELb0EE', '<false>').replace('ILb1ELb0EE', '<true>').replace('ILb0ELb1EE', '<false, true>')
         out[name] = dict(vgpr=field('next_free_vgpr'), sgpr=field('next_free_sgpr'),
                          scratch=field('private_segment_fixed_size'))
     return out

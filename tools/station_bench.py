@@ -9,7 +9,11 @@ vp/vs and noise, like tools/chain_bench.py).  For S stations of c chains each, t
                the output: "scaled": true)
 
     python tools/station_bench.py [--modes stations,onepool,singles] [--repeats 5] [--sample 16] [--root DIR]
-                                  [--out FILE.jsonl] [SxC ...]            (default 64x16 256x16 1024x16 1024x4)
+                                  [--vary-p LO HI] [--out FILE.jsonl] [SxC ...]   (default 64x16 256x16 1024x16 1024x4)
+
+--vary-p LO HI: every station its own receiver-function ray parameter, spread evenly over [LO, HI] s/deg; the station
+pool runs with per_station=('p',) (the per-row form of rf_kernel), the single pools each at their station's p, `onepool`
+at station 0's.
 
 A warm-up pool of every mode runs first; then `--repeats` rounds, each round running every mode once (alternating,
 so that a drift of the box hits all modes alike).  One JSON line per (S, c, mode) with every repeat's seconds,
@@ -31,6 +35,8 @@ def main():
     ap.add_argument('--sample', type=int, default=16)
     ap.add_argument('--iters', type=int, default=None, help='burn-in iterations (main phase: half of it)')
     ap.add_argument('--root', default=None, help='tree whose bayhunter_amd is measured (default: this one)')
+    ap.add_argument('--vary-p', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                    help="stations with p spread evenly over [LO, HI] s/deg, pooled with per_station=('p',)")
     ap.add_argument('--tag', default=None)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -63,7 +69,8 @@ def main():
         kw = dict(nmodels=iters + iters // 2 + 1)     # room for every iteration
         if mode == 'stations':
             from bayhunter_amd.stations import StationPool
-            with StationPool(stations, ip, case['priors'], seeds=seeds, **kw) as pool:
+            per = dict(per_station=('p',)) if args.vary_p else {}
+            with StationPool(stations, ip, case['priors'], seeds=seeds, **per, **kw) as pool:
                 t0 = time.perf_counter()
                 pool.run()
                 return time.perf_counter() - t0, S
@@ -85,6 +92,9 @@ def main():
         S, c = (int(v) for v in cfg.lower().split('x'))
         iters = args.iters or (120 if S * c <= 4096 else 60)
         stations = make_stations(data, S, yerr=True)
+        if args.vary_p:
+            for joint, p in zip(stations, np.linspace(args.vary_p[0], args.vary_p[1], S)):
+                joint.targets[1].moddata.plugin.set_modelparams(p=float(p))
         for mode in modes:                      # first-use costs (kernel forms, helper threads, pinned buffers, the
             run(mode, S, c, 6, stations)        # set-up's factorisation) are not chain iterations
         time.sleep(0.25)                        # numpy's BLAS workers spin ~0.1 s after the set-up's factorisation
@@ -98,7 +108,7 @@ def main():
         total = S * c * (iters + iters // 2)
         for mode in modes:
             v = np.asarray(secs[mode])
-            rec = dict(bench='station_pool', tag=args.tag, mode=mode, stations=S, chains_per_station=c, chains=S * c,
+            rec = dict(bench='station_pool', tag=args.tag, vary_p=args.vary_p, mode=mode, stations=S, chains_per_station=c, chains=S * c,
                        iterations=iters + iters // 2, repeats=args.repeats, seconds=[round(float(x), 4) for x in v],
                        median_s=round(float(np.median(v)), 4), min_s=round(float(v.min()), 4),
                        max_s=round(float(v.max()), 4), chain_iterations_per_s=round(total / float(np.median(v))),
