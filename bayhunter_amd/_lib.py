@@ -12,9 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
-           "datafits.hip"]
+           "posterior_sets.hip", "datafits.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h",
-           "swd_form_table.h", "posterior_core.h", "stats_core.h", "stats_host.h"]
+           "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "stats_core.h",
+           "stats_host.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->
@@ -229,6 +230,13 @@ _SIGS = {
     "bh_posterior_scan": (C.c_int, [_vp, C.POINTER(C.c_longlong), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_longlong)]),
     "bh_posterior_finish": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "bh_posterior_destroy": (None, [_vp]),
+    "bh_posterior_sets_create": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, _vp, C.c_int, _vp,
+                                           C.c_int, _vp, C.c_int, _vp, C.POINTER(_vp)]),
+    "bh_posterior_sets_scan": (C.c_int, [_vp] * 9),
+    "bh_posterior_sets_finish": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
+    "bh_posterior_sets_destroy": (None, [_vp]),
+    "bh_posterior_sets_status_text": (C.c_char_p, [C.c_int]),
+    "bh_posterior_sets_set_chunk_bytes": (C.c_int, [_vp, C.c_longlong]),
     "bh_datafits_create": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, C.c_int, _vp,
                                      C.POINTER(_vp)]),
     "bh_datafits_scan": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _vp, _vp, _vp]),

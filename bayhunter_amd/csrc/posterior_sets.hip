@@ -1,0 +1,489 @@
+// posterior_sets.hip -- the velocity-depth posterior of many sets of rows at once (bh_posterior_sets_*).
+//
+// A network inverted in one pool (StationPool) is read station by station: the statistics of posterior.hip over each
+// station's rows.  One bh_posterior handle per station is a few thousand rows per launch, i.e. the latency of its
+// launches, copies and synchronisations times the number of stations.  Here the rows come in contiguous segments,
+// one per set, and a block belongs to one set: blockIdx.z names it, and the block runs the very body post_kernel
+// runs (posterior_kernel.h) over the set's rows, as block x of the G blocks a handle of that many rows would have
+// launched, with the set's own outputs.  The slab of a set is added in block order like there, the mean and the
+// standard deviation leave the host through the same expressions: every number of a set is bit for bit the number
+// of a single-set handle over its rows.
+//
+//   scan     one launch (grid: blocks of the largest set, depth tiles, sets) and one slab reduction
+//   finish   per set its own Vs edges (concatenated, with offsets) and histogram; the select runs over
+//            nsets * D columns with each set's two middle ranks; one launch per radix pass for all sets
+//   chunks   the select's digit table is 2 * 256 * 8 B per column, so the sets are taken in chunks whose table
+//            stays under a budget; a set is never split, and nothing a set's blocks compute depends on the chunk
+#include <cstring>
+#include <memory>
+#include <new>
+#include "posterior_kernel.h"
+
+namespace {
+
+using bh::u64;
+using namespace bh::post;
+
+constexpr long long kDigitBudget = 64ll << 20;       // bytes of digit table per chunk (bh_posterior_sets_set_chunk_bytes)
+
+enum { S_SKIP = 1, S_HIST_GLOBAL = 2 };              // per set, for the finish
+
+struct SetArgs {
+    const long long *start;            // [nsets + 1] rows of set z: start[z] .. start[z + 1]
+    int first, Gmax;                   // the chunk's first set; blocks per set in the slab and the argmin partials
+    const int *sflags;                 // [nsets] finish: S_SKIP, S_HIST_GLOBAL
+    const int *vedge_off;              // [nsets + 1] into vedges
+    const u64 *hist_off;               // [nsets + 1] into hist
+};
+
+template <typename T, int MODE>
+__global__ __launch_bounds__(kThreads) void post_sets_kernel(PostArgs a, SetArgs s)
+{
+    const int zl = blockIdx.z, z = s.first + zl;
+    const long long r0 = s.start[z], r1 = s.start[z + 1];
+    const int G = blocks_of(r1 - r0), bx = blockIdx.x;
+    if (bx >= G) return;
+    const size_t col = (size_t)z * a.D;
+    a.slab += (size_t)zl * s.Gmax * a.D;
+    if (MODE == MODE_SCAN) {
+        a.kmin += col;
+        a.kmax += col;
+        a.cnt += 2 * (size_t)z;
+        a.nlay += (size_t)z * (a.maxn + 1);
+        if (a.nif > 1) a.ifhist += (size_t)z * (a.nif - 1);
+        a.mfkey += (size_t)z * s.Gmax;
+        a.mfrow += (size_t)z * s.Gmax;
+    } else {
+        const int f = s.sflags[z];
+        if (f & S_SKIP) return;
+        a.mean += col;
+        if (a.flags & F_HIST) {
+            a.vedges += s.vedge_off[z];
+            a.nve = s.vedge_off[z + 1] - s.vedge_off[z];
+            a.hist += s.hist_off[z];
+            if (f & S_HIST_GLOBAL) a.flags |= F_HIST_GLOBAL;
+        }
+        if (a.flags & F_RADIX) {
+            a.gbase += (size_t)zl * a.D;
+            a.ngroups += (size_t)zl * a.D;
+        }
+    }
+    post_block<T, MODE>(a, r0, r1, bx, G);
+}
+
+// Σ over a set's blocks in block order: one thread per (set of the chunk, column)
+__global__ void sets_reduce_kernel(const double *slab, const long long *start, int first, int nc, int Gmax, int D,
+                                   double *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nc * D) return;
+    const int zl = i / D, c = i % D, z = first + zl;
+    const int G = blocks_of(start[z + 1] - start[z]);
+    double s = 0.0;
+    for (int g = 0; g < G; g++) s = s + slab[((size_t)zl * Gmax + g) * D + c];
+    out[(size_t)z * D + c] = s;
+}
+
+}  // namespace
+
+struct bh_posterior_sets {
+    int fp64 = 0, width = 0, nif = 0, maxn = 0, D = 0, nsets = 0, Gmax = 1, chunk = 1, scanned = 0;
+    const void *rows = nullptr;
+    long long nrows = 0, stride = 0;
+    const int *w = nullptr;
+    const double *misfit = nullptr;
+    hipStream_t st = nullptr;
+    std::vector<long long> start;      // [nsets + 1]
+    std::vector<u64> total;            // [nsets] of the scan
+    std::vector<int> status;           // [nsets] of the scan
+    bh::DevBufs bufs;
+    // device
+    long long *dstart = nullptr;
+    double *dep = nullptr, *ifedges = nullptr;
+    double *slab = nullptr, *red = nullptr, *dmean = nullptr;    // [chunk][Gmax][D], [nsets][D], [nsets][D]
+    u64 *kmin = nullptr, *kmax = nullptr;                        // [nsets][D]
+    u64 *cnt = nullptr, *nlay = nullptr, *ifhist = nullptr, *mfkey = nullptr;
+    long long *mfrow = nullptr;
+    int *sflags = nullptr;
+
+    int G(int z) const { return blocks_of(start[z + 1] - start[z]); }
+    int chunk_blocks(int first, int nc) const
+    {
+        int g = 1;
+        for (int z = first; z < first + nc; z++) g = G(z) > g ? G(z) : g;
+        return g;
+    }
+};
+
+namespace {
+
+template <typename T, int MODE>
+int launch(bh_posterior_sets *p, PostArgs &a, SetArgs &s, int nc, size_t lds_bytes)
+{
+    dim3 grid((unsigned)p->chunk_blocks(s.first, nc), (unsigned)((p->D + kTile - 1) / kTile), (unsigned)nc);
+    hipLaunchKernelGGL((post_sets_kernel<T, MODE>), grid, dim3(kThreads), lds_bytes, p->st, a, s);
+    STATS_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+template <int MODE>
+int run(bh_posterior_sets *p, PostArgs &a, SetArgs &s, int nc, size_t lds_bytes)
+{
+    return p->fp64 ? launch<double, MODE>(p, a, s, nc, lds_bytes) : launch<float, MODE>(p, a, s, nc, lds_bytes);
+}
+
+// the chunk's slab, added up per set into red
+int reduce_chunk(bh_posterior_sets *p, int first, int nc)
+{
+    hipLaunchKernelGGL(sets_reduce_kernel, dim3((unsigned)((nc * p->D + 255) / 256)), dim3(256), 0, p->st,
+                       (const double *)p->slab, (const long long *)p->dstart, first, nc, p->Gmax, p->D, p->red);
+    STATS_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+PostArgs base_args(const bh_posterior_sets *p)
+{
+    PostArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.rows = p->rows;
+    a.nrows = p->nrows;
+    a.stride = p->stride;
+    a.width = p->width;
+    a.D = p->D;
+    a.w = p->w;
+    a.misfit = p->misfit;
+    a.dep = p->dep;
+    a.slab = p->slab;
+    a.maxn = p->maxn;
+    return a;
+}
+
+template <typename T>
+int fetch(std::vector<T> &host, const T *dev, size_t count, hipStream_t st)
+{
+    host.resize(count);
+    if (count) STATS_HIP(hipMemcpyAsync(host.data(), dev, sizeof(T) * count, hipMemcpyDeviceToHost, st));
+    return BH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bh_posterior_sets_set_chunk_bytes(bh_posterior_sets *p, long long bytes)
+{
+    if (!p) return bh::fail_arg_("post is NULL");
+    if (p->slab) return bh::fail_arg_("bh_posterior_sets_set_chunk_bytes after bh_posterior_sets_scan");
+    const long long fit = (bytes > 0 ? bytes : kDigitBudget) / ((long long)p->D * 2 * 256 * (long long)sizeof(u64));
+    p->chunk = (int)(fit < 1 ? 1 : fit > p->nsets ? p->nsets : fit);
+    return BH_OK;
+}
+
+const char *bh_posterior_sets_status_text(int status)
+{
+    return status == BH_POSTERIOR_SET_EMPTY ? bh::scan_fault(0, 0)
+           : status == BH_POSTERIOR_SET_OVERFLOW ? bh::scan_fault(~0ull, 0) : "";
+}
+
+int bh_posterior_sets_create(const void *rows, int fp64, long long nrows, long long stride, int width,
+                             const int *weights, const double *misfits, const long long *set_start, int nsets,
+                             const double *dep, int ndep, const double *ifedges, int nifedges, void *stream,
+                             bh_posterior_sets **post)
+{
+    if (!post) return bh::fail_arg_("post is NULL");
+    *post = nullptr;
+    if (!rows || nrows < 1) return bh::fail_arg_("bh_posterior_sets_create: no rows (empty selection)");
+    if (nrows > (1ll << 32)) return bh::fail_arg_("bh_posterior_sets_create: more than 2^32 rows (the weight total could overflow)");
+    if (width < 2 || width > 2 * BH_MAX_LAYERS + 2 || stride < width) return bh::fail_arg_("bh_posterior_sets_create: width / stride");
+    if (nsets < 1 || nsets > 65535) return bh::fail_arg_("bh_posterior_sets_create: 1 to 65535 sets");
+    if (!set_start || set_start[0] != 0 || set_start[nsets] != nrows)
+        return bh::fail_arg_("bh_posterior_sets_create: set_start must begin at 0 and end at nrows");
+    for (int z = 0; z < nsets; z++)
+        if (set_start[z] > set_start[z + 1]) return bh::fail_arg_("bh_posterior_sets_create: set_start must be ascending");
+    if (!dep || ndep < 1 || !bh::ascending(dep, ndep)) return bh::fail_arg_("bh_posterior_sets_create: the depth grid must be ascending");
+    if ((long long)nsets * ndep > 0x3fffffff) return bh::fail_arg_("bh_posterior_sets_create: more than 2^30 (set, depth) columns");
+    if (nifedges && (nifedges < 2 || !ifedges || !bh::ascending(ifedges, nifedges)))
+        return bh::fail_arg_("bh_posterior_sets_create: interface edges must be ascending");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
+        return BH_ERR_NO_DEVICE;
+    }
+    std::unique_ptr<bh_posterior_sets> p(new (std::nothrow) bh_posterior_sets);
+    if (!p) return bh::fail_arg_("out of memory");
+    p->fp64 = fp64 ? 1 : 0;
+    p->rows = rows;
+    p->nrows = nrows;
+    p->stride = stride;
+    p->width = width;
+    p->w = weights;
+    p->misfit = misfits;
+    p->D = ndep;
+    p->nsets = nsets;
+    p->nif = nifedges;
+    p->maxn = width / 2;
+    p->st = (hipStream_t)stream;
+    p->start.assign(set_start, set_start + nsets + 1);
+    p->total.assign(nsets, 0);
+    p->status.assign(nsets, BH_POSTERIOR_SET_EMPTY);
+    p->Gmax = p->chunk_blocks(0, nsets);
+    (void)bh_posterior_sets_set_chunk_bytes(p.get(), 0);
+    const size_t cols = (size_t)nsets * ndep;
+    STATS_HIP(p->bufs.alloc(p->dstart, (size_t)nsets + 1));
+    STATS_HIP(p->bufs.alloc(p->red, cols));
+    STATS_HIP(p->bufs.alloc(p->dmean, cols));
+    STATS_HIP(p->bufs.alloc(p->kmin, cols));
+    STATS_HIP(p->bufs.alloc(p->kmax, cols));
+    STATS_HIP(p->bufs.alloc(p->dep, ndep));
+    STATS_HIP(p->bufs.alloc(p->cnt, 2 * (size_t)nsets));
+    STATS_HIP(p->bufs.alloc(p->nlay, (size_t)nsets * (p->maxn + 1)));
+    STATS_HIP(p->bufs.alloc(p->mfkey, (size_t)nsets * p->Gmax));
+    STATS_HIP(p->bufs.alloc(p->mfrow, (size_t)nsets * p->Gmax));
+    STATS_HIP(p->bufs.alloc(p->sflags, nsets));
+    STATS_HIP(hipMemcpyAsync(p->dstart, p->start.data(), sizeof(long long) * (nsets + 1), hipMemcpyHostToDevice, p->st));
+    STATS_HIP(hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st));
+    if (nifedges) {
+        STATS_HIP(p->bufs.alloc(p->ifedges, nifedges));
+        STATS_HIP(p->bufs.alloc(p->ifhist, (size_t)nsets * (nifedges - 1)));
+        STATS_HIP(hipMemcpyAsync(p->ifedges, ifedges, sizeof(double) * nifedges, hipMemcpyHostToDevice, p->st));
+    }
+    STATS_HIP(hipStreamSynchronize(p->st));
+    *post = p.release();
+    return BH_OK;
+}
+
+void bh_posterior_sets_destroy(bh_posterior_sets *post)
+{
+    if (post) {
+        (void)hipStreamSynchronize(post->st);
+        delete post;
+    }
+}
+
+int bh_posterior_sets_scan(bh_posterior_sets *p, long long *total, double *vmin, double *vmax, double *mean,
+                           long long *nlayers, long long *ifhist, long long *argmin, int *status)
+{
+    if (!p) return bh::fail_arg_("post is NULL");
+    if (!status) return bh::fail_arg_("bh_posterior_sets_scan: status is NULL");
+    p->scanned = 0;
+    if (!p->slab) STATS_HIP(p->bufs.alloc(p->slab, (size_t)p->chunk * p->Gmax * p->D));   // the chunk is settled now
+    const int D = p->D, S = p->nsets, nl1 = p->maxn + 1, nih = p->nif > 1 ? p->nif - 1 : 0;
+    const int cols = S * D;
+    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmin, cols, ~0ull);
+    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmax, cols, 0ull);
+    STATS_HIP(hipGetLastError());
+    STATS_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2 * S, p->st));
+    STATS_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (size_t)S * nl1, p->st));
+    if (nih) STATS_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (size_t)S * nih, p->st));
+    PostArgs a = base_args(p);
+    a.flags = F_ROWS;
+    a.kmin = p->kmin;
+    a.kmax = p->kmax;
+    a.cnt = p->cnt;
+    a.nlay = p->nlay;
+    a.ifedges = p->ifedges;
+    a.nif = p->nif;
+    a.ifhist = p->ifhist;
+    a.mfkey = p->mfkey;
+    a.mfrow = p->mfrow;
+    a.off_nlay = 0;
+    a.off_if = nl1;
+    const size_t lds = sizeof(u64) * (size_t)(nl1 + nih);
+    SetArgs s;
+    std::memset(&s, 0, sizeof(s));
+    s.start = p->dstart;
+    s.Gmax = p->Gmax;
+    for (int first = 0; first < S; first += p->chunk) {
+        const int nc = S - first < p->chunk ? S - first : p->chunk;
+        s.first = first;
+        int rc = run<MODE_SCAN>(p, a, s, nc, lds);
+        if (!rc) rc = reduce_chunk(p, first, nc);
+        if (rc) return rc;
+    }
+    std::vector<u64> cnt, nl, ih, mk, kmn, kmx;
+    std::vector<long long> mr;
+    std::vector<double> sum;
+    int rc = fetch(cnt, p->cnt, 2 * (size_t)S, p->st);
+    if (!rc) rc = fetch(nl, p->nlay, (size_t)S * nl1, p->st);
+    if (!rc) rc = fetch(ih, p->ifhist, (size_t)S * nih, p->st);
+    if (!rc && p->misfit) rc = fetch(mk, p->mfkey, (size_t)S * p->Gmax, p->st);
+    if (!rc && p->misfit) rc = fetch(mr, p->mfrow, (size_t)S * p->Gmax, p->st);
+    if (!rc) rc = fetch(sum, p->red, (size_t)cols, p->st);
+    if (!rc) rc = fetch(kmn, p->kmin, (size_t)cols, p->st);
+    if (!rc) rc = fetch(kmx, p->kmax, (size_t)cols, p->st);
+    if (rc) return rc;
+    STATS_HIP(hipStreamSynchronize(p->st));
+    for (int z = 0; z < S; z++)
+        if (cnt[2 * z + 1])
+            return bh::fail_arg_((std::string("bh_posterior_sets_scan: ") + bh::scan_fault(cnt[2 * z], cnt[2 * z + 1])).c_str());
+    std::vector<double> mu((size_t)cols);
+    const double nan = std::nan("");
+    for (int z = 0; z < S; z++) {
+        const u64 included = cnt[2 * z];
+        p->total[z] = included;
+        p->status[z] = included == 0 ? BH_POSTERIOR_SET_EMPTY
+                       : included > (1ull << 53) ? BH_POSTERIOR_SET_OVERFLOW : BH_POSTERIOR_SET_OK;
+        status[z] = p->status[z];
+        const bool live = p->status[z] == BH_POSTERIOR_SET_OK;
+        for (int c = 0; c < D; c++) {
+            const size_t i = (size_t)z * D + c;
+            mu[i] = live ? sum[i] / (double)included : nan;
+            if (vmin) vmin[i] = live ? bh::post_unkey64(kmn[i]) : nan;
+            if (vmax) vmax[i] = live ? bh::post_unkey64(kmx[i]) : nan;
+            if (mean) mean[i] = mu[i];
+        }
+        if (total) total[z] = (long long)included;
+        if (nlayers)
+            for (int i = 0; i < nl1; i++) nlayers[(size_t)z * nl1 + i] = (long long)nl[(size_t)z * nl1 + i];
+        if (ifhist)
+            for (int i = 0; i < nih; i++) ifhist[(size_t)z * nih + i] = (long long)ih[(size_t)z * nih + i];
+        if (argmin) {
+            long long best = -1;
+            u64 bk = 0;
+            const int G = p->G(z);
+            for (int g = 0; p->misfit && g < G; g++) {
+                const u64 k = mk[(size_t)z * p->Gmax + g];
+                const long long r = mr[(size_t)z * p->Gmax + g];
+                if (r >= 0 && (best < 0 || k < bk || (k == bk && r < best))) { best = r; bk = k; }
+            }
+            argmin[z] = best;
+        }
+    }
+    STATS_HIP(hipMemcpyAsync(p->dmean, mu.data(), sizeof(double) * cols, hipMemcpyHostToDevice, p->st));
+    STATS_HIP(hipStreamSynchronize(p->st));
+    p->scanned = 1;
+    return BH_OK;
+}
+
+int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const int *vedge_off, const int *dbin,
+                             int ndbins, long long *hist, double *stdev, double *median)
+{
+    if (!p) return bh::fail_arg_("post is NULL");
+    if (!p->scanned) return bh::fail_arg_("bh_posterior_sets_finish before bh_posterior_sets_scan");
+    const int D = p->D, S = p->nsets;
+    const bool want_hist = vedges != nullptr;
+    if (want_hist && (!vedge_off || vedge_off[0] != 0 || !dbin || ndbins < 1 || !hist))
+        return bh::fail_arg_("bh_posterior_sets_finish: Vs edges need their offsets (from 0), depth bins and histogram");
+    const int tile_fits = want_hist ? tiles_fit(dbin, D, ndbins) : 1;
+    if (tile_fits < 0) return bh::fail_arg_("bh_posterior_sets_finish: depth bin out of range");
+    std::vector<int> sflags(S, 0);
+    std::vector<u64> hoff((size_t)S + 1, 0);
+    for (int z = 0; z < S; z++) {
+        bool live = p->status[z] == BH_POSTERIOR_SET_OK;
+        if (want_hist) {
+            const int nve = vedge_off[z + 1] - vedge_off[z];
+            if (nve < 0) return bh::fail_arg_("bh_posterior_sets_finish: vedge_off must be ascending");
+            if (nve == 0) live = false;          // the caller leaves the set out
+            if (live && (nve < 2 || !bh::ascending(vedges + vedge_off[z], nve)))
+                return bh::fail_arg_("bh_posterior_sets_finish: a set's Vs edges must be ascending, two at least");
+            hoff[z + 1] = hoff[z] + (u64)ndbins * (u64)(nve > 1 ? nve - 1 : 0);
+            if (live && (!tile_fits || (size_t)kTile * (nve - 1) * sizeof(u64) > (size_t)kHistLdsBytes))
+                sflags[z] |= S_HIST_GLOBAL;
+        }
+        if (!live) sflags[z] |= S_SKIP;
+    }
+    bh::CallBufs tmp(p->st);
+    PostArgs a = base_args(p);
+    a.mean = p->dmean;
+    SetArgs s;
+    std::memset(&s, 0, sizeof(s));
+    s.start = p->dstart;
+    s.Gmax = p->Gmax;
+    s.sflags = p->sflags;
+    STATS_HIP(hipMemcpyAsync(p->sflags, sflags.data(), sizeof(int) * S, hipMemcpyHostToDevice, p->st));
+    if (want_hist) {
+        double *dve = nullptr;
+        int *ddb = nullptr, *dvo = nullptr;
+        u64 *dho = nullptr;
+        const size_t nve_all = (size_t)vedge_off[S], nhist = (size_t)hoff[S];
+        STATS_HIP(tmp.alloc(dve, nve_all ? nve_all : 1));
+        STATS_HIP(tmp.alloc(ddb, D));
+        STATS_HIP(tmp.alloc(dvo, (size_t)S + 1));
+        STATS_HIP(tmp.alloc(dho, (size_t)S + 1));
+        STATS_HIP(tmp.alloc(a.hist, nhist ? nhist : 1));
+        if (nve_all) STATS_HIP(hipMemcpyAsync(dve, vedges, sizeof(double) * nve_all, hipMemcpyHostToDevice, p->st));
+        STATS_HIP(hipMemcpyAsync(ddb, dbin, sizeof(int) * D, hipMemcpyHostToDevice, p->st));
+        STATS_HIP(hipMemcpyAsync(dvo, vedge_off, sizeof(int) * ((size_t)S + 1), hipMemcpyHostToDevice, p->st));
+        STATS_HIP(hipMemcpyAsync(dho, hoff.data(), sizeof(u64) * ((size_t)S + 1), hipMemcpyHostToDevice, p->st));
+        if (nhist) STATS_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * nhist, p->st));
+        a.flags |= F_HIST;
+        a.vedges = dve;
+        a.dbin = ddb;
+        a.ndb = ndbins;
+        s.vedge_off = dvo;
+        s.hist_off = dho;
+    }
+    if (median) a.flags |= F_RADIX;
+    if (stdev) a.flags |= F_SQ;
+    const int first_flags = a.flags;
+    // LDS: radix digits first, then the histogram tile
+    a.off_radix = 0;
+    a.off_hist = median ? kTile * 2 * 256 : 0;
+    const double nan = std::nan("");
+    for (int first = 0; first < S; first += p->chunk) {
+        const int nc = S - first < p->chunk ? S - first : p->chunk;
+        s.first = first;
+        int tile = 0;                  // the widest LDS histogram tile of the chunk
+        for (int z = first; want_hist && z < first + nc; z++)
+            if (!(sflags[z] & (S_SKIP | S_HIST_GLOBAL))) {
+                const int t = kTile * (vedge_off[z + 1] - vedge_off[z] - 1);
+                tile = t > tile ? t : tile;
+            }
+        // the median: each set's two middle order statistics (0-based), at most two groups a column
+        std::vector<uint64_t> ranks;
+        if (median) {
+            ranks.resize(2 * (size_t)nc * D);
+            for (int zl = 0; zl < nc; zl++) {
+                const u64 t = (sflags[first + zl] & S_SKIP) ? 0 : p->total[first + zl];
+                for (int c = 0; c < D; c++) {
+                    ranks[(size_t)zl * D + c] = t ? (t - 1) / 2 : 0;
+                    ranks[(size_t)(nc + zl) * D + c] = t / 2;
+                }
+            }
+        }
+        bh::CallBufs seltmp(p->st);
+        bh::DeviceSelect sel(nc * D, median ? 2 : 0, p->fp64 ? 64 : 32, ranks.data(), bh::RadixSelect::PerColumn());
+        if (median) {
+            int rc = sel.alloc(seltmp);
+            if (rc) return rc;
+            a.gbase = sel.dgbase;
+            a.ngroups = sel.dngroups;
+            a.gpfx = sel.dgpfx;
+            a.digits = sel.ddigits;
+        }
+        a.flags = first_flags;
+        size_t lds = sizeof(u64) * (size_t)(a.off_hist + tile);
+        for (bool pass1 = true; pass1 || (median && !sel.done()); pass1 = false) {
+            int rc = median ? sel.begin_pass(p->st) : BH_OK;
+            a.shift = median ? sel.shift : 0;
+            if (!rc) rc = run<MODE_FINISH>(p, a, s, nc, lds);
+            if (!rc && pass1 && stdev) rc = reduce_chunk(p, first, nc);
+            if (rc) return rc;
+            a.flags &= ~(F_SQ | F_HIST | F_HIST_GLOBAL);   // later passes: digits only
+            lds = sizeof(u64) * (size_t)(kTile * 2 * 256);
+            if (!median) break;
+            rc = sel.end_pass(p->st);
+            if (rc) return rc;
+        }
+        if (median)
+            for (int zl = 0; zl < nc; zl++)
+                for (int c = 0; c < D; c++)
+                    median[(size_t)(first + zl) * D + c] =
+                        (sflags[first + zl] & S_SKIP) ? nan : median_of(sel, p->fp64, zl * D + c);
+    }
+    if (stdev) {
+        std::vector<double> sq;
+        int rc = fetch(sq, p->red, (size_t)S * D, p->st);
+        if (rc) return rc;
+        STATS_HIP(hipStreamSynchronize(p->st));
+        for (int z = 0; z < S; z++)
+            for (int c = 0; c < D; c++) {
+                const size_t i = (size_t)z * D + c;
+                stdev[i] = (sflags[z] & S_SKIP) ? nan : std::sqrt(sq[i] / (double)p->total[z]);
+            }
+    }
+    if (want_hist && hoff[S]) return bh::read_hist(a.hist, (size_t)hoff[S], hist, p->st);
+    return BH_OK;
+}
+
+}  // extern "C"

@@ -53,8 +53,8 @@ BH_HD int post_bin(const double *edges, int ne, double v)
 }
 
 // Host side of the exact weighted order statistics: an 8-bit radix select over the keys of ncols columns,
-// nranks 0-based ranks (the same in every column), most significant digit first.  Per (rank, column) it
-// holds the key prefix found so far and the rank left among the keys with that prefix.  A pass is
+// nranks 0-based ranks (the same in every column, or one list per column), most significant digit first.  Per
+// (rank, column) it holds the key prefix found so far and the rank left among the keys with that prefix.  A pass is
 //   plan()      the distinct prefixes of each column's ranks ("groups", in order of first occurrence by rank):
 //               group t of column c is slot gbase[c] + t, its prefix gpfx[slot]
 //   (device)    digits[slot][256]: the weight of the column's keys with key >> (shift + 8) == gpfx[slot]
@@ -76,6 +76,13 @@ struct RadixSelect {
     {
         for (int i = 0; i < nranks; i++)
             for (int c = 0; c < ncols; c++) left[(size_t)i * ncols + c] = ranks[i];
+    }
+    // ranks of its own for every column: ranks[nranks][ncols] (columns of sets with different weight totals)
+    struct PerColumn {};
+    RadixSelect(int ncols_, int nranks_, int keybits, const uint64_t *ranks, PerColumn)
+        : RadixSelect(ncols_, nranks_, keybits, ranks)
+    {
+        for (size_t i = 0; i < left.size(); i++) left[i] = ranks[i];
     }
     bool done() const { return shift < 0; }
     void plan()

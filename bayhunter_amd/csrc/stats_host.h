@@ -44,6 +44,13 @@ public:
     }
 };
 
+// a call's buffers whose kernels may still be queued when the call returns early: the stream is drained before they go
+struct CallBufs : DevBufs {
+    hipStream_t st;
+    explicit CallBufs(hipStream_t s) : st(s) {}
+    ~CallBufs() { (void)hipStreamSynchronize(st); }
+};
+
 static __global__ void stats_fill_kernel(u64 *p, int n, u64 v)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,6 +119,14 @@ struct DeviceSelect : RadixSelect {
     }
 };
 
+// what is wrong with a scan's counts, in the words every entry point reports it (NULL: nothing)
+inline const char *scan_fault(u64 included, u64 negative)
+{
+    return negative ? "negative weight"
+           : included == 0 ? "empty selection (no included row with a positive weight)"
+           : included > (1ull << 53) ? "weight total above 2^53" : nullptr;
+}
+
 // The part of a handle both reductions share: n columns, G blocks along the rows (a function of the row count
 // only, so that the slab order is fixed), and what a successful scan leaves for the finish.
 struct ColumnStats {
@@ -156,9 +171,7 @@ struct ColumnStats {
     int end_scan(const char *who, u64 included, u64 negative, const std::vector<double> &sum, double *vmin,
                  double *vmax, double *mean)
     {
-        const char *bad = negative ? "negative weight"
-                          : included == 0 ? "empty selection (no included row with a positive weight)"
-                          : included > (1ull << 53) ? "weight total above 2^53" : nullptr;
+        const char *bad = scan_fault(included, negative);
         if (bad) return bh::fail_arg_((std::string(who) + ": " + bad).c_str());
         total = included;
         std::vector<double> mu(n);

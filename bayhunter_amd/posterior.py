@@ -149,6 +149,50 @@ def _to_device(a, dtype, dev):
     return t if t.dim() < 2 or t.stride(1) == 1 else t.contiguous()
 
 
+def _grids(dep_int, depint):
+    """(depth grid of the single models, half-step grid and depth bin edges of the density) as summarize takes them."""
+    hist_dep_int = dep_int
+    if dep_int is None and depint is not None:
+        dep_int = hist_dep_int = models2d_dep_int((0, 100), depint)
+    dep_int = default_dep_int() if dep_int is None else np.asarray(dep_int, dtype=np.float64)
+    dep2, depbins = hist_grids(hist_dep_int)
+    if dep_int.size < 2:
+        raise ValueError("dep_int: at least two depths (they are the mode histogram's depth edges)")
+    return dep_int, dep2, depbins
+
+
+def mode_edges(vmin, vmax):
+    """Vs edges of get_singlemodels' mode histogram, from the per-depth min / max of a scan: int((max - min) / 0.025)
+    bins over linspace(min, max).  ValueError where the reference raises (no bin)."""
+    vmin, vmax = vmin.min(), vmax.max()
+    vsbins = int((vmax - vmin) / VS_INTERVAL)
+    if vsbins < 1:
+        raise ValueError("`bins[0]` must be positive, when an integer (all Vs values within 0.025 km/s)")
+    return np.linspace(vmin, vmax, vsbins + 1)
+
+
+def density_edges(vmin, vmax):
+    """Vs edges of _plot_bestmodels_hist, from the per-depth min / max of a scan on its half-step grid."""
+    vmin, vmax = vmin.min(), vmax.max()
+    return np.arange(vs_round(vmin) - 2 * VS_INTERVAL, vs_round(vmax) + 3 * VS_INTERVAL, VS_INTERVAL)
+
+
+def _result(s, dep_int, vedges, mhist, std, median, h2, vsb, depbins, minmisfit):
+    """summarize()'s dict from a scan `s` (total, vmin, vmax, mean, nlayers, ifhist), the finish on both grids and
+    the row of the least misfit (None: no misfits)."""
+    mean = s['mean']
+    vs_center = (vedges[:-1] + vedges[1:]) / 2.
+    dep_center = (dep_int[:-1] + dep_int[1:]) / 2.
+    single = dict(mean=(mean, dep_int), median=(median, dep_int),
+                  minmax=(np.array((s['vmin'], s['vmax'])), dep_int),
+                  stdminmax=(np.array((mean - std, mean + std)), dep_int),
+                  mode=(vs_center[np.argmax(mhist, axis=1)], dep_center))
+    if minmisfit is not None:
+        single['minmisfit'] = stepmodel(minmisfit)
+    return dict(singlemodels=single, hist2d=(h2.T.copy(), vsb, depbins), interfaces=(s['ifhist'], depbins),
+                nlayers=s['nlayers'], nmodels=s['total'])
+
+
 def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, device=None):
     """Posterior statistics of `models` ([rows, 2*maxlayers], reference layout, float32 or float64; numpy or
     a torch tensor) with integer `weights` (>= 0, default 1 each).
@@ -177,41 +221,163 @@ def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, dev
     mf = None if misfits is None else _to_device(misfits, torch.float64, dev)
     if w is not None and w.numel() != rows.shape[0] or mf is not None and mf.numel() != rows.shape[0]:
         raise ValueError("one weight and one misfit per row")
-    hist_dep_int = dep_int
-    if dep_int is None and depint is not None:
-        dep_int = hist_dep_int = models2d_dep_int((0, 100), depint)
-    dep_int = default_dep_int() if dep_int is None else np.asarray(dep_int, dtype=np.float64)
-    dep2, depbins = hist_grids(hist_dep_int)
-    if dep_int.size < 2:
-        raise ValueError("dep_int: at least two depths (they are the mode histogram's depth edges)")
+    dep_int, dep2, depbins = _grids(dep_int, depint)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         with _Grid(rows, w, mf, dep_int, depbins, stream) as ga:
             s = ga.scan()
-            # (5) mode: int((max - min) / 0.025) Vs bins over linspace(min, max), depth edges dep_int
-            vmin, vmax = s['vmin'].min(), s['vmax'].max()
-            vsbins = int((vmax - vmin) / VS_INTERVAL)
-            if vsbins < 1:
-                raise ValueError("`bins[0]` must be positive, when an integer (all Vs values within 0.025 km/s)")
-            vedges = np.linspace(vmin, vmax, vsbins + 1)
+            vedges = mode_edges(s['vmin'], s['vmax'])
             mhist, std, median = ga.finish(vedges, bin_index(dep_int, dep_int), dep_int.size - 1, True)
         # the density of _plot_bestmodels_hist on its half-step grid
         with _Grid(rows, w, None, dep2, None, stream) as gb:
             s2 = gb.scan()
-            vmin2, vmax2 = s2['vmin'].min(), s2['vmax'].max()
-            vsb = np.arange(vs_round(vmin2) - 2 * VS_INTERVAL, vs_round(vmax2) + 3 * VS_INTERVAL, VS_INTERVAL)
+            vsb = density_edges(s2['vmin'], s2['vmax'])
             h2, _, _ = gb.finish(vsb, bin_index(dep2, depbins), depbins.size - 1, False)
-    mean = s['mean']
-    vs_center = (vedges[:-1] + vedges[1:]) / 2.
-    dep_center = (dep_int[:-1] + dep_int[1:]) / 2.
-    single = dict(mean=(mean, dep_int), median=(median, dep_int),
-                  minmax=(np.array((s['vmin'], s['vmax'])), dep_int),
-                  stdminmax=(np.array((mean - std, mean + std)), dep_int),
-                  mode=(vs_center[np.argmax(mhist, axis=1)], dep_center))
-    if mf is not None:
-        single['minmisfit'] = stepmodel(rows[s['argmin']].cpu().numpy())
-    return dict(singlemodels=single, hist2d=(h2.T.copy(), vsb, depbins), interfaces=(s['ifhist'], depbins),
-                nlayers=s['nlayers'], nmodels=s['total'])
+    minmisfit = None if mf is None else rows[s['argmin']].cpu().numpy()
+    return _result(s, dep_int, vedges, mhist, std, median, h2, vsb, depbins, minmisfit)
+
+
+# ---- many sets of rows in one pass ------------------------------------------------------------------------
+
+class _Sets(_Handle):
+    """One bh_posterior_sets handle: the rows, in contiguous sets, on one depth grid."""
+
+    def __init__(self, rows, weights, misfits, set_start, dep, ifedges, stream, chunk_bytes=None):
+        self.dep = np.ascontiguousarray(dep, dtype=np.float64)
+        self.ifedges = None if ifedges is None else np.ascontiguousarray(ifedges, dtype=np.float64)
+        self.set_start = np.ascontiguousarray(set_start, dtype=np.int64)
+        self.width, self.nsets = rows.shape[1], self.set_start.size - 1
+        nif = 0 if self.ifedges is None else self.ifedges.size
+        _Handle.__init__(
+            self, 'posterior_sets', rows.data_ptr(), int(rows.dtype.itemsize == 8), rows.shape[0], rows.stride(0),
+            self.width, None if weights is None else weights.data_ptr(),
+            None if misfits is None else misfits.data_ptr(), self.set_start.ctypes.data, self.nsets,
+            self.dep.ctypes.data, self.dep.size, None if not nif else self.ifedges.ctypes.data, nif, stream)
+        if chunk_bytes is not None:
+            _lib.check(self.lib.bh_posterior_sets_set_chunk_bytes(self.h, int(chunk_bytes)))
+
+    def scan(self):
+        """-> dict of arrays with one row per set, and 'status' (0: the set has statistics)."""
+        S, D = self.nsets, self.dep.size
+        total, argmin = np.zeros(S, dtype=np.int64), np.full(S, -1, dtype=np.int64)
+        status = np.zeros(S, dtype=np.int32)
+        vmin, vmax, mean = np.zeros((S, D)), np.zeros((S, D)), np.zeros((S, D))
+        nlay = np.zeros((S, self.width // 2 + 1), dtype=np.int64)
+        ifh = np.zeros((S, max(0, (0 if self.ifedges is None else self.ifedges.size) - 1)), dtype=np.int64)
+        _lib.check(self.lib.bh_posterior_sets_scan(self.h, total.ctypes.data, vmin.ctypes.data, vmax.ctypes.data,
+                                                   mean.ctypes.data, nlay.ctypes.data,
+                                                   ifh.ctypes.data if ifh.size else None, argmin.ctypes.data,
+                                                   status.ctypes.data))
+        return dict(total=total, vmin=vmin, vmax=vmax, mean=mean, nlayers=nlay, ifhist=ifh, argmin=argmin,
+                    status=status)
+
+    def finish(self, vedges, dbin, ndbins, stats):
+        """vedges: per set its Vs edges, or None to leave the set out -> (per set hist[ndbins, edges - 1] or None,
+        std [sets, D], median [sets, D]) -- the last two None without `stats`, NaN rows for sets left out."""
+        S, D = self.nsets, self.dep.size
+        nve = np.array([0 if e is None else e.size for e in vedges], dtype=np.int64)
+        off = np.concatenate(([0], np.cumsum(nve))).astype(np.int32)
+        allv = np.ascontiguousarray(np.concatenate([e for e in vedges if e is not None] + [np.zeros(1)]))
+        hoff = np.concatenate(([0], np.cumsum(ndbins * np.maximum(nve - 1, 0))))
+        dbin = np.ascontiguousarray(dbin, dtype=np.int32)
+        hist = np.zeros(max(1, hoff[-1]), dtype=np.int64)
+        std, median = (np.zeros((S, D)), np.zeros((S, D))) if stats else (None, None)
+        _lib.check(self.lib.bh_posterior_sets_finish(self.h, allv.ctypes.data, off.ctypes.data, dbin.ctypes.data, ndbins,
+                                                     hist.ctypes.data, None if std is None else std.ctypes.data,
+                                                     None if median is None else median.ctypes.data))
+        hists = [None if vedges[z] is None else hist[hoff[z]:hoff[z + 1]].reshape(ndbins, nve[z] - 1) for z in range(S)]
+        return hists, std, median
+
+
+class SetResults(list):
+    """summarize_sets' list: entry s is summarize()'s dict of set s, or None for a set in `failed`
+    ({set index: message}).  `std[s]` is the set's standard deviation per depth (summarize reports mean -+ std)."""
+
+    def __init__(self, results, failed, dep_int, std):
+        list.__init__(self, results)
+        self.failed, self.dep, self.std = failed, dep_int, std
+
+    def section(self):
+        """The single models stacked: dict(dep [D], mean / median / std / vmin / vmax [sets, D], mode [sets, D - 1]),
+        a failed set a row of NaN."""
+        S, D = len(self), self.dep.size
+        out = dict(dep=self.dep)
+        for k in ('mean', 'median', 'std', 'vmin', 'vmax'):
+            out[k] = np.full((S, D), np.nan)
+        out['mode'] = np.full((S, D - 1), np.nan)
+        for z, res in enumerate(self):
+            if res is None:
+                continue
+            sm = res['singlemodels']
+            out['mean'][z], out['median'][z], out['std'][z] = sm['mean'][0], sm['median'][0], self.std[z]
+            out['vmin'][z], out['vmax'][z] = sm['minmax'][0]
+            out['mode'][z] = sm['mode'][0]
+        return out
+
+
+def summarize_sets(models, set_start, weights=None, dep_int=None, misfits=None, depint=None, device=None, strict=True,
+                   chunk_bytes=None):
+    """summarize() of every set of rows in one pass: set s is models[set_start[s]:set_start[s + 1]] (set_start
+    [sets + 1], ascending from 0 to the number of rows; a set may be empty), with its weights and misfits.
+
+    -> SetResults: a list with summarize()'s dict per set, every field bit for bit what summarize returns for the
+    set's rows alone.  A set for which summarize raises (empty selection; all Vs within 0.025 km/s) raises here
+    too, as a ValueError naming the first such set -- or, with strict=False, has the entry None and its message in
+    the list's `failed` {set index: message}.  A negative weight fails the call.
+
+    chunk_bytes   bound on the device memory of the median's digit table (default 64 MiB): the sets are processed
+                  in chunks that keep to it, and no result depends on it."""
+    import torch
+    dev = _torch_device(device)
+    if not isinstance(models, torch.Tensor):
+        models = np.asarray(models)
+    if models.ndim != 2:
+        raise ValueError("models: [rows, 2*maxlayers]")
+    set_start = np.ascontiguousarray(set_start, dtype=np.int64)
+    S = set_start.size - 1
+    if set_start.ndim != 1 or S < 1 or set_start[0] != 0 or set_start[-1] != models.shape[0] or np.any(np.diff(set_start) < 0):
+        raise ValueError("set_start: [sets + 1], ascending from 0 to the number of rows")
+    fdtype = torch.float32 if str(models.dtype).endswith('float32') else torch.float64
+    rows = _to_device(models, fdtype, dev)
+    w = None if weights is None else _to_device(weights, torch.int32, dev)
+    mf = None if misfits is None else _to_device(misfits, torch.float64, dev)
+    if w is not None and w.numel() != rows.shape[0] or mf is not None and mf.numel() != rows.shape[0]:
+        raise ValueError("one weight and one misfit per row")
+    dep_int, dep2, depbins = _grids(dep_int, depint)
+    failed, results, std = {}, [None] * S, None
+    if rows.shape[0] == 0:
+        failed = {z: "empty selection: no models" for z in range(S)}
+    else:
+        lib = _lib.load()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            with _Sets(rows, w, mf, set_start, dep_int, depbins, stream, chunk_bytes) as ga:
+                s = ga.scan()
+                vedges = [None] * S
+                for z in range(S):
+                    if s['status'][z]:
+                        failed[z] = lib.bh_posterior_sets_status_text(int(s['status'][z])).decode()
+                        continue
+                    try:
+                        vedges[z] = mode_edges(s['vmin'][z], s['vmax'][z])
+                    except ValueError as e:
+                        failed[z] = str(e)
+                mhist, std, median = ga.finish(vedges, bin_index(dep_int, dep_int), dep_int.size - 1, True)
+            with _Sets(rows, w, None, set_start, dep2, None, stream, chunk_bytes) as gb:
+                s2 = gb.scan()
+                vsb = [None if z in failed else density_edges(s2['vmin'][z], s2['vmax'][z]) for z in range(S)]
+                h2, _, _ = gb.finish(vsb, bin_index(dep2, depbins), depbins.size - 1, False)
+        live = [z for z in range(S) if z not in failed]
+        best = None if mf is None or not live else rows[torch.from_numpy(s['argmin'][live]).to(dev)].cpu().numpy()
+        for i, z in enumerate(live):
+            sz = {k: s[k][z] for k in ('vmin', 'vmax', 'mean', 'nlayers', 'ifhist')}
+            sz['total'] = int(s['total'][z])
+            results[z] = _result(sz, dep_int, vedges[z], mhist[z], std[z], median[z], h2[z], vsb[z], depbins,
+                                 None if best is None else best[i])
+    if failed and strict:
+        z = min(failed)
+        raise ValueError("set %d: %s" % (z, failed[z]))
+    return SetResults(results, failed, dep_int, std)
 
 
 # ---- the chain pool's own sample block ------------------------------------------------------------------
@@ -245,12 +411,12 @@ def pool_selection(pool, selection='weighted'):
     return ci, ri, w
 
 
-def pool_outliers(pool, dev=0.05):
-    """PlotFromStorage.get_outliers (Plotting.py:113-154) on the likes save() writes: the median of each
-    chain's thinned main-phase likes against the best chain's -> global chain indices (sorted)."""
+def chain_like_medians(pool):
+    """The median of each chain's thinned main-phase likes, as np.median of the float32 values save() writes gives it
+    -> (chains (local indices of those with main-phase rows, ascending), medians float64)."""
     ci, ri, cnt = pool_selection(pool, 'saved')
     if ci.size == 0:
-        return np.zeros(0, dtype=np.int64)
+        return np.zeros(0, dtype=np.int64), np.zeros(0)
     likes = pool.likes[ci, ri]
     order = np.lexsort((likes, ci))
     cs, ls = cnt[order], likes[order]
@@ -261,14 +427,25 @@ def pool_outliers(pool, dev=0.05):
     pick = lambda r: ls[np.searchsorted(cum, off + r, side='right')]
     lo, hi = pick((tot - 1) // 2), pick(tot // 2)
     # np.median of float32: the middle value, or the float32 mean of the two middle ones
-    med = np.where(tot % 2 == 1, lo, (lo + hi) / np.float32(2)).astype(np.float32).astype(np.float64)
+    return chains, np.where(tot % 2 == 1, lo, (lo + hi) / np.float32(2)).astype(np.float32).astype(np.float64)
+
+
+_NO_BEST_CHAIN = "best chain median likelihood is 0: outliers are undefined (Plotting.py:136-140)"
+
+
+def pool_outliers(pool, dev=0.05):
+    """PlotFromStorage.get_outliers (Plotting.py:113-154) on the likes save() writes: the median of each
+    chain's thinned main-phase likes against the best chain's -> global chain indices (sorted)."""
+    chains, med = chain_like_medians(pool)
+    if chains.size == 0:
+        return np.zeros(0, dtype=np.int64)
     maxlike = np.max(med)
     if maxlike > 0:
         scores = med / maxlike
     elif maxlike < 0:
         scores = maxlike / med
     else:
-        raise ValueError("best chain median likelihood is 0: outliers are undefined (Plotting.py:136-140)")
+        raise ValueError(_NO_BEST_CHAIN)
     return (chains[(1 - scores) > dev] + pool.first).astype(np.int64)
 
 
@@ -295,3 +472,75 @@ def pool_posterior(pool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True
     res = summarize(pool.models[ci, ri], w.astype(np.int32), dep_int=dep_int, device=device)
     res['chains'] = np.unique(ci) + pool.first
     return res
+
+
+# ---- every station of a station pool ----------------------------------------------------------------------
+
+def station_rows(pool, chains_per_station, selection='weighted', dev=0.05, exclude_outliers=True):
+    """pool_rows of every station of a pool whose chains come in runs of `chains_per_station` per station, without
+    a loop over stations: the selection is pool_selection on all chains, the outlier chains are found per station
+    from chain_like_medians on all chains (each chain's median against the best of its own station).
+    -> (ci, ri, w, set_start [stations + 1], failed {station index: message}): station s owns the rows
+    set_start[s]:set_start[s + 1], there ci - s * chains_per_station, ri, w are pool_rows of the station's view.
+    A station in `failed` (its best chain's median likelihood is 0, or a weight does not fit the device's int32: what
+    pool_rows raises for) has no rows; so has one without main-phase rows."""
+    c = int(chains_per_station)
+    S = pool.nchains // c
+    ci, ri, w = pool_selection(pool, selection)
+    failed = {}
+    if exclude_outliers and ci.size:
+        chains, med = chain_like_medians(pool)
+        st = chains // c
+        best = np.full(S, -np.inf)
+        np.maximum.at(best, st, med)
+        best = best[st]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            scores = np.where(best > 0, med / best, best / med)
+        for s in np.unique(st[best == 0]):
+            failed[int(s)] = _NO_BEST_CHAIN
+        out = chains[(best != 0) & ((1 - scores) > dev)]
+        keep = ~np.isin(ci, out) & ~np.isin(ci // c, np.fromiter(failed, dtype=np.int64, count=len(failed)))
+        ci, ri, w = ci[keep], ri[keep], w[keep]
+    big = w > np.iinfo(np.int32).max
+    if big.any():                                          # pool_rows' refusal, for the stations it would refuse
+        for s in np.unique(ci[big] // c):
+            failed.setdefault(int(s), "a weight above 2^31 - 1")
+        keep = ~np.isin(ci // c, np.unique(ci[big] // c))
+        ci, ri, w = ci[keep], ri[keep], w[keep]
+    return ci, ri, w, np.searchsorted(ci // c, np.arange(S + 1)).astype(np.int64), failed
+
+
+class StationPosterior(object):
+    """StationPool.posterior's result.
+
+    stations   {station name: the dict pool.station(name).posterior(...) returns}, failed stations left out
+    failed     {station name: message}
+    dep        the depth grid [D]
+    mean, median, std, vmin, vmax [nstations, D], mode [nstations, D - 1]   the single models of all stations, in
+               the pool's station order: the section (or, with the stations' coordinates, the volume); a failed
+               station is a row of NaN"""
+
+    def __init__(self, names, results, failed):
+        self.names = list(names)
+        self.stations = {n: r for n, r in zip(names, results) if r is not None}
+        self.failed = {names[z]: msg for z, msg in failed.items()}
+        for k, v in results.section().items():
+            setattr(self, k, v)
+
+
+def stations_posterior(spool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None,
+                       strict=True):
+    """StationPool.posterior: summarize_sets() over every station's main-phase rows (see StationPool.posterior)."""
+    pool, c = spool.pool, spool.chains_per_station
+    ci, ri, w, set_start, failed = station_rows(pool, c, selection, dev, exclude_outliers)
+    if dep_int is None:
+        dep_int = models2d_dep_int(pool.priors['z'], depint)
+    res = summarize_sets(pool.models[ci, ri], set_start, w.astype(np.int32), dep_int=dep_int, device=device, strict=False)
+    res.failed.update(failed)
+    if res.failed and strict:
+        z = min(res.failed)
+        raise ValueError("station %r: %s" % (spool.names[z], res.failed[z]))
+    for z, r in enumerate(res):
+        if r is not None:
+            r['chains'] = np.unique(ci[set_start[z]:set_start[z + 1]]) - z * c
+    return StationPosterior(spool.names, res, res.failed)

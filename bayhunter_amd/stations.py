@@ -11,6 +11,7 @@ it is in, so a station's chains are bit for bit the chains of a `ChainPool` of t
     pool = StationPool({'ST1': joint1, 'ST2': joint2, ...}, initparams, priors, chains_per_station=8,
                        random_seeds=[11, 12, ...]).run()
     pool.station('ST2').posterior()          # the interface of a ChainPool, restricted to the station's chains
+    pool.posterior().mean                    # every station's posterior in one pass: [nstations, depths]
     pool.save()                              # one directory per station, each what a single-station pool writes
 
 One plugin parameter may differ between stations when the pool is told so: the ray parameter `p` of a receiver
@@ -345,6 +346,18 @@ class StationPool(object):
         if not 0 <= s < self.nstations:
             raise IndexError("station %d of %d" % (s, self.nstations))
         return StationView(self, int(s))
+
+    def posterior(self, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None,
+                  strict=True):
+        """The velocity-depth posterior of every station in one pass over the pool's rows (posterior.summarize_sets):
+        per station, selection and outlier chains as station(s).posterior(...) takes them, and the very dict it
+        returns ('chains' numbered within the station).  -> posterior.StationPosterior: `stations[name]` those
+        dicts, `failed` {name: message} for stations without a posterior (no main-phase rows left, all Vs within
+        0.025 km/s, best chain's median likelihood 0), and the stacked single models `dep`, `mean / median / std /
+        vmin / vmax [nstations, D]`, `mode [nstations, D - 1]` with NaN rows for failed stations.  strict=True: a
+        failed station is a ValueError naming the first one."""
+        from .posterior import stations_posterior
+        return stations_posterior(self, dep_int, depint, dev, exclude_outliers, selection, device, strict)
 
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone

@@ -524,6 +524,51 @@ int  bh_posterior_finish(bh_posterior *post, const double *vedges, int nvedges, 
                          long long *hist, double *stdev, double *median);
 void bh_posterior_destroy(bh_posterior *post);
 
+/* ---- the same statistics for many sets of rows in one pass (the stations of a network) ----- */
+/* The rows come in contiguous segments, one per set: set s is rows set_start[s] .. set_start[s + 1].  Every number
+ * reported for a set is bit for bit what a bh_posterior handle over that set's rows alone reports (a block of the
+ * kernel belongs to one set and runs as the block it would be there; the per-block partials of a set are reduced in
+ * the same order), from one scan launch, one finish launch and one launch per further radix pass for all sets.
+ *
+ * rows, weights, misfits, dep, ifedges, stream    as for bh_posterior_create
+ * set_start  HOST [nsets + 1], ascending, set_start[0] = 0, set_start[nsets] = nrows; 1 <= nsets <= 65535.  A set may
+ *            be empty
+ *
+ *   bh_posterior_sets_create   BH_ERR_ARG for what bh_posterior_create refuses and for a bad set_start / nsets
+ *   bh_posterior_sets_scan     per set: weight total [nsets], min / max / mean [nsets][ndep], nuclei counts
+ *                              [nsets][width/2 + 1], interface histogram [nsets][nifedges - 1], the first argmin row
+ *                              of the misfits counted from the first row of `rows` (-1: none) [nsets], and
+ *                              status [nsets] (required): BH_POSTERIOR_SET_OK, or why the set has no statistics
+ *                              (bh_posterior_sets_status_text: the words bh_posterior_scan fails with).  Such a set
+ *                              has NaN min / max / mean and is left out by the finish; the call succeeds.  A negative
+ *                              weight anywhere fails the call
+ *   bh_posterior_sets_finish   after a scan.  With vedges: the Vs edges of all sets one after the other, set s owning
+ *                              vedges[vedge_off[s] .. vedge_off[s + 1]) (vedge_off[nsets + 1] from 0, ascending; two
+ *                              edges at least and ascending for every set of status 0; a set given NO edges is left
+ *                              out like a failed one), dbin [ndep] and ndbins as for bh_posterior_finish, and hist
+ *                              the sets' histograms one after the other, set s owning ndbins * (edges of s - 1)
+ *                              counters.  std and median [nsets][ndep] when not NULL; NaN for a set left out
+ *   bh_posterior_sets_set_chunk_bytes   the sets of a handle are processed in chunks (one after the other on the
+ *                              handle's stream, a set never split) so that the radix select's digit table of a chunk,
+ *                              2 * 256 * 8 B per (set, depth), stays under 64 MiB.  This sets the handle's own bound
+ *                              (<= 0: the default), before its first scan.  No result depends on it
+ * Every output is a HOST buffer; each call returns when its results are there. */
+#define BH_POSTERIOR_SET_OK       0
+#define BH_POSTERIOR_SET_EMPTY    1   /* no included row with a positive weight */
+#define BH_POSTERIOR_SET_OVERFLOW 2   /* weight total above 2^53 */
+typedef struct bh_posterior_sets bh_posterior_sets;
+int  bh_posterior_sets_create(const void *rows, int fp64, long long nrows, long long stride, int width,
+                              const int *weights, const double *misfits, const long long *set_start, int nsets,
+                              const double *dep, int ndep, const double *ifedges, int nifedges, void *stream,
+                              bh_posterior_sets **post);
+int  bh_posterior_sets_scan(bh_posterior_sets *post, long long *total, double *vmin, double *vmax, double *mean,
+                            long long *nlayers, long long *ifhist, long long *argmin, int *status);
+int  bh_posterior_sets_finish(bh_posterior_sets *post, const double *vedges, const int *vedge_off, const int *dbin,
+                              int ndbins, long long *hist, double *stdev, double *median);
+void bh_posterior_sets_destroy(bh_posterior_sets *post);
+const char *bh_posterior_sets_status_text(int status);
+int  bh_posterior_sets_set_chunk_bytes(bh_posterior_sets *post, long long bytes);
+
 /* ---- posterior statistics of the modelled data -------------------------------------------- */
 /* The data half of looking at an inversion's result (PlotFromStorage.plot_bestdatafits / plot_rfcorr,
  * src/Plotting.py:1054-1150), over the whole posterior instead of one model per chain: per column of the

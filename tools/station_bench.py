@@ -15,6 +15,12 @@ vp/vs and noise, like tools/chain_bench.py).  For S stations of c chains each, t
 pool runs with per_station=('p',) (the per-row form of rf_kernel), the single pools each at their station's p, `onepool`
 at station 0's.
 
+--posterior: instead of the three ways to run, what reading the result costs.  One finished StationPool of S x c chains
+is summarised twice: by the loop over its station views (pool.station(s).posterior(), one pair of handles per station)
+and by StationPool.posterior() (one pass over all stations).  Each is warmed once, then timed --repeats times
+wall-clock around a device synchronisation; the two results are asserted equal, field by field and bit for bit,
+before a time is reported.  One JSON line per S x c.
+
 A warm-up pool of every mode runs first; then `--repeats` rounds, each round running every mode once (alternating,
 so that a drift of the box hits all modes alike).  One JSON line per (S, c, mode) with every repeat's seconds,
 their median / min / max and chain iterations per second from the median; appended to --out if given."""
@@ -29,7 +35,8 @@ import numpy as np
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('configs', nargs='*', default=['64x16', '256x16', '1024x16', '1024x4'])
+    ap.add_argument('configs', nargs='*', default=None,
+                    help='default 64x16 256x16 1024x16 1024x4 (with --posterior: 64x16 256x16 1024x16)')
     ap.add_argument('--modes', default='stations,onepool,singles')
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--sample', type=int, default=16)
@@ -37,9 +44,13 @@ def main():
     ap.add_argument('--root', default=None, help='tree whose bayhunter_amd is measured (default: this one)')
     ap.add_argument('--vary-p', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
                     help="stations with p spread evenly over [LO, HI] s/deg, pooled with per_station=('p',)")
+    ap.add_argument('--posterior', action='store_true',
+                    help='time StationPool.posterior() against the loop over station views on one finished pool')
     ap.add_argument('--tag', default=None)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if not args.configs:
+        args.configs = ['64x16', '256x16', '1024x16'] + ([] if args.posterior else ['1024x4'])
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     root = os.path.abspath(args.root) if args.root else here
     sys.path.insert(0, os.path.join(here, 'tests', 'scenarios'))
@@ -88,10 +99,69 @@ def main():
                 dt += time.perf_counter() - t0
         return dt, k
 
+    def same(a, b, path=''):
+        """every leaf of two result trees equal (NaN = NaN)"""
+        if isinstance(a, dict):
+            assert set(a) == set(b), path
+            for k in a:
+                same(a[k], b[k], path + '/' + str(k))
+        elif isinstance(a, (list, tuple)):
+            assert len(a) == len(b), path
+            for i, (x, y) in enumerate(zip(a, b)):
+                same(x, y, '%s[%d]' % (path, i))
+        else:
+            x, y = np.asarray(a), np.asarray(b)
+            assert np.array_equal(x, y, equal_nan=x.dtype.kind in 'fc'), path
+
+    def posterior_leg(S, c, iters, stations):
+        import torch
+        from bayhunter_amd.stations import StationPool
+        with StationPool(stations, params(iters), case['priors'], seeds=seeds_of(S, c), nmodels=iters + iters // 2 + 1) as pool:
+            pool.run()
+
+        def loop():
+            out, failed = {}, {}
+            for name in pool.names:
+                try:
+                    out[name] = pool.station(name).posterior()
+                except ValueError as e:
+                    failed[name] = str(e)
+            return out, failed
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = fn()
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, r
+
+        one = lambda: pool.posterior(strict=False)
+        (_, (want, wfailed)), (_, got) = timed(loop), timed(one)       # warm
+        assert sorted(got.failed) == sorted(wfailed) and list(got.stations) == list(want), (got.failed, wfailed)
+        same(got.stations, want)
+        secs = dict(loop=[], one_call=[])
+        for _ in range(args.repeats):
+            secs['loop'].append(timed(loop)[0])
+            secs['one_call'].append(timed(one)[0])
+        med = {k: float(np.median(v)) for k, v in secs.items()}
+        return dict(bench='station_posterior', tag=args.tag, stations=S, chains_per_station=c, chains=S * c,
+                    iterations=iters + iters // 2, models=int(sum(r['nmodels'] for r in want.values())),
+                    stations_failed=len(wfailed), equal=True, repeats=args.repeats,
+                    loop_s=[round(x, 4) for x in secs['loop']], one_call_s=[round(x, 4) for x in secs['one_call']],
+                    loop_median_s=round(med['loop'], 4), one_call_median_s=round(med['one_call'], 4),
+                    loop_ms_per_station=round(1e3 * med['loop'] / S, 3), speedup=round(med['loop'] / med['one_call'], 2))
+
     for cfg in args.configs:
         S, c = (int(v) for v in cfg.lower().split('x'))
         iters = args.iters or (120 if S * c <= 4096 else 60)
         stations = make_stations(data, S, yerr=True)
+        if args.posterior:
+            line = json.dumps(posterior_leg(S, c, iters, stations))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, 'a') as fh:
+                    fh.write(line + '\n')
+            continue
         if args.vary_p:
             for joint, p in zip(stations, np.linspace(args.vary_p[0], args.vary_p[1], S)):
                 joint.targets[1].moddata.plugin.set_modelparams(p=float(p))
