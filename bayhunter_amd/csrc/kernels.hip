@@ -189,8 +189,9 @@ __device__ __forceinline__ void swd_lane_prof(Lay &lay, Src &src, const SwdTarge
     nv.cycles = 0;
     unsigned long long td = 0, te = 0, tc = 0, n = 0, t0 = clock64(), t1;
     for (;;) {
-        swd_events(S, lay, src, tg, per, wss);
+        swd_events_pass(S, lay, src, tg, per, wss);
         t1 = clock64(); td += t1 - t0; t0 = t1;
+        if (S.ev != SWD_EV_NONE) continue;
         if (S.st == SWD_ST_DONE) break;
         const double wvno = S.omega / S.ceval;
         const double del = (tg.iwave == 1) ? swd_dltar1(lay, S.mmax, S.llw, wvno, S.omega)

@@ -434,40 +434,50 @@ BH_DEV bool swd_neville(NevRegs &n, int &m, bool nev2, double c1, double del1, d
 #if defined(BH_LANE_PROFILE)
     const unsigned long long lp_t0 = clock64();
 #endif
-    double ym1;                       // y(m+1)
-    if (nev2) {                       // x(m+1)=c3, y(m+1)=del3
-        ym1 = del3;
-        // (tables longer than three points are rare: the two outer tests let a wave skip them)
-        if (m <= 3) {
-            if (m == 1) { n.x2 = c3; n.y2 = del3; } else if (m == 2) { n.x3 = c3; n.y3 = del3; }
-            else { n.x4 = c3; n.y4 = del3; }
-        } else if (m <= 6) {
-            if (m == 4) { n.x5 = c3; n.y5 = del3; } else if (m == 5) { n.x6 = c3; n.y6 = del3; }
-            else { n.x7 = c3; n.y7 = del3; }
-        } else {
-            if (m == 7) { n.x8 = c3; n.y8 = del3; } else if (m == 8) { n.x9 = c3; n.y9 = del3; }
-            else if (m == 9) { n.x10 = c3; n.y10 = del3; } else { n.x11 = c3; n.y11 = del3; }
+    // Every entry is written by selects on the entry itself, never inside an arm that other entries pass by:
+    // a divergent arm that assigns some entries makes the compiler carry an old and a new copy of the whole
+    // table across the join.  Only tables longer than three points -- rare -- sit
+    // behind tests, which a wave skips.
+    const int mo = m;                                       // the append position: x(mo+1), y(mo+1)
+    const double ym1 = nev2 ? del3 : del2;                  // y(m+1)
+    n.x1 = nev2 ? n.x1 : c1;
+    n.y1 = nev2 ? n.y1 : del1;
+    n.x2 = nev2 ? (mo == 1 ? c3 : n.x2) : c2;
+    n.y2 = nev2 ? (mo == 1 ? del3 : n.y2) : del2;
+    n.x3 = (nev2 & (mo == 2)) ? c3 : n.x3;
+    n.y3 = (nev2 & (mo == 2)) ? del3 : n.y3;
+    n.x4 = (nev2 & (mo == 3)) ? c3 : n.x4;
+    n.y4 = (nev2 & (mo == 3)) ? del3 : n.y4;
+    if (nev2 & (mo >= 4)) {
+#define BH_NEV_PUT(J, XJ1, YJ1) n.XJ1 = (mo == J) ? c3 : n.XJ1; n.YJ1 = (mo == J) ? del3 : n.YJ1;
+        BH_NEV_PUT(4, x5, y5) BH_NEV_PUT(5, x6, y6) BH_NEV_PUT(6, x7, y7)
+        if (mo >= 7) {
+            BH_NEV_PUT(7, x8, y8) BH_NEV_PUT(8, x9, y9) BH_NEV_PUT(9, x10, y10)
+            n.x11 = (mo >= 10) ? c3 : n.x11; n.y11 = (mo >= 10) ? del3 : n.y11;
         }
-    } else {
-        n.x1 = c1; n.y1 = del1; n.x2 = c2; n.y2 = del2; m = 1;
-        ym1 = del2;
+#undef BH_NEV_PUT
     }
-    // j = m .. 1 (surfdisp96.f:649-654)
-    bool bad = false;
+    m = nev2 ? mo : 1;
+    // j = m .. 1 (surfdisp96.f:649-654); a step whose guard fires ends the pass and leaves x(j) as it was.
+    // The quotient of a step is computed whether or not the step counts -- also above the table's length and
+    // after the guard has fired, where denom may be 0 -- and dropped by the select (no traps on the device or
+    // in the host replay): the lanes of a wave are at different j anyway, so skipping saves a wave nothing.
+    bool live = true;
     const double guard = 1.0e-10 * fabs(ym1);
 #define BH_NEV_STEP(J, XJ, YJ, XJ1)                                               \
-    if (!bad && m >= J) {                                                         \
-        double denom = ym1 - n.YJ;                                                \
-        if (fabs(denom) < guard) bad = true;                                      \
-        else n.XJ = (-n.YJ * n.XJ1 + ym1 * n.XJ) / denom;                         \
-    }
-    if (m >= 7) {
-        BH_NEV_STEP(10, x10, y10, x11)
-        BH_NEV_STEP(9, x9, y9, x10)
-        BH_NEV_STEP(8, x8, y8, x9)
-        BH_NEV_STEP(7, x7, y7, x8)
+    {                                                                             \
+        const double denom = ym1 - n.YJ;                                          \
+        live = live & !((m >= J) & (fabs(denom) < guard));                        \
+        const double q = (-n.YJ * n.XJ1 + ym1 * n.XJ) / denom;                    \
+        n.XJ = (live & (m >= J)) ? q : n.XJ;                                      \
     }
     if (m >= 4) {
+        if (m >= 7) {
+            BH_NEV_STEP(10, x10, y10, x11)
+            BH_NEV_STEP(9, x9, y9, x10)
+            BH_NEV_STEP(8, x8, y8, x9)
+            BH_NEV_STEP(7, x7, y7, x8)
+        }
         BH_NEV_STEP(6, x6, y6, x7)
         BH_NEV_STEP(5, x5, y5, x6)
         BH_NEV_STEP(4, x4, y4, x5)
@@ -483,7 +493,7 @@ BH_DEV bool swd_neville(NevRegs &n, int &m, bool nev2, double c1, double del1, d
         if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) n.cycles += clock64() - lp_t0;
     }
 #endif
-    return !bad;
+    return live;
 }
 BH_DEV bool swd_neville(NevMem &n, int &m, bool nev2, double c1, double del1, double c2, double del2,
                         double c3, double del3, double *x1)
@@ -631,6 +641,58 @@ BH_DEV void swd_on_solved(SwdState &S, Src &src, const SwdTargetDev &tg, int wss
     S.ev = SWD_EV_BEGIN_PERIOD;
 }
 
+// ---- the rare events (bodies of swd_driver's other branches; shared with swd_events_pass) ----------
+// The next model (FETCH), surfdisp96.f:96-222: extremal velocities, start value, workspace.
+template <class Lay, class Src>
+BH_DEV void swd_on_fetch(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg, int wss)
+{
+    const double dc = (double)0.005f;               // dabs(dble(ddc)), ddc = 0.005 (real*4)
+    const int ifunc = tg.iwave, kmax = tg.nper, nmode = tg.mode;
+    S.mmax = src.next(lay, S.out, S.cws, S.cbws);
+    if (S.mmax <= 0) { S.st = SWD_ST_DONE; S.ev = SWD_EV_NONE; return; }
+    S.err = 0;
+    S.llw = 1;
+    if (lay.b(0) <= 0.0f) S.llw = 2;
+    if (tg.iflsph == 1) src.sphere(lay, S.mmax, ifunc);   // once per model (shared by a team)
+    int jmn = 0, jsol = 1;                    // extremal velocities, surfdisp96.f:139-156
+    S.betmx = -1.e20f;
+    float betmn = 1.e20f;
+    for (int i = 0; i < S.mmax; i++) {
+        float bi = lay.b(i), ai = lay.a(i);
+        if (bi > 0.01f && bi < betmn) { betmn = bi; jmn = i; jsol = 1; }
+        else if (bi <= 0.01f && ai < betmn) { betmn = ai; jmn = i; jsol = 0; }
+        if (bi > S.betmx) S.betmx = bi;
+    }
+    float cc1 = (jsol == 0) ? betmn : swd_gtsolh(lay.a(jmn), lay.b(jmn));
+    cc1 = .95f * cc1;
+    cc1 = .90f * cc1;
+    S.cc = (double)cc1;                       // cc = c1 = cm
+    S.cfail = (double)S.betmx + dc;           // getsol: c1 >= betmx+dc -> no root
+    if (nmode > 1)
+        for (int i = 0; i < kmax; i++) { S.cws[i * wss] = 0.0; S.cbws[i * wss] = 0.0; }
+    S.iq = 1; S.k = 1; S.ift = 999; S.c1 = S.cc;
+    if (kmax > 0 && nmode > 0) S.ev = SWD_EV_BEGIN_PERIOD;
+    else { src.done(S.err); S.ev = SWD_EV_FETCH; }
+}
+// The periods of a mode are done (BEGIN_PERIOD with k > kmax: 1600 loop done -> next mode).
+template <class Src>
+BH_DEV void swd_on_periods_done(SwdState &S, Src &src, const SwdTargetDev &tg)
+{
+    S.iq++; S.k = 1;
+    if (S.iq > tg.mode) { src.done(S.err); S.ev = SWD_EV_FETCH; }
+}
+// No root on the first solve: label 1700.
+template <class Src>
+BH_DEV void swd_on_noroot(SwdState &S, Src &src, const SwdTargetDev &tg)
+{
+    if (S.iq <= 1) S.err = 1;
+    S.ift = S.k;
+    src.fill_zero(S, S.k, tg.nper);               // cg(k..kmax) = 0, surfdisp96.f:348-354
+    S.iq++; S.k = 1;
+    if (S.iq > tg.mode) { src.done(S.err); S.ev = SWD_EV_FETCH; }
+    else S.ev = SWD_EV_BEGIN_PERIOD;
+}
+
 // ---- driver: task / period / pass / mode bookkeeping (surfdisp96.f:96-355) ------------------------
 // Consumes the pending event(s) until the search needs a period-equation value (S.st != DONE, then
 // S.omega / S.ceval say where) or the task source is drained (S.st == SWD_ST_DONE).
@@ -650,64 +712,28 @@ template <class Lay, class Src>
 BH_DEV void swd_driver(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
                        const double *BH_RESTRICT per, int wss, bool allow_fetch = true)
 {
-    const double dc = (double)0.005f;               // dabs(dble(ddc)), ddc = 0.005 (real*4)
-    const int ifunc = tg.iwave, kmax = tg.nper, nmode = tg.mode;
-    const bool multimode = nmode > 1;
+    const int kmax = tg.nper;
     while (S.ev != SWD_EV_NONE) {
-        if (S.ev == SWD_EV_FETCH) {                   // surfdisp96.f:96-222 for the next model
+        if (S.ev == SWD_EV_FETCH) {
             if (!allow_fetch) { S.st = SWD_ST_DONE; break; }
-            S.mmax = src.next(lay, S.out, S.cws, S.cbws);
-            if (S.mmax <= 0) { S.st = SWD_ST_DONE; S.ev = SWD_EV_NONE; break; }
-            S.err = 0;
-            S.llw = 1;
-            if (lay.b(0) <= 0.0f) S.llw = 2;
-            if (tg.iflsph == 1) src.sphere(lay, S.mmax, ifunc);   // once per model (shared by a team)
-            int jmn = 0, jsol = 1;                    // extremal velocities, surfdisp96.f:139-156
-            S.betmx = -1.e20f;
-            float betmn = 1.e20f;
-            for (int i = 0; i < S.mmax; i++) {
-                float bi = lay.b(i), ai = lay.a(i);
-                if (bi > 0.01f && bi < betmn) { betmn = bi; jmn = i; jsol = 1; }
-                else if (bi <= 0.01f && ai < betmn) { betmn = ai; jmn = i; jsol = 0; }
-                if (bi > S.betmx) S.betmx = bi;
-            }
-            float cc1 = (jsol == 0) ? betmn : swd_gtsolh(lay.a(jmn), lay.b(jmn));
-            cc1 = .95f * cc1;
-            cc1 = .90f * cc1;
-            S.cc = (double)cc1;                       // cc = c1 = cm
-            S.cfail = (double)S.betmx + dc;           // getsol: c1 >= betmx+dc -> no root
-            if (multimode)
-                for (int i = 0; i < kmax; i++) { S.cws[i * wss] = 0.0; S.cbws[i * wss] = 0.0; }
-            S.iq = 1; S.k = 1; S.ift = 999; S.c1 = S.cc;
-            if (kmax > 0 && nmode > 0) S.ev = SWD_EV_BEGIN_PERIOD;
-            else { src.done(S.err); S.ev = SWD_EV_FETCH; }
+            swd_on_fetch(S, lay, src, tg, wss);
         } else if (S.ev == SWD_EV_BEGIN_PERIOD) {
-            if (S.k > kmax) {                         // 1600 loop done -> next mode
-                S.iq++; S.k = 1;
-                if (S.iq > nmode) { src.done(S.err); S.ev = SWD_EV_FETCH; }
-                continue;
-            }
+            if (S.k > kmax) { swd_on_periods_done(S, src, tg); continue; }
             if (S.k >= S.ift) { S.ev = SWD_EV_NOROOT; S.pass = 0; continue; }
             swd_on_begin_period(S, tg, per, wss);
         } else if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) {
             swd_on_solved(S, src, tg, wss);
-        } else {                                      // NOROOT on the first solve: label 1700
-            if (S.iq <= 1) S.err = 1;
-            S.ift = S.k;
-            src.fill_zero(S, S.k, kmax);                  // cg(k..kmax) = 0, surfdisp96.f:348-354
-            S.iq++; S.k = 1;
-            if (S.iq > nmode) { src.done(S.err); S.ev = SWD_EV_FETCH; }
-            else S.ev = SWD_EV_BEGIN_PERIOD;
+        } else {
+            swd_on_noroot(S, src, tg);
         }
     }
 }
 
-// The pending event(s) of a search, the common chain first: "root found -> value stored -> next period"
-// is two straight-line blocks; only the rare events (task fetch, no root, end of the periods / of a
-// mode) enter the driver's loop.  In a wave of the throughput kernel some lane ends a period in 86 %
-// of the loop trips, and the loop -- an if-chain per trip, two trips per chain, the whole search state
-// copied between loop headers -- was 10.6 % of the kernel's lane-cycles (tools/lane_phase_profile.py).
-// Same operations in the same order as swd_driver alone.
+// The pending event(s) of a search for the team kernels (swd_team_body, swd_teamw_consume), the common chain first:
+// "root found -> value stored -> next period" is two straight-line blocks; only the rare events (task fetch, no root,
+// end of the periods / of a mode) enter the driver's loop.  Same operations in the same order as swd_driver alone.
+// (The throughput kernel, for which the fast blocks were written -- some lane of a wave ends a period in 86 % of its
+// loop trips -- has its own form below, swd_events_pass.)
 template <class Lay, class Src>
 BH_DEV void swd_events(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
                        const double *BH_RESTRICT per, int wss, bool allow_fetch = true)
@@ -718,6 +744,31 @@ BH_DEV void swd_events(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
     if (S.ev != SWD_EV_NONE)
 #endif
         swd_driver(S, lay, src, tg, per, wss, allow_fetch);
+}
+
+// The same events for the throughput kernel, without the driver's loop: one straight-line pass whose arms stand in
+// the order in which the chain of a search runs through them -- root found, end of the periods or of a mode, no
+// root, next model, period begins --, so that one pass takes a lane from the last root of a model to the first
+// trial of the next.  An arm consumes what an arm before it has announced; every pending event meets its arm, so
+// a pass consumes at least one.  What is still pending after the pass (S.ev != SWD_EV_NONE: a model without
+// periods, modes cut off at their first period) waits for the next pass: swd_lane lets the lane sit out one
+// evaluation.  Each arm does what swd_driver's branch for that event does, and a lane's events keep their order.
+// (As a loop inside the hot loop the driver kept a second set of registers for the search state and copied
+// the state into it and back at the loop's headers: 78 register moves and nothing else in three blocks,
+// DESIGN.md section 4.1.)
+template <class Lay, class Src>
+BH_DEV void swd_events_pass(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
+                            const double *BH_RESTRICT per, int wss)
+{
+    const int kmax = tg.nper;
+    if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) swd_on_solved(S, src, tg, wss);
+    if (S.ev == SWD_EV_BEGIN_PERIOD && (S.k > kmax || S.k >= S.ift)) {
+        if (S.k > kmax) swd_on_periods_done(S, src, tg);
+        else { S.ev = SWD_EV_NOROOT; S.pass = 0; }
+    }
+    if (S.ev == SWD_EV_NOROOT && S.pass != 1) swd_on_noroot(S, src, tg);
+    if (S.ev == SWD_EV_FETCH) swd_on_fetch(S, lay, src, tg, wss);
+    if (S.ev == SWD_EV_BEGIN_PERIOD && S.k <= kmax && S.k < S.ift) swd_on_begin_period(S, tg, per, wss);
 }
 
 // ---- control: getsol + nevill as a resumable machine, fed the period-equation value at S.ceval -----
@@ -796,6 +847,81 @@ BH_DEV void swd_control(SwdState &S, double del, Nev &nv)
     }
 }
 
+// The same machine for a table in registers (the throughput kernel), where the lanes of a wave are in
+// different states: the decisions are taken first, as flags, and every field of the state is then written once,
+// by selects, at the top level.  Written as nested arms like above, each join of divergent arms keeps an old and
+// a new copy of whatever the arms assign -- the Neville table and half the state -- and a third of the control
+// code's vector instructions were register moves.  Same operations on the same values as
+// the generic form; tests/hostsim/control_paths_sim.cpp runs the two side by side.  Only swd_kernel (and
+// swd_team_body, a diagnostic build) keeps its table in registers.  The narrow teams (swd_tpl_body: 8, 16, 32
+// lanes per search) keep theirs in LDS and run the generic form, although their teams diverge in control too and
+// carry as many moves (about 1 090 of 3 950 vector instructions): they sit at 195-199 of 200 allocated VGPRs, and
+// what the flat form does to that budget has not been measured.  They were left as they are.
+BH_DEV void swd_control(SwdState &S, double del, NevRegs &nv)
+{
+    const double dc = (double)0.005f;
+    const double pct = (double)0.01f;               // `0.01` literal in nevill is real*4
+    const bool isA = S.st == SWD_ST_A, isB = S.st == SWD_ST_B, isN = !(isA | isB);
+    const bool first = S.ifirst == 1;
+    const double half = 0.5 * (S.c1 + S.c2);
+    // getsol entry (A), surfdisp96.f:426-438: idir = -1 iff the signs of del1st and del1 differ
+    const int idirA = (first | !bh_signs_differ(S.del1st, del)) ? +1 : -1;
+    // scan (B), surfdisp96.f:461-470: bracketed -> nevill's first half (:583), else one step further
+    const bool brk = isB & bh_signs_differ(S.del1, del);
+    const bool scan = isB & !brk;
+    const bool outb = (S.c2 < S.cc) | (S.c2 >= S.cfail);
+    // the reference leaves the scan only through these two bounds; a NaN/Inf model would spin forever there (and
+    // hang the GPU here), hence the hard step cap
+    const bool noroot = scan & (outb | (S.nbrk + 1 > SWD_MAX_BRACKET_STEPS));
+    const bool bracket_step = isA | (scan & !noroot);
+    // nevill (TOP: label 100, surfdisp96.f:587-598; MID: straight to :599)
+    const bool top = isN & (S.st != SWD_ST_MID);
+    const int nctrl1 = S.nctrl + 1;
+    const bool fin_ctrl = top & (nctrl1 >= 100);
+    const bool tomid = top & !fin_ctrl & ((S.c3 < dmin(S.c1, S.c2)) | (S.c3 > dmax(S.c1, S.c2)));
+    const bool mid = isN & !fin_ctrl & !tomid;        // surfdisp96.f:599-669
+    const double s13 = S.del1 - del, s32 = del - S.del2;
+    const bool hi = bh_signs_differ(del, S.del1);    // the new point replaces the upper end
+    const double c1m = hi ? S.c1 : S.c3, del1m = hi ? S.del1 : del;
+    const double c2m = hi ? S.c3 : S.c2, del2m = hi ? del : S.del2;
+    const bool conv = fabs(c1m - c2m) <= 1.e-6 * c1m;
+    const bool refine = mid & !conv, finish = fin_ctrl | (mid & conv);
+    const int nevm = bh_signs_differ(s13, s32) ? 0 : S.nev;
+    const double ss1 = fabs(del1m), s1 = pct * ss1, ss2 = fabs(del2m), s2 = pct * ss2;
+    const bool do_half = (s1 > ss2) | (s2 > ss1) | (nevm == 0);
+    bool ok = false;
+    double x1 = 0.0;
+    int m = S.m;
+    if (refine & !do_half) ok = swd_neville(nv, m, nevm == 2, c1m, del1m, c2m, del2m, S.c3, del, &x1);
+    const double c3r = ok ? x1 : 0.5 * (c1m + c2m);    // refine: the Neville estimate, else the midpoint
+    const bool newhalf = brk | tomid;
+    const double c3n = newhalf ? half : refine ? c3r : S.c3;
+    // ---- the state, each field once
+    S.del1st = (isA & first) ? del : S.del1st;
+    S.idir = isA ? idirA : S.idir;
+    S.nbrk = isA ? 0 : (scan & !outb) ? S.nbrk + 1 : S.nbrk;
+    S.del1 = (isA | scan) ? del : mid ? del1m : S.del1;
+    S.del2 = isB ? del : mid ? del2m : S.del2;
+    S.del3 = isN ? del : S.del3;
+    S.c1 = scan ? S.c2 : mid ? c1m : S.c1;
+    S.c2 = mid ? c2m : S.c2;
+    S.c3 = c3n;
+    S.nev = brk ? 1 : tomid ? 0 : refine ? (ok ? 2 : 1) : S.nev;
+    S.m = refine ? (ok ? (m < 10 ? m + 1 : 10) : 1) : S.m;
+    S.nctrl = brk ? 1 : top ? nctrl1 : S.nctrl;
+    S.ceval = (newhalf | refine) ? c3n : S.ceval;
+    S.st = (brk | refine) ? SWD_ST_TOP : tomid ? SWD_ST_MID : S.st;
+    S.ev = noroot ? SWD_EV_NOROOT : S.ev;
+    if (bracket_step) {                               // label 1000, surfdisp96.f:448-460
+        S.c2 = swd_bracket_next(S.c1, S.idir, S.clow, dc);
+        S.ceval = S.c2; S.st = SWD_ST_B;
+    }
+    if (finish) {                                     // label 1000 of nevill + getsol tail (:475-476)
+        S.c1 = S.c3;
+        S.ev = (S.c1 > (double)S.betmx) ? SWD_EV_NOROOT : SWD_EV_SOLVED;
+    }
+}
+
 // Runs (model, target) tasks to completion, one after the other, on this lane: one period-equation
 // evaluation per loop trip, at a single call site (throughput kernel; see the header comment).
 // On the GPU `src` is a per-target atomic work queue: a lane whose search ends early pulls the next
@@ -812,7 +938,8 @@ BH_DEV void swd_lane(Lay &lay, Src &src, const SwdTargetDev &tg, const double *B
     swd_nev_init(nv);
     long nc = 0;
     for (;;) {
-        swd_events(S, lay, src, tg, per, wss);
+        swd_events_pass(S, lay, src, tg, per, wss);
+        if (S.ev != SWD_EV_NONE) continue;
         if (S.st == SWD_ST_DONE) break;
         double wvno = S.omega / S.ceval;
         double del = (tg.iwave == 1) ? swd_dltar1(lay, S.mmax, S.llw, wvno, S.omega)

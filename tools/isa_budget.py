@@ -4,6 +4,9 @@ selects, LDS, SALU, waits.  Used for the per-phase budgets in DESIGN.md / profil
 (dynamic totals come from the PMC pass, SQ_INSTS_VALU).
 
     python tools/isa_budget.py rf_kernelILb0 [min block size]      # mangled-name fragment
+    python tools/isa_budget.py swd_kernel 8 --moves                # also: register moves (v_mov_b32 / v_mov_b64) per block
+
+move_counts(frag) returns (vector instructions, register moves) of a kernel (tests/test_swd_state_moves.py).
 """
 import collections
 import os
@@ -35,7 +38,13 @@ def cls(op):
     return 'salu' if op.startswith('s_') else 'other'
 
 
-def main(frag, minsize=1):
+def is_move(op):
+    """A plain register move: v_mov_b32 / v_mov_b64 in any encoding (the search state copied between register sets)."""
+    return op.startswith(('v_mov_b32', 'v_mov_b64'))
+
+
+def kernel_blocks(frag):
+    """Basic blocks of the kernel whose mangled name holds `frag`: [{name, note, ins: [opcode, ...]}, ...]"""
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, 'k.s')
         flags = [f for f in _lib.HIPCC_FLAGS if f not in ('-shared', '-fPIC')]
@@ -53,16 +62,31 @@ def main(frag, minsize=1):
             blocks.append(cur)
         elif l.startswith('\t') and not l.strip().startswith((';', '.')):
             cur['ins'].append(l.split()[0])
+    return blocks
+
+
+def move_counts(frag):
+    ins = [o for b in kernel_blocks(frag) for o in b['ins']]
+    return sum(o.startswith('v_') for o in ins), sum(is_move(o) for o in ins)
+
+
+def main(frag, minsize=1, moves=False):
+    blocks = kernel_blocks(frag)
     keys = ['v_f64', 'v_other', 'v_sel', 'v_mov', 'lds', 'vmem', 'salu', 's_wait']
-    print('%-12s %5s  %s  %s' % ('block', 'instr', '  '.join('%7s' % k for k in keys), 'loop'))
+    extra = ['valu', 'moves'] if moves else []
+    print('%-12s %5s  %s  %s' % ('block', 'instr', '  '.join('%7s' % k for k in keys + extra), 'loop'))
     tot = collections.Counter()
     for b in blocks:
         c = collections.Counter(cls(o) for o in b['ins'])
+        if moves:
+            c['valu'] = sum(o.startswith('v_') for o in b['ins'])
+            c['moves'] = sum(is_move(o) for o in b['ins'])
         tot.update(c)
         if len(b['ins']) >= minsize:
-            print('%-12s %5d  %s  %s' % (b['name'], len(b['ins']), '  '.join('%7d' % c[k] for k in keys), b['note'][:44]))
-    print('%-12s %5d  %s' % ('total', sum(tot.values()), '  '.join('%7d' % tot[k] for k in keys)))
+            print('%-12s %5d  %s  %s' % (b['name'], len(b['ins']), '  '.join('%7d' % c[k] for k in keys + extra), b['note'][:44]))
+    print('%-12s %5d  %s' % ('total', sum(tot[k] for k in keys) + tot['other'], '  '.join('%7d' % tot[k] for k in keys + extra)))
 
 
 if __name__ == '__main__':
-    main(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+    argv = [a for a in sys.argv[1:] if a != '--moves']
+    main(argv[0], int(argv[1]) if len(argv) > 1 else 1, moves='--moves' in sys.argv)
