@@ -985,7 +985,8 @@ __global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team16_kernel(SwdArg
 __global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team8_kernel(SwdArgs A) { BH_NARROW_BODY<8>(A); }
 
 // -------------------------------------------------------------------------------------------- RF
-// bit reversal (+ 1/sqrt(n)) and radix-2 butterflies of Mb buffers in LDS; all threads of the group
+// bit reversal (+ 1/sqrt(n)) and the butterfly passes (rf_core.h: one radix-2 stage when log2 n is odd, radix-4 passes
+// of two stages each for the rest) of Mb buffers in LDS; all threads of the group
 __device__ __forceinline__ void rf_block_fft(double *S, int per_model, int Mb, int n, const RfLaunch &P,
                                              const double *tw, int tid)
 {
@@ -999,10 +1000,17 @@ __device__ __forceinline__ void rf_block_fft(double *S, int per_model, int Mb, i
 #if defined(BH_RF_EXP) && BH_RF_EXP == 2
     return;
 #endif
-    for (int l = 1; l < n; l <<= 1) {
+    if (rf_fft_radix2_first(P.log2n)) {              // odd log2 n: one radix-2 stage, the rest in pairs
         for (int idx = tid; idx < Mb * (n / 2); idx += RF_T) {
             int m = idx / (n / 2), bf = idx - m * (n / 2);
-            rf_fft_butterfly(S + (long)m * per_model, tw, l, bf);
+            rf_fft_butterfly(S + (long)m * per_model, tw, 1, bf);
+        }
+        __syncthreads();
+    }
+    for (int l = rf_fft_radix4_first(P.log2n); 4 * l <= n; l <<= 2) {
+        for (int idx = tid; idx < Mb * (n / 4); idx += RF_T) {
+            int m = idx / (n / 4), bf = idx - m * (n / 4);
+            rf_fft_butterfly4(S + (long)m * per_model, tw, l, bf);
         }
         __syncthreads();
     }

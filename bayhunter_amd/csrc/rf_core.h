@@ -343,6 +343,65 @@ BH_DEV RfFreq rf_freq_load_lgw(const double *BH_RESTRICT ftab, int j)
     return F;
 }
 
+// The attenuation exponent of a phase factor, x = w d Im(slowness), is about w d / (2 Q v): <= 0.2 for crustal Q, up
+// to ten for Q = 5 over a thick slow layer (tests/rf_extreme.py).  For |x| <= RF_EXP_SMALL bh_exp_bounded's range
+// reduction does nothing: k = rint(x log2 e) is zero as long as |x| log2 e <= 0.5, i.e. |x| <= ln 2 / 2 = 0.3466; with
+// k = 0 the reduced argument fma(-k, ln2, x) is x itself (for x = -0 it is +0: the polynomial is 1 either way) and the
+// final ldexp(p, 0) is p.  rf_exp_small is that polynomial -- the same coefficients in the same Horner order, Taylor to
+// degree 13, truncation 4e-18 on |r| <= ln 2 / 2 -- of x directly: inside the bound its result equals bh_exp_bounded's
+// bit for bit (deviation 0 ulp), six vector instructions shorter (multiply, round, two fma, convert, ldexp).  The bound
+// is 0.34 and not the 0.5 the arguments would allow: beyond ln 2 / 2 the truncation alone is 0.5^14 / 14! = 7e-16, three
+// ulp of a result near one.
+#define RF_EXP_SMALL 0.34
+#if defined(BH_HOSTSIM) && defined(BH_HOSTSIM_GLIBC_MATH)
+BH_DEV double rf_exp_small(double x) { return std::exp(x); }
+#else
+BH_DEV double rf_exp_small(double x)
+{
+    double p = 1.6059043836821613e-10;                  // 1/13!, bh_exp_bounded's polynomial
+    p = bh_fma_k(p, x, 2.08767569878681e-09);
+    p = bh_fma_k(p, x, 2.505210838544172e-08);
+    p = bh_fma_k(p, x, 2.755731922398589e-07);
+    p = bh_fma_k(p, x, 2.7557319223985893e-06);
+    p = bh_fma_k(p, x, 2.48015873015873e-05);
+    p = bh_fma_k(p, x, 1.984126984126984e-04);
+    p = bh_fma_k(p, x, 1.3888888888888889e-03);
+    p = bh_fma_k(p, x, 8.333333333333333e-03);
+    p = bh_fma_k(p, x, 4.1666666666666664e-02);
+    p = bh_fma_k(p, x, 1.6666666666666666e-01);
+    p = bh_fma(p, x, 0.5);
+    p = bh_fma(p, x, 1.0);
+    p = bh_fma(p, x, 1.0);
+    return p;
+}
+#endif
+// True when c holds in every active lane of the wave: one scalar compare of the ballot, so a branch on it is a scalar
+// branch and neither arm runs under a partial exec mask.  (A NaN argument fails c: the wave takes the full form.)  The
+// host replay runs one virtual thread at a time and decides per thread -- the two forms agree bit for bit wherever the
+// short one is allowed, so which lanes share a wave does not show in the result.
+#if defined(BH_HOSTSIM)
+BH_DEV bool rf_wave_all(bool c) { return c; }
+#else
+BH_DEV bool rf_wave_all(bool c) { return __builtin_amdgcn_ballot_w64(!c) == 0ull; }
+#endif
+// exp(za), exp(zb) of the two phase factors of a layer: the exponent without range reduction when both real parts of
+// every active lane are inside RF_EXP_SMALL, cexp_bounded's otherwise; sine and cosine as there.
+BH_DEV void rf_cexp_pair(cd za, cd zb, cd *ea, cd *eb)
+{
+    double xa, xb, s, c;
+    if (rf_wave_all(fabs(za.re) <= RF_EXP_SMALL && fabs(zb.re) <= RF_EXP_SMALL)) {
+        xa = rf_exp_small(za.re);
+        xb = rf_exp_small(zb.re);
+    } else {
+        xa = bh_exp_bounded(za.re);
+        xb = bh_exp_bounded(zb.re);
+    }
+    bh_sincos(za.im, &s, &c);
+    *ea = mk(xa * c, xa * s);
+    bh_sincos(zb.im, &s, &c);
+    *eb = mk(xb * c, xb * s);
+}
+
 #if !defined(BH_HOSTSIM)
 #pragma clang fp contract(fast)
 #endif
@@ -435,7 +494,8 @@ BH_DEV cd rf_phase3_body(const double *S, const RfLayout &lo, const RfLaunch &P,
         }
         cd plc = csqrt_fast(gp * lay[RF_P_IVP2] - (ROW ? row_p2 : P.p2));   // Q finite -> im != 0
         cd slc = csqrt_fast(gs * lay[RF_P_IVS2] - (ROW ? row_p2 : P.p2));
-        cd e11 = cexp_bounded(mk(wd * plc.im, -(wd * plc.re))), e22 = cexp_bounded(mk(wd * slc.im, -(wd * slc.re)));
+        cd e11, e22;
+        rf_cexp_pair(mk(wd * plc.im, -(wd * plc.re)), mk(wd * slc.im, -(wd * slc.re)), &e11, &e22);
         const double *ci = lay + RF_P_COEF, *cn = ci + RF_REC;
         if (i == 0) rf_layer_step<M, true>(ci, cn, e11, e22, m, tq, g);
         else rf_layer_step<M, false>(ci, cn, e11, e22, m, tq, g);
@@ -548,6 +608,30 @@ BH_DEV void rf_fft_butterfly(double *X, const double *tw, int l, int bf)
     rf_xst(X, i + l, a - tmp);
     rf_xst(X, i, a + tmp);
 }
+// Two stages in one trip: radix-4 butterfly number bf (0 .. n/4-1) of the pass that takes the stages with half-spans
+// l and 2l.  Elements i, i+l, i+2l, i+3l (i = 4l * block + m, m < l) are the two pairs of stage l -- both with the
+// twiddle tw[l+m] -- and then, crosswise, the pairs (i, i+2l) and (i+l, i+3l) of stage 2l with tw[2l+m] and tw[3l+m].
+// Every product and sum is the one rf_fft_butterfly forms, in the same order, so a pass equals the two radix-2 stages
+// bit for bit; what goes is half of the trips through LDS (four loads and stores per four elements instead of eight),
+// of the index and swizzle arithmetic and of the barriers between stages.
+BH_DEV void rf_fft_butterfly4(double *X, const double *tw, int l, int bf)
+{
+    int m = bf & (l - 1), i = ((bf - m) << 2) + m;
+    cd w1 = ld_cd(tw + 2 * (l + m)), w2 = ld_cd(tw + 2 * (2 * l + m)), w3 = ld_cd(tw + 2 * (3 * l + m));
+    cd x0 = rf_xld(X, i), x1 = rf_xld(X, i + l), x2 = rf_xld(X, i + 2 * l), x3 = rf_xld(X, i + 3 * l);
+    cd t1 = w1 * x1, t3 = w1 * x3;
+    cd a0 = x0 + t1, a1 = x0 - t1, a2 = x2 + t3, a3 = x2 - t3;
+    cd u2 = w2 * a2, u3 = w3 * a3;
+    rf_xst(X, i, a0 + u2);
+    rf_xst(X, i + l, a1 + u3);
+    rf_xst(X, i + 2 * l, a0 - u2);
+    rf_xst(X, i + 3 * l, a1 - u3);
+}
+// The plan of the transform's passes behind the bit reversal, for the kernel (rf_block_fft, kernels.hip) and the host
+// replay (rf_host.h) alike: when log2 n is odd (128, 512) one radix-2 stage with half-span 1, then radix-4 passes
+// with half-spans l = rf_fft_radix4_first(log2n), 4l, 16l, ... as long as 4l <= n.
+BH_HD bool rf_fft_radix2_first(int log2n) { return (log2n & 1) != 0; }
+BH_HD int rf_fft_radix4_first(int log2n) { return (log2n & 1) ? 2 : 1; }
 
 
 }  // namespace bh

@@ -73,4 +73,50 @@ inline void rf_fill_twiddles(double *tw, int nsamp)
         }
 }
 
+// ---- host replay of the workgroup program (only with -DBH_HOSTSIM: the phase functions as plain C++) -------------
+#if defined(BH_HOSTSIM)
+// The inverse transform of phase 4 on one model's buffer X, pass by pass as rf_block_fft (kernels.hip) runs it: the
+// same plan (rf_fft_radix2_first / rf_fft_radix4_first) and the same butterflies (rf_fft_butterfly / rf_fft_butterfly4).
+// radix4 = false: every stage as a radix-2 stage, the transform before the radix-4 passes (for comparing the two).
+inline void rf_host_fft(double *X, const double *tw, const RfLaunch &P, bool radix4 = true)
+{
+    const int n = P.nsamp;
+    for (int i = 0; i < n; i++) rf_fft_bitrev_scale(X, n, P.log2n, P.sc, i);
+    if (!radix4) {
+        for (int l = 1; l < n; l <<= 1)
+            for (int bf = 0; bf < n / 2; bf++) rf_fft_butterfly(X, tw, l, bf);
+        return;
+    }
+    if (rf_fft_radix2_first(P.log2n))
+        for (int bf = 0; bf < n / 2; bf++) rf_fft_butterfly(X, tw, 1, bf);
+    for (int l = rf_fft_radix4_first(P.log2n); 4 * l <= n; l <<= 2)
+        for (int bf = 0; bf < n / 4; bf++) rf_fft_butterfly4(X, tw, l, bf);
+}
+
+// Phases 1 to 4 of the uniform form for one model on a host array laid out like the model's LDS block; rf[0 .. nout).
+// S: rf_layout(nlay, nsamp).per_model doubles, tw: 2 nsamp, ftab: RF_FTAB (nsamp / 2 + 1) doubles of work space.
+inline void rf_host_replay(int nlay, const double *h, const double *vp, const double *vs, const double *rho,
+                           const double *qp, const double *qs, double p, double gauss, int nsamp, double fsamp,
+                           double tshift, double nsv, int waveno, int nout, double *S, double *tw, double *ftab,
+                           double *rf, bool radix4 = true)
+{
+    RfLaunch P = RfLaunch();
+    rf_fill_launch(P, p, gauss, nsamp, fsamp, tshift, nsv, waveno, nout);
+    P.sigma = std::nan("");
+    P.Lmax = nlay;
+    const RfLayout lo = rf_layout(nlay, nsamp);
+    for (int k = 0; k < lo.per_model; k++) S[k] = 0.0;
+    rf_fill_twiddles(tw, nsamp);
+    rf_fill_freq_table(P, ftab);
+    for (int i = 0; i < nlay; i++) rf_phase1_layer(S, lo, nlay, i, h, vp, vs, rho, qp, qs, 0);
+    for (int i = 0; i < nlay; i++) rf_phase2_interface(S, lo, P, nlay, i, vp[0], vs[0]);
+    // (every task reads the layer records, which the spectrum's rows never reach: rf_layout)
+    for (int j = 0; j < P.nfreq; j++)
+        rf_xst(S, j, j < P.nact ? rf_phase3_task(S, lo, P, nlay, j, rf_freq_load(ftab, j)) : mk(0., 0.));
+    for (int i = nsamp / 2 + 1; i < nsamp; i++) rf_fft_hermitian(S, nsamp, i);
+    rf_host_fft(S, tw, P, radix4);
+    for (int i = 0; i < nout; i++) rf[i] = P.qn * S[2 * rf_swz(i)];
+}
+#endif
+
 }  // namespace bh
