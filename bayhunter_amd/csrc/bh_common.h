@@ -170,6 +170,13 @@ BH_DEV cd conj(cd a) { return mk(a.re, -a.im); }
 
 // complex / complex: Smith's algorithm as in libgcc's __divdc3 (the reference's std::complex
 // division lowers to it); the NaN/Inf recovery tail of __divdc3 is not needed here.
+// Not contracted: only the set-up phase of the receiver function divides complex by complex (rf_coeffs, rf_coeffm,
+// rf_displacement2: once per interface), and that phase follows the reference expression by expression.  Smith's
+// numerators a (c/d) + b cancel, so a fused product there moved a component by up to 272 ulp from libgcc's quotient
+// (4 ulp of the modulus; tests/test_gpu_math_probe.py); with every product rounded the device's quotient is libgcc's.
+#if !defined(BH_HOSTSIM)
+#pragma clang fp contract(off)
+#endif
 BH_DEV cd operator/(cd x, cd y)
 {
     double a = x.re, b = x.im, c = y.re, d = y.im, ratio, denom;
@@ -183,8 +190,15 @@ BH_DEV cd operator/(cd x, cd y)
     return mk(((b * ratio) + a) / denom, (b - (a * ratio)) / denom);
 }
 BH_DEV cd rdiv(double x, cd y) { return mk(x, 0.0) / y; }
+#if !defined(BH_HOSTSIM)
+#pragma clang fp contract(fast)
+#endif
 // Fast reciprocal / square root for the tolerance-checked receiver-function recursion: hardware
-// seed (v_rcp_f64 / v_rsq_f64) + Newton steps, ~1 ulp, half the instructions of the IEEE sequences.
+// seed (v_rcp_f64 / v_rsq_f64) + Newton steps, half the instructions of the IEEE sequences.  Measured on the device
+// against long double, 2^19 operands each of magnitude 2^-20 .. 2^20 and 2^-300 .. 2^300 (bh_selftest_math,
+// tests/test_gpu_math_probe.py): frcp, fsqrt and the root of fsqrt_hinv 0.500 ulp at worst, i.e. no operand found on
+// which they are not correctly rounded; h of fsqrt_hinv 1.49 ulp (what 0.5 / sqrt(x) in two roundings gives: 1.49);
+// crecip 2.72 ulp per component, csqrt_fast 2.64.
 // Arguments there are well scaled (1e-6..1e6) and non-zero: fsqrt has no select for a zero or negative
 // argument (it is only asked for |z| of a slowness, which cannot vanish; a NaN stays a NaN).
 #if defined(BH_HOSTSIM)
@@ -253,8 +267,12 @@ BH_DEV void fsqrt_hinv(double x, double *gout, double *hout)
     h = __builtin_fma(h, r, h);
     double d = __builtin_fma(-g, g, x);
     g = __builtin_fma(d, h, g);
-    r = __builtin_fma(-h, g, 0.5);                // one more step on h: ~1 ulp like frcp
-    h = __builtin_fma(h, r, h);
+    // One more step on h, against the refined g.  r = 1/2 - h g is half of Newton's residual 1 - 2 h g, so the step is
+    // h + h (2 r).  (It was h + h r until the device test of this function: that halves the error where Newton
+    // squares it -- 10.0 ulp at worst in h, 18.7 in csqrt_fast's smaller component.  The coupled step above is a
+    // different iteration: there g and h carry the same error and r corrects both.)
+    r = __builtin_fma(-h, g, 0.5);
+    h = __builtin_fma(h, r + r, h);
     *gout = g;
     *hout = h;
 }
@@ -271,7 +289,9 @@ BH_DEV cd csqrt_fast(cd z)
     return (re > 0) ? mk(m, o) : mk(fabs(o), copysign(m, im));
 }
 
-// principal square root, glibc csqrt's formulation for finite non-zero arguments
+// principal square root, glibc csqrt's formulation for finite non-zero arguments, except that |z| is sqrt(re^2 + im^2)
+// where glibc takes hypot(re, im): bit-equal to glibc for im == 0 (all the library asks: the vertical slownesses of
+// rf_coeffm) and for re == 0, up to 2 ulp from it for 6 % of generic arguments (tests/test_math_probe.py)
 BH_DEV cd csqrt_(cd z)
 {
     double re = z.re, im = z.im;

@@ -2,7 +2,10 @@
 //
 // The reference calls glibc's sin, cos, exp (through dsin/dcos/dexp and std::complex).  No device
 // libm reproduces those bit for bit, so the only requirement here is accuracy (< 1 ulp, measured
-// against glibc in tests/test_hostsim.py::test_math_accuracy) -- and a short instruction stream:
+// against glibc in tests/test_hostsim.py::test_math_accuracy for the host build, and on the device's own
+// output in tests/test_gpu_math_probe.py, which also finds the two builds equal bit for bit: the slow
+// reduction, the NaN arm, saturation and subnormal results included; tests/test_math_probe.py has the
+// host forms' special values) -- and a short instruction stream:
 // the period equation spends half of its instructions in these three functions, and a wave whose
 // lanes straddle the oscillatory/evanescent branch of surfdisp96.f:929-968 pays for both sides.
 //

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "swd_form_table.h"
 #include "rf_host.h"
+#include "math_probe.h"
 
 namespace {
 
@@ -1075,6 +1076,31 @@ int bh_selftest_division(long n, unsigned seed, int max_exp, long *mismatches)
     BH_HIP(hipMemcpy(&h, d, sizeof(h), hipMemcpyDeviceToHost));
     BH_HIP(hipFree(d));
     *mismatches = (long)h;
+    return BH_OK;
+}
+
+// One primitive of math_probe.h over n elements.  The device buffers cover whole workgroups and the input's tail behind
+// element n is NaN (all bits set), so a kernel that lost its `i < n` guard would stay inside its allocations and
+// rf_cexp_pair's wave-uniform test would see lanes outside its bound there.
+int bh_selftest_math(int op, long n, const double *in, double *out)
+{
+    if (op < 0 || op >= bh::MP_NOPS) return fail_arg("unknown op");
+    if (n < 0 || n > (1L << 28)) return fail_arg("n out of range");
+    if (!in || !out) return fail_arg("NULL pointer");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (n == 0) return BH_OK;
+    const size_t npad = ((size_t)n + 255) / 256 * 256;
+    const size_t bin = npad * bh::MP_IN * sizeof(double), bout = npad * bh::MP_OUT * sizeof(double);
+    const size_t nin = (size_t)n * bh::MP_IN * sizeof(double), nout = (size_t)n * bh::MP_OUT * sizeof(double);
+    char *d = nullptr;
+    BH_HIP(hipMalloc((void **)&d, bin + bout));
+    hipError_t e = hipMemset(d, 0xff, bin + bout);
+    if (e == hipSuccess) e = hipMemcpy(d, in, nin, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = bh::launch_math_probe(op, n, (const double *)d, (double *)(d + bin), nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d + bin, nout, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    BH_HIP(e);
     return BH_OK;
 }
 

@@ -304,6 +304,15 @@ int synrf_cwrap(int nsamp, double fsamp, double tshift, double p, double a, doub
  * and quotients by an exact square through the squared reciprocal. */
 int bh_selftest_division(long n, unsigned seed, int max_exp, long *mismatches);
 
+/* The transcendental and complex primitives of the kernels (csrc/bh_math.h, bh_common.h, rf_core.h, swd_team.h), one
+ * call per element on the device: primitive `op` (enum MathProbeOp, csrc/math_probe.h) applied to n elements of six
+ * input doubles each, four output doubles each (unused outputs 0).  in and out are host arrays; the call allocates,
+ * copies in, launches on the null stream, copies back and frees.  Thread i of the kernel handles element i in
+ * workgroups of 256, so wave w holds elements 64 w .. 64 w + 63.  BH_ERR_ARG for an unknown op, n < 0 or a null
+ * pointer.  tests/test_gpu_math_probe.py compares the result with the host build of the same header bit for bit
+ * and with extended precision. */
+int bh_selftest_math(int op, long n, const double *in /* host, [n][6] */, double *out /* host, [n][4] */);
+
 /* ---- lock-step chain pool (host side of the sampler) ------------------------------------ */
 /* Replaces the per-process loop `while iiter < iter_phase2: SingleChain.iterate()`
  * (src/SingleChain.py:511-589,591-606) for MANY chains advanced together, so that every iteration
