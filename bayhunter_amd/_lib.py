@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
            "posterior_sets.hip", "datafits.hip", "math_probe.hip"]
-HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h",
+HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "stats_core.h",
            "stats_host.h", "math_probe.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
@@ -174,6 +174,7 @@ _SIGS = {
     "bh_eval_set_concurrency": (C.c_int, [_vp, C.c_int]),
     "bh_eval_set_observations": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
     "bh_eval_set_rf_slowness": (C.c_int, [_vp, C.c_int, _vp]),
+    "bh_eval_set_gaps": (C.c_int, [_vp, C.c_int, _vp]),
     "bh_forward_batch": (C.c_int, [C.c_int] * 3 + [_vp] * 5 + [C.c_int, C.POINTER(SwdTarget), _vp, C.c_int,
                                    C.POINTER(EvalInterp), C.c_int, C.POINTER(RfParams), _vp, C.c_double, C.c_int, _vp,
                                    C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
@@ -211,6 +212,10 @@ _SIGS = {
                                       C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "bh_likelihood_sets": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(LikeTarget), _vp, C.c_int, _vp, C.c_int,
                                      C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "bh_likelihood_gaps_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "bh_likelihood_sets_gaps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(LikeTarget), _vp, C.c_int, _vp, C.c_int,
+                                          C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                          _vp, _vp, C.c_size_t, _vp]),
     "bh_surfdisp96": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, _vp, _vp, C.POINTER(C.c_int)]),
     "bh_synrf": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,

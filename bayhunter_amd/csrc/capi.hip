@@ -15,6 +15,7 @@
 #include <vector>
 #include "../../include/bayhunter_amd.h"
 #include "kernels.h"
+#include "like_core.h"
 #include "swd_form_table.h"
 #include "rf_host.h"
 #include "math_probe.h"
@@ -38,6 +39,14 @@ int fail_arg(const char *what)
 namespace bh {
 int fail_arg_(const char *what) { g_err = what; return BH_ERR_ARG; }
 int fail_hip_(int e, const char *what) { return fail_hip((hipError_t)e, what); }     // evalplan.hip
+
+// the likelihood of observation sets, with or without data gaps (defined with bh_likelihood_sets; evalplan.hip)
+int likelihood_sets_(int stages, int B, int ntargets, const bh_like_target *targets, const double *out, int out_stride,
+                     const int *err, int nflags, int nsets, const int *obs_id, const double *yobs, int set_stride,
+                     const double *set_scale, const double *set_logdet, const double *noise, const double *aux,
+                     double *logL, double *misfits, void *workspace, size_t workspace_bytes,
+                     const unsigned char *set_present, void *gaps_workspace, size_t gaps_workspace_bytes,
+                     const int *gap_cols, const int *gap_cnt, void *stream);
 
 // bh_rf_batch's parameter checks: bh_forward_batch (evalplan.hip) makes them before its first launch
 int check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool zr)
@@ -889,6 +898,60 @@ int bh_likelihood_sets(int stages, int B, int ntargets, const bh_like_target *ta
                        const double *aux, double *logL, double *misfits, void *workspace, size_t workspace_bytes,
                        void *stream)
 {
+    return bh::likelihood_sets_(stages, B, ntargets, targets, out, out_stride, err, nflags, nsets, obs_id, yobs, set_stride,
+                                set_scale, set_logdet, noise, aux, logL, misfits, workspace, workspace_bytes, nullptr,
+                                nullptr, 0, nullptr, nullptr, stream);
+}
+
+size_t bh_likelihood_gaps_workspace_bytes(int nsets, int set_stride, int ntargets)
+{
+    if (nsets < 1 || set_stride < 1 || ntargets < 1) return 0;
+    return ((size_t)nsets * (size_t)set_stride + (size_t)nsets * (size_t)ntargets) * sizeof(int);
+}
+
+int bh_likelihood_sets_gaps(int stages, int B, int ntargets, const bh_like_target *targets, const double *out,
+                            int out_stride, const int *err, int nflags, int nsets, const int *obs_id, const double *yobs,
+                            int set_stride, const double *set_scale, const double *set_logdet, const double *noise,
+                            const double *aux, double *logL, double *misfits, void *workspace, size_t workspace_bytes,
+                            const unsigned char *set_present, void *gaps_workspace, size_t gaps_workspace_bytes,
+                            void *stream)
+{
+    return bh::likelihood_sets_(stages, B, ntargets, targets, out, out_stride, err, nflags, nsets, obs_id, yobs, set_stride,
+                                set_scale, set_logdet, noise, aux, logL, misfits, workspace, workspace_bytes, set_present,
+                                gaps_workspace, gaps_workspace_bytes, nullptr, nullptr, stream);
+}
+
+}  // extern "C"
+
+namespace bh {
+// The kept-sample tables of like_core.h from set_present[nsets][set_stride], cols then cnt in one vector (the layout
+// of bh_likelihood_gaps_workspace_bytes), after the refusals: a dense-Gaussian target with a gap, a target without
+// a kept sample.  The targets have been checked against set_stride.  evalplan.hip: bh_eval_set_gaps.
+int like_gaps_derive(const char *who, int nsets, int set_stride, int ntargets, const bh_like_target *targets,
+                     const unsigned char *set_present, std::vector<int> &tables, bool *any_gap)
+{
+    tables.assign((size_t)nsets * set_stride + (size_t)nsets * ntargets, 0);
+    int s = 0, t = 0;
+    const int rc = like_gap_tables(nsets, set_stride, ntargets, targets, set_present, tables.data(),
+                                   tables.data() + (size_t)nsets * set_stride, any_gap, &s, &t);
+    if (rc == 1)
+        return fail_arg_((std::string(who) + ": set " + std::to_string(s) + ", target " + std::to_string(t) +
+                          " is BH_COV_GAUSS and has a gap (its dense R^-1 belongs to one n and to contiguous samples)").c_str());
+    if (rc == 2)
+        return fail_arg_((std::string(who) + ": set " + std::to_string(s) + ", target " + std::to_string(t) +
+                          " has no sample left (set_present is 0 in all its columns)").c_str());
+    return BH_OK;
+}
+
+// bh_likelihood_sets and bh_likelihood_sets_gaps.  The gaps come as set_present (HOST) with a device workspace for
+// the tables derived from it, or as tables that are on the device already (gap_cols, gap_cnt: an evaluation plan's).
+int likelihood_sets_(int stages, int B, int ntargets, const bh_like_target *targets, const double *out, int out_stride,
+                     const int *err, int nflags, int nsets, const int *obs_id, const double *yobs, int set_stride,
+                     const double *set_scale, const double *set_logdet, const double *noise, const double *aux,
+                     double *logL, double *misfits, void *workspace, size_t workspace_bytes,
+                     const unsigned char *set_present, void *gaps_workspace, size_t gaps_workspace_bytes,
+                     const int *gap_cols, const int *gap_cnt, void *stream)
+{
     if (stages < 1 || stages > 3) return fail_arg("bh_likelihood_stage: stages is BH_LIKE_STAGE_GAUSS | BH_LIKE_STAGE_REST");
     if (B < 0 || ntargets < 1 || ntargets > BH_MAX_TARGETS) return fail_arg("B/ntargets out of range");
     if (nsets < 1) return fail_arg("bh_likelihood_sets: nsets < 1");
@@ -912,6 +975,20 @@ int bh_likelihood_sets(int stages, int B, int ntargets, const bh_like_target *ta
         A.tg[t] = bh::LikeTargetDev{s.n, s.off, s.cov, s.aux_off, s.logdet_extra};
         if (s.n > nmax) nmax = s.n;
     }
+    bh::LikeGaps G{gap_cols, gap_cnt};
+    bool masked = gap_cols && gap_cnt;
+    std::vector<int> tables;
+    if (set_present) {
+        const size_t need = bh_likelihood_gaps_workspace_bytes(nsets, set_stride, ntargets);
+        if (!gaps_workspace || gaps_workspace_bytes < need) {
+            g_err = "bh_likelihood_sets_gaps: gaps_workspace is NULL or smaller than bh_likelihood_gaps_workspace_bytes()";
+            return BH_ERR_WORKSPACE;
+        }
+        if (int rc = like_gaps_derive("bh_likelihood_sets_gaps", nsets, set_stride, ntargets, targets, set_present, tables, &masked))
+            return rc;
+        G.cols = (const int *)gaps_workspace;
+        G.cnt = G.cols + (size_t)nsets * set_stride;
+    }
     int rc = ensure_device();
     if (rc) return rc;
     A.B = B; A.ntargets = ntargets; A.out_stride = out_stride; A.nflags = nflags;
@@ -922,9 +999,18 @@ int bh_likelihood_sets(int stages, int B, int ntargets, const bh_like_target *ta
     A.gq = (need > 0 && workspace && workspace_bytes >= need) ? (double *)workspace : nullptr;
     A.gq_groups = (int)(need / ((size_t)ntargets * (size_t)B * 2 * sizeof(double)));
     if (stages != 3 && !A.gq) return fail_arg("bh_likelihood_stage: the stages can only be split with a workspace");
-    BH_HIP(bh::launch_like(A, nmax, (hipStream_t)stream, stages));
+    masked = masked && (stages & BH_LIKE_STAGE_REST);        // (the dense products have no gaps)
+    if (masked && set_present) {
+        // in stream order behind whatever still reads the workspace; the host copy goes when this call returns
+        BH_HIP(hipMemcpyAsync(gaps_workspace, tables.data(), tables.size() * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream));
+        BH_HIP(hipStreamSynchronize((hipStream_t)stream));
+    }
+    BH_HIP(bh::launch_like(A, nmax, (hipStream_t)stream, stages, masked ? &G : nullptr));
     return BH_OK;
 }
+}  // namespace bh
+
+extern "C" {
 
 // ---- single-model drop-ins ------------------------------------------------------------------
 namespace {

@@ -22,7 +22,15 @@
 
 namespace bh {   // capi.hip
 int fail_arg_(const char *what); int fail_hip_(int e, const char *what);
-int check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool zr); }
+int check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool zr);
+int like_gaps_derive(const char *who, int nsets, int set_stride, int ntargets, const bh_like_target *targets,
+                     const unsigned char *set_present, std::vector<int> &tables, bool *any_gap);
+int likelihood_sets_(int stages, int B, int ntargets, const bh_like_target *targets, const double *out, int out_stride,
+                     const int *err, int nflags, int nsets, const int *obs_id, const double *yobs, int set_stride,
+                     const double *set_scale, const double *set_logdet, const double *noise, const double *aux,
+                     double *logL, double *misfits, void *workspace, size_t workspace_bytes,
+                     const unsigned char *set_present, void *gaps_workspace, size_t gaps_workspace_bytes,
+                     const int *gap_cols, const int *gap_cnt, void *stream); }
 extern "C" const char *bh_last_error(void);
 
 namespace {
@@ -98,6 +106,9 @@ struct bh_eval_plan {
     double *set_scale = nullptr, *set_logdet = nullptr;
     std::vector<int> set_of_chain;
     double *rf_set_p = nullptr;   // [nrf][nsets] ray parameters per set (bh_eval_set_rf_slowness), or null: rf[i].p
+    int *gaps = nullptr;          // [nsets][row] columns of the kept samples, then [nsets][T] their counts
+                                  // (bh_eval_set_gaps; like_core.h), or null: no set has a gap
+    bool gaps_set = false;        // bh_eval_set_gaps has been called (a table without a gap leaves `gaps` null)
     bool submitted = false;       // a batch has been submitted: the observations are fixed from then on
     int last_count = 0;           // models of the submission `done` belongs to (set once `done` is recorded)
     bool failed = false;          // the last submission returned an error: nothing to wait for, no results
@@ -110,7 +121,7 @@ static void plan_free(bh_eval_plan *p)
     (void)hipSetDevice(p->dev);
     if (p->st) (void)hipStreamSynchronize(p->st);
     if (p->side) (void)hipStreamSynchronize(p->side);
-    void *dptr[] = {p->dblock, p->periods, p->obsx, p->yobs, p->aux, p->set_scale, p->set_logdet, p->rf_set_p, p->out, p->dres, p->err, p->keys,
+    void *dptr[] = {p->dblock, p->periods, p->obsx, p->yobs, p->aux, p->set_scale, p->set_logdet, p->rf_set_p, p->gaps, p->out, p->dres, p->err, p->keys,
                     p->keys_out, p->iota, p->order, p->sort_tmp, p->like_ws, p->swd_ws};
     for (void *d : dptr)
         if (d) (void)hipFree(d);
@@ -398,18 +409,20 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
     // third of a millisecond for the OTHER chain group's teams to drain (rocprofv3 of a 4 096-chain pool: 0.31 ms per
     // call where it takes 0.04 ms alone, 22 % of the kernel time).
     const bool staged = overlap && p->gauss_on_side;
-    if (staged && (rc = bh_likelihood_sets(BH_LIKE_STAGE_GAUSS, count, T, p->like.data(), p->out, p->row, p->err, p->nflags,
-                                           p->nsets, dset, p->yobs, p->row, p->set_scale, p->set_logdet, dnoise, p->aux, logL,
-                                           mis, p->like_ws, p->like_bytes, rst)))
+    const int *gcols = p->gaps, *gcnt = p->gaps ? p->gaps + (size_t)p->nsets * p->row : nullptr;
+    if (staged && (rc = bh::likelihood_sets_(BH_LIKE_STAGE_GAUSS, count, T, p->like.data(), p->out, p->row, p->err, p->nflags,
+                                             p->nsets, dset, p->yobs, p->row, p->set_scale, p->set_logdet, dnoise, p->aux,
+                                             logL, mis, p->like_ws, p->like_bytes, nullptr, nullptr, 0, gcols, gcnt, rst)))
         return rc;
     if (overlap) {
         EP_HIP(hipEventRecord(p->join, p->side));
         EP_HIP(hipStreamWaitEvent(p->st, p->join, 0));
         *forked = false;                  // joined
     }
-    if ((rc = bh_likelihood_sets(staged ? BH_LIKE_STAGE_REST : (BH_LIKE_STAGE_GAUSS | BH_LIKE_STAGE_REST), count, T,
-                                 p->like.data(), p->out, p->row, p->err, p->nflags, p->nsets, dset, p->yobs, p->row,
-                                 p->set_scale, p->set_logdet, dnoise, p->aux, logL, mis, p->like_ws, p->like_bytes, p->st)))
+    if ((rc = bh::likelihood_sets_(staged ? BH_LIKE_STAGE_REST : (BH_LIKE_STAGE_GAUSS | BH_LIKE_STAGE_REST), count, T,
+                                   p->like.data(), p->out, p->row, p->err, p->nflags, p->nsets, dset, p->yobs, p->row,
+                                   p->set_scale, p->set_logdet, dnoise, p->aux, logL, mis, p->like_ws, p->like_bytes,
+                                   nullptr, nullptr, 0, gcols, gcnt, p->st)))
         return rc;
     // results: [count] logL then [count][T+1] misfits, contiguous on both sides
     EP_HIP(hipMemcpyAsync(p->hres, p->dres, (size_t)count * (T + 2) * sizeof(double), hipMemcpyDeviceToHost, p->st));
@@ -506,6 +519,35 @@ int bh_eval_set_rf_slowness(bh_eval_plan *p, int nsets, const double *table)
         return rc;
     }
     p->rf_set_p = d;
+    return BH_OK;
+}
+
+int bh_eval_set_gaps(bh_eval_plan *p, int nsets, const unsigned char *set_present)
+{
+    if (nsets < 1) return bh::fail_arg_("bh_eval_set_gaps: nsets < 1");
+    if (!set_present) return bh::fail_arg_("bh_eval_set_gaps: NULL pointer (set_present)");
+    if (!p) return bh::fail_arg_("plan is NULL");
+    if (p->submitted) return bh::fail_arg_("bh_eval_set_gaps: called after bh_eval_submit");
+    if (p->gaps_set) return bh::fail_arg_("bh_eval_set_gaps: the plan has its gaps already");
+    if (p->set_of_chain.empty())
+        return bh::fail_arg_("bh_eval_set_gaps: call bh_eval_set_observations first (it tells the plan the set of every chain)");
+    if (nsets != p->nsets)
+        return bh::fail_arg_(("bh_eval_set_gaps: nsets = " + std::to_string(nsets) + ", but bh_eval_set_observations gave the plan " +
+                              std::to_string(p->nsets) + " sets").c_str());
+    std::vector<int> tables;
+    bool any_gap = false;
+    if (int rc = bh::like_gaps_derive("bh_eval_set_gaps", nsets, p->row, p->T, p->like.data(), set_present, tables, &any_gap))
+        return rc;
+    if (any_gap) {
+        EP_HIP(hipSetDevice(p->dev));
+        int *d = nullptr;
+        if (int rc = upload(&d, tables.data(), tables.size())) {
+            if (d) (void)hipFree(d);
+            return rc;
+        }
+        p->gaps = d;
+    }
+    p->gaps_set = true;
     return BH_OK;
 }
 

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "kernels.h"
+#include "like_core.h"
 
 namespace bh {
 
@@ -280,6 +281,148 @@ __global__ __launch_bounds__(LIKE_T) void like_kernel(LikeArgs A)
     }
 }
 
+// like_kernel for observation sets with data gaps (like_core.h): a row's residual vector of a target is the n'
+// samples its set has, gathered through the set's column list while it is staged into LDS, and everything behind
+// the staging runs on n' -- lane i on elements i, i + 64, ... of the compacted vector, so a row's sums have the order,
+// and the bits, of like_kernel on the kept columns alone.  A kernel of its own and not a template parameter of
+// like_kernel: calls without gaps keep like_kernel's code object instruction for instruction (as a template its
+// unmasked instantiation came out with another register allocation and schedule).  The dense arms are like_kernel's:
+// a dense-Gaussian target has no gaps (its n' is n).
+__global__ __launch_bounds__(LIKE_T) void like_gaps_kernel(LikeArgs A, LikeGaps G)
+{
+    extern __shared__ double sm[];          // [LIKE_M][nmax] residuals, then [LIKE_M][4] partials
+    __shared__ double red[LIKE_M][LIKE_T / 64][2];
+    __shared__ double acc_logl[LIKE_M];
+    __shared__ double acc_mis[LIKE_M];
+    __shared__ int bad[LIKE_M];
+    __shared__ int setof[LIKE_M];           // the models' observation sets
+    __shared__ int npts[BH_NT][LIKE_M];     // the models' sample counts n' per target
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b0 = blockIdx.x * LIKE_M;
+    const int Mb = min(LIKE_M, A.B - b0);
+    const int NW = LIKE_T / 64;
+
+    if (tid < LIKE_M) {
+        acc_logl[tid] = 0.0;
+        acc_mis[tid] = 0.0;
+        int flag = 0;
+        if (tid < Mb)
+            for (int f = 0; f < A.nflags; f++) flag |= A.err[(long)(b0 + tid) * A.nflags + f];
+        const int set = tid < Mb ? like_set_of(A, b0 + tid) : 0;
+        bad[tid] = flag | (set < 0);
+        setof[tid] = max(set, 0);
+        for (int t = 0; t < A.ntargets; t++) npts[t][tid] = G.cnt[(long)max(set, 0) * A.ntargets + t];
+    }
+    __syncthreads();
+
+    for (int t = 0; t < A.ntargets; t++) {
+        const LikeTargetDev tg = A.tg[t];
+        const int n = tg.n;
+        // residuals d = ymod - yobs of the workgroup's models -> LDS (coalesced row reads)
+        for (int idx = tid; idx < Mb * n; idx += LIKE_T) {
+            int m = idx / n, i = idx - m * n;
+            if (i >= npts[t][m]) continue;              // a row's LDS block keeps its pitch n; n' of it are used
+            sm[m * n + i] = like_residual<true>(A.out + (long)(b0 + m) * A.out_stride + tg.off,
+                                                A.yobs + (long)setof[m] * A.set_stride + tg.off,
+                                                G.cols + (long)setof[m] * A.set_stride + tg.off, i);
+        }
+        __syncthreads();
+
+        if (tg.cov == 3 && A.gq) {
+            // precomputed on the matrix cores (gauss_q_kernel)
+            if (tid < LIKE_M) {
+                for (int w = 0; w < NW; w++) { red[tid][w][0] = 0.0; red[tid][w][1] = 0.0; }
+                if (tid < Mb) {                     // the partials of the target's column-tile groups, in group order
+                    const double *g = A.gq + ((long)t * A.B + (b0 + tid)) * 2 * A.gq_groups;
+                    double qq = 0.0, ss = 0.0;
+                    for (int k = 0; k < gq_groups_of(n); k++) { qq += g[2 * k]; ss += g[2 * k + 1]; }
+                    red[tid][0][1] = qq;
+                    red[tid][0][0] = ss;
+                }
+            }
+        } else if (tg.cov == 3) {
+            // q_m = d_m^T R^-1 d_m : thread i owns row i for all LIKE_M models
+            const double *R = A.aux + tg.aux_off;
+            double s2[LIKE_M], q[LIKE_M];
+#pragma unroll
+            for (int m = 0; m < LIKE_M; m++) { s2[m] = 0.0; q[m] = 0.0; }
+            for (int i = tid; i < n; i += LIKE_T) {
+                double rd[LIKE_M];
+#pragma unroll
+                for (int m = 0; m < LIKE_M; m++) rd[m] = 0.0;
+                const double *Ri = R + (long)i * n;
+                for (int j = 0; j < n; j++) {
+                    double r = Ri[j];
+#pragma unroll
+                    for (int m = 0; m < LIKE_M; m++) rd[m] += r * sm[m * n + j];
+                }
+#pragma unroll
+                for (int m = 0; m < LIKE_M; m++) {
+                    double d = sm[m * n + i];
+                    q[m] += d * rd[m];
+                    s2[m] += d * d;
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < LIKE_M; m++) {
+                double a = wave_sum(s2[m]), c = wave_sum(q[m]);
+                if (lane == 0) { red[m][wv][0] = a; red[m][wv][1] = c; }
+            }
+        } else {
+            // closed forms: wave w handles models w, w+NW, ...
+            for (int m = wv; m < LIKE_M; m += NW) {
+                double s2 = 0.0, q = 0.0;
+                if (m < Mb) {
+                    const double *d = sm + m * n;
+                    const int nk = npts[t][m];
+                    if (tg.cov == 0) {
+                        like_nocorr_lane(d, nk, lane, s2, q);
+                    } else if (tg.cov == 1) {
+                        const double *se = A.set_scale ? A.set_scale + (long)setof[m] * A.set_stride + tg.off : A.aux + tg.aux_off;
+                        like_scaled_lane<true>(d, nk, lane, se, G.cols + (long)setof[m] * A.set_stride + tg.off, s2, q);
+                    } else {
+                        double r = A.noise[(long)(b0 + m) * 2 * A.ntargets + 2 * t];
+                        like_exp_lane(d, nk, lane, r, s2, q);
+                    }
+                }
+                s2 = wave_sum(s2);
+                q = wave_sum(q);
+                if (lane == 0) {
+                    for (int w = 0; w < NW; w++) { red[m][w][0] = 0.0; red[m][w][1] = 0.0; }
+                    red[m][0][0] = s2;
+                    red[m][0][1] = q;
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < Mb) {
+            const int m = tid;
+            double s2 = 0.0, q = 0.0;
+            for (int w = 0; w < NW; w++) { s2 += red[m][w][0]; q += red[m][w][1]; }
+            const double corr = A.noise[(long)(b0 + m) * 2 * A.ntargets + 2 * t];
+            const double sigma = A.noise[(long)(b0 + m) * 2 * A.ntargets + 2 * t + 1];
+            double logl, rms;                   // over the row's n' samples (a dense-Gaussian target has no gaps: n)
+            like_target_part(tg.cov, npts[t][m], s2, q, corr, sigma,
+                             (tg.cov == 1 && A.set_logdet) ? A.set_logdet[(long)setof[m] * A.ntargets + t] : tg.logdet_extra,
+                             logl, rms);
+            acc_logl[m] += logl;
+            acc_mis[m] += rms;
+            A.misfits[(long)(b0 + m) * (A.ntargets + 1) + t] = bad[m] ? 1e15 : rms;
+        }
+        __syncthreads();
+    }
+    if (tid < Mb) {
+        const int m = tid;
+        if (bad[m]) {   // src/Targets.py:325-328
+            A.logL[b0 + m] = -1e15;
+            for (int t = 0; t <= A.ntargets; t++) A.misfits[(long)(b0 + m) * (A.ntargets + 1) + t] = 1e15;
+        } else {
+            A.logL[b0 + m] = acc_logl[m];
+            A.misfits[(long)(b0 + m) * (A.ntargets + 1) + A.ntargets] = acc_mis[m];
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Voronoi nuclei -> layers (src/Models.py:26-52) + prior checks (src/SingleChain.py:330-392).
 // One lane per proposal; every operation is the reference's IEEE operation, so h, vp, rho are
@@ -457,7 +600,8 @@ hipError_t launch_voronoi(const VoronoiArgs &A, hipStream_t stream)
 
 // stages: 1 = the dense Gaussian products (they need only the rows of their own targets: an evaluation plan runs
 // them behind the receiver-function kernel on its side stream, beside the dispersion searches), 2 = like_kernel
-hipError_t launch_like(const LikeArgs &A, int nmax, hipStream_t stream, int stages)
+// gaps: the tables of observation sets with data gaps (like_core.h), or null: like_kernel as it always was
+hipError_t launch_like(const LikeArgs &A, int nmax, hipStream_t stream, int stages, const LikeGaps *gaps)
 {
     if (A.gq && (stages & 1)) {   // dense Gaussian targets first, on the FP64 MFMA
         for (int t = 0; t < A.ntargets; t++)
@@ -485,20 +629,22 @@ hipError_t launch_like(const LikeArgs &A, int nmax, hipStream_t stream, int stag
     }
     if (!(stages & 2)) return hipGetLastError();
     size_t lds = (size_t)LIKE_M * nmax * sizeof(double);
-    static size_t lds_set[16] = {0};
+    static size_t lds_set[2][16] = {{0}, {0}};   // [masked form][device]
+    const void *fn = gaps ? (const void *)like_gaps_kernel : (const void *)like_kernel;
     if (lds > 48 * 1024) {
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
         dev &= 15;
-        if (lds > lds_set[dev]) {
-            e = hipFuncSetAttribute((const void *)like_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (lds > lds_set[gaps != nullptr][dev]) {
+            e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
-            lds_set[dev] = lds;
+            lds_set[gaps != nullptr][dev] = lds;
         }
     }
     dim3 grid((A.B + LIKE_M - 1) / LIKE_M);
-    hipLaunchKernelGGL(like_kernel, grid, dim3(LIKE_T), lds, stream, A);
+    if (gaps) hipLaunchKernelGGL(like_gaps_kernel, grid, dim3(LIKE_T), lds, stream, A, *gaps);
+    else hipLaunchKernelGGL(like_kernel, grid, dim3(LIKE_T), lds, stream, A);
     return hipGetLastError();
 }
 

@@ -32,6 +32,8 @@ class EvalPlan(object):
         lay, desc = layout['layout'], layout['desc']
         self.rows, self.Lmax, self.T, self.row = int(max_models), int(Lmax), len(desc), int(lay.row)
         self.nrf = len(lay.rf)
+        # a layout whose targets have data gaps must not run before the plan has them (set_gaps)
+        self._gaps_due = 'present' in layout and not np.asarray(layout['present']).all()
         interp = lay.interp([sp.obsx.ctypes.data for _, _, _, sp in lay.resampled])   # (copied by bh_eval_create)
         self.handle = C.c_void_p()
         _lib.check(self.lib.bh_eval_create(
@@ -53,6 +55,9 @@ class EvalPlan(object):
         return self.handle
 
     def submit(self, count):
+        if self._gaps_due:
+            raise _lib.BayHunterAmdError("the plan's targets have data gaps: give it every set's observations and the table "
+                                         "of present samples first (set_observations, set_gaps)")
         _lib.check(self.lib.bh_eval_submit(self._live(), int(count)))
 
     def set_observations(self, yobs, set_of_chain, set_scale=None, set_logdet=None):
@@ -82,6 +87,18 @@ class EvalPlan(object):
         if p.ndim != 2 or p.shape[1] != self.nrf:
             raise ValueError("p: one row of %d ray parameters (one per receiver-function target) per observation set" % self.nrf)
         _lib.check(self.lib.bh_eval_set_rf_slowness(self._live(), p.shape[0], p.ctypes.data))
+
+    def set_gaps(self, present):
+        """Data gaps of the observation sets (bh_eval_set_gaps): present[nsets, row], nonzero where a set has the
+        sample, nsets that of `set_observations`, which comes first (with set_scale / set_logdet computed over the kept
+        samples and a finite placeholder in yobs at a gap).  Once, before the first submit.  The likelihood of a row
+        then leaves out the samples its set lacks, as if those lines had been deleted from the station's data file;
+        a dense-Gaussian target with a gap and a target without a kept sample are refused."""
+        present = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+        if present.ndim != 2 or present.shape[1] != self.row:
+            raise ValueError("present: one row of %d bytes per observation set" % self.row)
+        _lib.check(self.lib.bh_eval_set_gaps(self._live(), present.shape[0], present.ctypes.data))
+        self._gaps_due = False
 
     def set_concurrency(self, plans_in_flight):
         """How many plans take turns on the device (the chain groups of a pool): the library chooses its kernel

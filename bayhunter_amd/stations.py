@@ -99,15 +99,55 @@ def check_stations(names, joints, per_station=()):
                 raise ValueError(what + "(%s) fixed noise correlation matrix" % a.ref)
 
 
-def observation_tables(joints):
+MISSING = ('refuse', 'mask')
+
+
+def find_gaps(names, joints, missing='refuse'):
+    """The samples every station lacks, after set_target_covariance: a non-finite obsdata.y, or a non-finite yerr on a
+    target that uses it (the yerr-scaled covariance model).  'refuse': ValueError naming station, target and the
+    first such sample.  'mask': they become the station's gaps (SingleTarget.present; None for a target without
+    any); ValueError naming station and target for a gap in a target with the dense Gaussian model (its R^-1 belongs
+    to one n and to contiguous samples) and for a target without a sample left.  -> number of missing samples."""
+    if missing not in MISSING:
+        raise ValueError("missing=%r: 'refuse' or 'mask'" % (missing,))
+    total = 0
+    for name, joint in zip(names, joints):
+        for t, tg in enumerate(joint.targets):
+            ybad = ~np.isfinite(np.asarray(tg.obsdata.y, dtype=np.float64))
+            bad = ybad
+            if tg.covmodel == _lib.COV_NOCORR_SCALED:
+                bad = ybad | ~np.isfinite(np.asarray(tg.obsdata.yerr, dtype=np.float64))
+            tg.present = None
+            if not bad.any():
+                continue
+            who = "station %r, target %d (%s): " % (name, t, tg.ref)
+            if missing == 'refuse':
+                i = int(np.argmax(bad))
+                raise ValueError(who + "%s is not finite at sample %d (x = %g); StationPool(missing='mask') treats such "
+                                 "samples as gaps of the station" % ('y' if ybad[i] else 'yerr', i, np.asarray(tg.obsdata.x)[i]))
+            if tg.covmodel == _lib.COV_GAUSS:
+                raise ValueError(who + "%d samples are missing, but a target with the dense Gaussian covariance model "
+                                 "cannot have gaps (its fixed R^-1 belongs to one n and to contiguous samples)" % bad.sum())
+            if bad.all():
+                raise ValueError(who + "no sample is left; stations that lack a whole target are not supported")
+            tg.present = ~bad
+            total += int(bad.sum())
+        joint._batch = None
+    return total
+
+
+def observation_tables(joints, present=False):
     """yobs[nsets, row], set_scale[nsets, row], set_logdet[nsets, ntargets] of stations that passed check_stations, from
     each station's own batch_layout() (so every number is the one a single-station plan uploads); the two tables of
-    the yerr-scaled targets are None when no target has that covariance model."""
-    yobs, scale, logdet = [], [], []
+    the yerr-scaled targets are None when no target has that covariance model.  Data gaps (find_gaps): the scaled
+    errors and their log-product are taken over a station's kept samples and yobs holds a finite placeholder at a
+    gap; present=True appends present[nsets, row] (uint8, 0 at a gap), or None when no station has one."""
+    yobs, scale, logdet, have = [], [], [], []
     for joint in joints:                    # one layout at a time: each carries its dense R^-1 (323 KB at n = 201)
         bl = joint.batch_layout()
         desc, row = bl['desc'], bl['layout'].row
         yobs.append(bl['yobs'])
+        have.append(bl['present'])
         sc, ld = np.ones(row), np.zeros(len(desc))
         for t in range(len(desc)):
             if desc[t].cov == _lib.COV_NOCORR_SCALED:
@@ -116,9 +156,11 @@ def observation_tables(joints):
                 ld[t] = d.logdet_extra
         scale.append(sc)
         logdet.append(ld)
+    tabs = (np.stack(yobs), np.stack(scale), np.stack(logdet))
     if not any(d.cov == _lib.COV_NOCORR_SCALED for d in desc):
-        return np.stack(yobs), None, None
-    return np.stack(yobs), np.stack(scale), np.stack(logdet)
+        tabs = (tabs[0], None, None)
+    have = np.stack(have)
+    return tabs + ((None if have.all() else have),) if present else tabs
 
 
 def rf_slowness_table(joints):
@@ -143,11 +185,13 @@ class StationGpuEvaluator(GpuEvaluator):
 
     def buffers(self, rows, Lmax, ntargets, chains):
         if self._tables is None:            # (after the pool has chosen the covariance models)
-            self._tables = observation_tables(self.joints)
+            self._tables = observation_tables(self.joints, present=True)
         packed, nlay, noise, chain = GpuEvaluator.buffers(self, rows, Lmax, ntargets)
-        yobs, scale, logdet = self._tables
+        yobs, scale, logdet, present = self._tables
         plan = self._plans[packed.ctypes.data]
         plan.set_observations(yobs, self.station_of_chain[chains[0]:chains[1]], scale, logdet)
+        if present is not None:
+            plan.set_gaps(present)
         if 'p' in self.per_station and plan.nrf:
             plan.set_rf_slowness(rf_slowness_table(self.joints))
         return packed, nlay, noise, chain
@@ -227,6 +271,22 @@ class StationPool(object):
                         for itself (the ray parameter; module docstring).  Without it stations that differ in `p`
                         are refused like any other difference; any other name: ValueError listing what is supported.
                         CPU evaluators get each row's station and use that station's own plugin as they always did
+    missing             'refuse' (default): a non-finite obsdata.y, or a non-finite yerr on a target that uses it, is a
+                        ValueError naming station, target and sample.  'mask': those samples are the station's GAPS -- a
+                        map node without long periods, a period that failed quality control.  Every row is still
+                        modelled on the pool's axis; the likelihood leaves out what the row's station lacks and values
+                        the target as the reference values it when those lines have been deleted from the data file
+                        (n' kept samples: rms, 2 n' log sigma, n' log 2 pi; scaled_err = yerr / min over the kept
+                        samples; the exponential law on the compacted vector, kept neighbours being neighbours).
+                        Refused: a gap in a target with the dense Gaussian model, and a target without a sample left.
+                        Two consequences of modelling on the pool's axis: (1) a kept value is not bit for bit what a
+                        run on the shortened axis gives -- the root search of period k starts from the root of period
+                        k - 1, so the two differ at its stopping tolerance, 1e-6 relative; (2) a model whose
+                        dispersion search fails at a period the station does not use still fails for that station.
+                        (A yerr with a NaN is dropped as a whole by ObservedData, as in the reference: give a gap any
+                        positive yerr, or inf.)  station(s).datafits() reports the observed value and the residual of
+                        a gap as NaN; CPU evaluators find the gaps in SingleTarget.present, which JointTarget.evaluate
+                        honours
     groups, nthreads, nmodels, lookahead   as for ChainPool
     shard               not supported yet (stations would have to be sharded whole): ValueError
 
@@ -234,8 +294,11 @@ class StationPool(object):
 
     def __init__(self, stations, initparams=None, modelpriors=None, chains_per_station=None, random_seeds=None,
                  seeds=None, evaluator=None, groups=None, nthreads=None, shard=None, nmodels=None, lookahead=None,
-                 device=None, per_station=()):
+                 device=None, per_station=(), missing='refuse'):
         self.per_station = check_per_station(per_station)
+        if missing not in MISSING:
+            raise ValueError("missing=%r: 'refuse' or 'mask'" % (missing,))
+        self.missing = missing
         if shard is not None:
             raise ValueError("StationPool does not take shard=(rank, world) yet: give every rank a StationPool of its "
                              "own stations")
@@ -290,6 +353,7 @@ class StationPool(object):
             joint.set_target_covariance(corrfix, corr, rcond)
         first.set_target_covariance(corrfix, corr, rcond)
         check_stations(self.names, self.stations, self.per_station)
+        self.ngaps = find_gaps(self.names, self.stations, missing)
         if evaluator is None:
             evaluator = StationGpuEvaluator(self.stations, self.station_of_chain, device, self.per_station)
         elif not hasattr(evaluator, 'submit') and _takes_station(evaluator):

@@ -147,6 +147,10 @@ class SingleTarget(object):
         self.valuation = Valuation()
         self.covmodel = _lib.COV_NOCORR
         self.get_covariance = self.valuation.get_covariance_nocorr
+        # Data gaps (stations.StationPool(missing='mask')): a boolean array, True where this station has the sample,
+        # or None: all of them.  A target with gaps is valued as the reference values it when those lines have been
+        # deleted from the data file -- every figure below is taken over the kept samples, compacted.
+        self.present = None
         logger.info("Initiated target: %s (ref: %s)" % (self.__class__.__name__, self.ref))
 
     def update_plugin(self, plugin):
@@ -157,22 +161,27 @@ class SingleTarget(object):
         return (type(mx) == np.ndarray and len(self.obsdata.x) == len(mx)
                 and bool(np.sum(self.obsdata.x - mx) <= 1e-5) and len(self.obsdata.y) == len(my))
 
+    def kept(self, values):
+        """`values` (one per sample) at the samples this station has."""
+        return values if self.present is None else np.asarray(values)[self.present]
+
     def calc_misfit(self):
-        self.valuation.misfit = self.valuation.get_rms(self.obsdata.y, self.moddata.y) \
+        self.valuation.misfit = self.valuation.get_rms(self.kept(self.obsdata.y), self.kept(self.moddata.y)) \
             if self._moddata_valid() else 1e15
 
     def calc_likelihood(self, c_inv, logc_det):
         self.valuation.likelihood = self.valuation.get_likelihood(
-            self.obsdata.y, self.moddata.y, c_inv, logc_det) if self._moddata_valid() else -1e15
+            self.kept(self.obsdata.y), self.kept(self.moddata.y), c_inv, logc_det) if self._moddata_valid() else -1e15
 
-    # closed-form Mahalanobis distance + log-determinant for the selected covariance model
+    # closed-form Mahalanobis distance + log-determinant for the selected covariance model; ydiff: the kept samples
     def quadratic_form(self, ydiff, corr, sigma):
         n = ydiff.size
         logdet = (2 * n) * np.log(sigma)
         if self.covmodel == _lib.COV_NOCORR:
             return ydiff.dot(ydiff) / sigma**2, logdet
         if self.covmodel == _lib.COV_NOCORR_SCALED:
-            se = self.obsdata.yerr / self.obsdata.yerr.min()
+            yerr = self.kept(self.obsdata.yerr)
+            se = yerr / yerr.min()
             return np.sum(ydiff**2 / se) / sigma**2, logdet + np.log(np.prod(se))
         if self.covmodel == _lib.COV_EXP:
             w = np.full(n, 1.0 + corr**2)
@@ -247,7 +256,7 @@ class JointTarget(object):
                 return
             target.calc_misfit()
             corr, sigma = noise[2 * n:2 * n + 2]
-            ydiff = target.moddata.y - target.obsdata.y
+            ydiff = target.kept(target.moddata.y - target.obsdata.y)
             madist, logc_det = target.quadratic_form(ydiff, corr, sigma)
             logL += -0.5 * (ydiff.size * LOG_2PI + logc_det) - madist / 2.
         self.proposallikelihood = logL
@@ -257,7 +266,9 @@ class JointTarget(object):
     def batch_layout(self):
         """What a batched evaluation needs besides device memory (no torch, no device): the row layout of
         the forward kernels (layout.RowLayout), the likelihood descriptors, and the observed data / auxiliary
-        arrays (scaled errors, dense R^-1) as host arrays."""
+        arrays (scaled errors, dense R^-1) as host arrays.  Data gaps (SingleTarget.present): `present[row]` holds 0 at
+        a missing sample, yobs a finite placeholder (0) and the scaled errors, taken over the kept samples, 1 -- the
+        table an evaluation plan takes in set_gaps.  Nothing non-finite goes to the device on account of a gap."""
         from .layout import RfSpec, RowLayout, SwdSpec
         swd, rf, order = [], [], []
         for t in self.targets:
@@ -274,15 +285,22 @@ class JointTarget(object):
                 raise TypeError("evaluate_batch supports the built-in SurfDisp / RFminiModRF plugins")
         lay = RowLayout(swd, rf)
         slices = [lay.slices[i if kind == 'swd' else len(swd) + i] for kind, i in order]
-        yobs = np.zeros(lay.row)
+        yobs, present = np.zeros(lay.row), np.ones(lay.row, dtype=np.uint8)
         aux, desc = [], (_lib.LikeTarget * self.ntargets)()
         aux_off = 0
         for n, (t, sl) in enumerate(zip(self.targets, slices)):
-            yobs[sl] = t.obsdata.y
+            k = t.present
+            yobs[sl] = t.obsdata.y if k is None else np.where(k, t.obsdata.y, 0.0)
+            if k is not None:
+                present[sl] = k
             extra, a = 0.0, None
-            if t.covmodel == _lib.COV_NOCORR_SCALED:
+            if t.covmodel == _lib.COV_NOCORR_SCALED and k is None:
                 a = t.obsdata.yerr / t.obsdata.yerr.min()
                 extra = float(np.log(np.prod(a)))
+            elif t.covmodel == _lib.COV_NOCORR_SCALED:
+                a = np.ones(k.size)
+                a[k] = t.obsdata.yerr[k] / t.obsdata.yerr[k].min()
+                extra = float(np.log(np.prod(a[k])))
             elif t.covmodel == _lib.COV_GAUSS:
                 a = np.ascontiguousarray(t.valuation.corr_inv, dtype=np.float64).ravel()
                 extra = float(t.valuation.logcorr_det)
@@ -290,13 +308,16 @@ class JointTarget(object):
             if a is not None:
                 aux.append(np.asarray(a, dtype=np.float64))
                 aux_off += aux[-1].size
-        return dict(layout=lay, desc=desc, nflags=max(1, len(swd)), yobs=yobs,
+        return dict(layout=lay, desc=desc, nflags=max(1, len(swd)), yobs=yobs, present=present,
                     aux=np.ascontiguousarray(np.concatenate(aux) if aux else np.zeros(1), dtype=np.float64))
 
     def _build_batch(self):
         import torch
         from .engine import ForwardEngine
         bl = self.batch_layout()
+        if not bl['present'].all():
+            raise ValueError("a target with data gaps is evaluated by a StationPool(missing='mask'), whose evaluation "
+                             "plans carry the gaps (EvalPlan.set_gaps)")
         eng = ForwardEngine(swd=bl['layout'].swd, rf=bl['layout'].rf)
         dev = eng.device
         self._batch = dict(eng=eng, desc=bl['desc'], nflags=bl['nflags'],

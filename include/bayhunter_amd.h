@@ -268,6 +268,36 @@ int bh_likelihood_sets(int stages, int B, int ntargets, const bh_like_target *ta
                        const double *aux, double *logL, double *misfits, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* Observation sets with DATA GAPS: a set (station) may lack samples of a target -- a map node without long periods,
+ * a period that failed quality control.  Every row is still modelled on the targets' common axes; the likelihood
+ * leaves out the samples a row's set does not have, and values such a target as the reference's Valuation
+ * (src/Targets.py:99-183) values it when those lines have been deleted from the data file: the residual vector is
+ * the n' kept samples in order, compacted; rms, 2 n log sigma and n log 2 pi take n'; the exponential law's tridiagonal
+ * form is built on the compacted vector (kept neighbours are neighbours, both ends have diagonal 1,
+ * (n' - 1) log(1 - r^2)).
+ *   set_present[nsets][set_stride]  HOST bytes, != 0: the set has this sample (only the targets' columns are read)
+ *   gaps_workspace                  bh_likelihood_gaps_workspace_bytes(nsets, set_stride, ntargets) bytes of DEVICE
+ *                                   memory for the tables derived from set_present (per set and target the columns of
+ *                                   the kept samples, in order, and their count); BH_ERR_WORKSPACE when missing
+ * set_scale and set_logdet are the caller's, computed over the KEPT samples (scaled_err = yerr / min of the kept yerr,
+ * in the targets' own columns; log of the product over the kept samples); yobs may hold any finite value at a gap.
+ * All other arguments are bh_likelihood_sets', and all are checked before the first launch; refused besides:
+ * a BH_COV_GAUSS target with a gap in any set (its dense R^-1 belongs to one n and to contiguous samples) and a
+ * target without a kept sample in some set, the message naming set and target.
+ * A row's result is bit for bit what bh_likelihood_stage gives when its target table, that row of `out` and yobs
+ * hold the kept columns only.  set_present = NULL is bh_likelihood_sets; so is a set_present without a gap (the
+ * same kernel on the same arguments).  With gaps, the rows of a set that has none go through the masked kernel with
+ * an identity column list: the same operations on the same values, the same bits.
+ * The call derives the tables and copies them to gaps_workspace on `stream`, and waits for that copy: a caller who
+ * evaluates batch after batch against the same gaps gives them to an evaluation plan once (bh_eval_set_gaps). */
+size_t bh_likelihood_gaps_workspace_bytes(int nsets, int set_stride, int ntargets);
+int bh_likelihood_sets_gaps(int stages, int B, int ntargets, const bh_like_target *targets, const double *out,
+                            int out_stride, const int *err, int nflags, int nsets, const int *obs_id, const double *yobs,
+                            int set_stride, const double *set_scale, const double *set_logdet, const double *noise,
+                            const double *aux, double *logL, double *misfits, void *workspace, size_t workspace_bytes,
+                            const unsigned char *set_present, void *gaps_workspace, size_t gaps_workspace_bytes,
+                            void *stream);
+
 /* ---- single-model drop-ins (host pointers, synchronous) --------------------------------- */
 /* Same argument list as the f2py wrapper of `subroutine surfdisp96`; model arrays are real*4 with
  * at least nlayer valid entries, t/cg real*8 with at least kmax entries.  *err as the reference. */
@@ -495,6 +525,12 @@ int  bh_eval_set_observations(bh_eval_plan *plan, int nsets, const double *yobs,
  * belongs to the plan and goes with it in bh_eval_destroy.  What else a receiver function depends on (gauss, nsv,
  * the time axis) and the periods of a dispersion target stay per plan. */
 int  bh_eval_set_rf_slowness(bh_eval_plan *plan, int nsets, const double *p);
+/* Data gaps for a plan with observation sets (bh_likelihood_sets_gaps): set_present[nsets][row], HOST bytes, != 0:
+ * the set has this sample.  Callable once, after bh_eval_set_observations (whose nsets it must equal; its set_scale
+ * and set_logdet are computed over the kept samples) and before the first bh_eval_submit.  Refused, before any device
+ * call: a BH_COV_GAUSS target with a gap and a target without a kept sample in some set.  The derived tables belong
+ * to the plan and go with it in bh_eval_destroy; a set_present without a gap leaves the plan as it was. */
+int  bh_eval_set_gaps(bh_eval_plan *plan, int nsets, const unsigned char *set_present);
 /* How many plans take turns on the device (a pool's chain groups; default 1): passed on as bh_swd_hint's second
  * argument with every submission. */
 int  bh_eval_set_concurrency(bh_eval_plan *plan, int plans_in_flight);

@@ -9,11 +9,18 @@ vp/vs and noise, like tools/chain_bench.py).  For S stations of c chains each, t
                the output: "scaled": true)
 
     python tools/station_bench.py [--modes stations,onepool,singles] [--repeats 5] [--sample 16] [--root DIR]
-                                  [--vary-p LO HI] [--out FILE.jsonl] [SxC ...]   (default 64x16 256x16 1024x16 1024x4)
+                                  [--vary-p LO HI] [--gaps FRACTION] [--out FILE.jsonl] [SxC ...]
+                                  (default 64x16 256x16 1024x16 1024x4)
 
 --vary-p LO HI: every station its own receiver-function ray parameter, spread evenly over [LO, HI] s/deg; the station
 pool runs with per_station=('p',) (the per-row form of rf_kernel), the single pools each at their station's p, `onepool`
 at station 0's.
+
+--gaps FRACTION: every station but station 0 lacks that fraction of its dispersion periods (its own random draw, at
+least one period kept; NaN in obsdata.y) and the station pool runs with missing='mask' (like_gaps_kernel); `singles` are
+one-station StationPools with missing='mask', `onepool` runs on station 0, which is complete.  --gaps 0 takes the
+same code path with no gap anywhere: the full-mask cost, to set against a tree without the feature (--root), which
+is run without the keyword.  Every line carries the library's source hash.
 
 --posterior: instead of the three ways to run, what reading the result costs.  One finished StationPool of S x c chains
 is summarised twice: by the loop over its station views (pool.station(s).posterior(), one pair of handles per station)
@@ -44,6 +51,8 @@ def main():
     ap.add_argument('--root', default=None, help='tree whose bayhunter_amd is measured (default: this one)')
     ap.add_argument('--vary-p', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
                     help="stations with p spread evenly over [LO, HI] s/deg, pooled with per_station=('p',)")
+    ap.add_argument('--gaps', type=float, default=None, metavar='FRACTION',
+                    help="fraction of the dispersion periods missing at every station but the first; pooled with missing='mask'")
     ap.add_argument('--posterior', action='store_true',
                     help='time StationPool.posterior() against the loop over station views on one finished pool')
     ap.add_argument('--tag', default=None)
@@ -61,6 +70,10 @@ def main():
     from bayhunter_amd.chains import ChainPool
     assert os.path.abspath(os.path.dirname(os.path.dirname(bayhunter_amd.__file__))) == root
     modes = args.modes.split(',')
+    import inspect
+    from bayhunter_amd.stations import StationPool
+    mask = dict(missing='mask') if args.gaps is not None and 'missing' in inspect.signature(StationPool.__init__).parameters else {}
+    assert mask or not args.gaps, 'this tree has no StationPool(missing=...)'
     data = os.path.join(here, 'tests', 'golden', 'tutorial_observed')
     case = CASES['tutorial']
 
@@ -81,7 +94,7 @@ def main():
         if mode == 'stations':
             from bayhunter_amd.stations import StationPool
             per = dict(per_station=('p',)) if args.vary_p else {}
-            with StationPool(stations, ip, case['priors'], seeds=seeds, **per, **kw) as pool:
+            with StationPool(stations, ip, case['priors'], seeds=seeds, **per, **mask, **kw) as pool:
                 t0 = time.perf_counter()
                 pool.run()
                 return time.perf_counter() - t0, S
@@ -93,7 +106,9 @@ def main():
         k = min(S, args.sample)
         dt = 0.0
         for s in range(k):                      # construction and close() of a pool are not counted: run() only
-            with ChainPool(stations[s], ip, case['priors'], seeds=seeds[s], **kw) as pool:
+            single = StationPool(stations[s:s + 1], ip, case['priors'], seeds=seeds[s:s + 1], **mask, **kw) if args.gaps \
+                else ChainPool(stations[s], ip, case['priors'], seeds=seeds[s], **kw)
+            with single as pool:
                 t0 = time.perf_counter()
                 pool.run()
                 dt += time.perf_counter() - t0
@@ -165,6 +180,13 @@ def main():
         if args.vary_p:
             for joint, p in zip(stations, np.linspace(args.vary_p[0], args.vary_p[1], S)):
                 joint.targets[1].moddata.plugin.set_modelparams(p=float(p))
+        if args.gaps:
+            for s, joint in enumerate(stations[1:], 1):
+                y = joint.targets[0].obsdata.y.copy()
+                miss = np.random.RandomState(5000 + s).uniform(size=y.size) < args.gaps
+                miss[np.random.RandomState(7000 + s).randint(y.size)] = False
+                y[miss] = np.nan
+                joint.targets[0].obsdata.y = y
         for mode in modes:                      # first-use costs (kernel forms, helper threads, pinned buffers, the
             run(mode, S, c, 6, stations)        # set-up's factorisation) are not chain iterations
         time.sleep(0.25)                        # numpy's BLAS workers spin ~0.1 s after the set-up's factorisation
@@ -178,7 +200,8 @@ def main():
         total = S * c * (iters + iters // 2)
         for mode in modes:
             v = np.asarray(secs[mode])
-            rec = dict(bench='station_pool', tag=args.tag, vary_p=args.vary_p, mode=mode, stations=S, chains_per_station=c, chains=S * c,
+            rec = dict(bench='station_pool', tag=args.tag, src=bayhunter_amd._lib.built_hash(), vary_p=args.vary_p, gaps=args.gaps,
+                       mode=mode, stations=S, chains_per_station=c, chains=S * c,
                        iterations=iters + iters // 2, repeats=args.repeats, seconds=[round(float(x), 4) for x in v],
                        median_s=round(float(np.median(v)), 4), min_s=round(float(v.min()), 4),
                        max_s=round(float(v.max()), 4), chain_iterations_per_s=round(total / float(np.median(v))),
