@@ -31,8 +31,7 @@ namespace bh {
 // instructions of a layer step of swd_kernel).  The three-address form with the coefficient as a scalar
 // operand needs neither the copy nor the VGPRs.  An "s" operand is read from one lane, so the scalar form
 // is only taken when K is a compile-time constant after inlining (__builtin_constant_p, resolved late
-// through llvm.is.constant); anything else gets the plain builtin.  (-DBH_NO_FMA_K: always the plain
-// builtin, for A/B measurements and the bit-parity matrix.)
+// through llvm.is.constant); anything else gets the plain builtin.
 #if defined(BH_HOSTSIM)
 BH_DEV double bh_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 BH_DEV double bh_fma_k(double a, double b, double k) { return __builtin_fma(a, b, k); }
@@ -40,9 +39,6 @@ BH_DEV double bh_rint(double x) { return __builtin_rint(x); }
 BH_DEV double bh_ldexp(double x, int k) { return __builtin_ldexp(x, k); }
 #else
 BH_DEV double bh_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-#if defined(BH_NO_FMA_K)
-BH_DEV double bh_fma_k(double a, double b, double k) { return __builtin_fma(a, b, k); }
-#else
 BH_DEV double bh_fma_k(double a, double b, double k)
 {
     if (!__builtin_constant_p(k)) return __builtin_fma(a, b, k);
@@ -50,7 +46,6 @@ BH_DEV double bh_fma_k(double a, double b, double k)
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(k));
     return r;
 }
-#endif
 BH_DEV double bh_rint(double x) { return __builtin_rint(x); }
 BH_DEV double bh_ldexp(double x, int k) { return __builtin_amdgcn_ldexp(x, k); }
 #endif

@@ -355,14 +355,14 @@ int retire_stream(hipStream_t stream)
 
 // kernel choice of bh_swd_batch: process-wide default (bh_swd_set_kernel), read once per call
 std::atomic<int> g_swd_mode{BH_SWD_AUTO};
-thread_local int g_last_form = -1;
+thread_local int g_last_form = -1;                 // what the last bh_swd_batch of this thread launched (bh_swd_last_form)
 thread_local int g_last_forms[bh::BH_NT] = {0};   // per target (bh_swd_last_forms)
 thread_local int g_forced_forms[bh::BH_NT] = {0};
 // what the caller knows about its next batch and the planner cannot see in device memory (bh_swd_hint): the mean
 // layer count of the models (0: unknown) and how many such calls are in flight together (>= 1)
 thread_local double g_hint_mean = 0.0;
 thread_local int g_hint_load = 1;
-thread_local int g_nforced = 0;                    // > 0: bh_swd_set_forms is in force for calls with that many targets    // what the last bh_swd_batch of this thread launched (bh_swd_last_form)
+thread_local int g_nforced = 0;                    // > 0: bh_swd_set_forms is in force for calls with that many targets
 
 long team_threshold()
 {
@@ -411,9 +411,9 @@ void plan_forms(int B, int Lmax, int ntargets, const bh_swd_target *targets, lon
         return;
     }
     if (swd_mode != BH_SWD_AUTO) {
-        const int w = swd_mode == BH_SWD_LANE ? 0 : swd_mode == BH_SWD_TEAM8 ? 8 : swd_mode == BH_SWD_TEAM16 ? 16
-                    : swd_mode == BH_SWD_TEAM32 ? 32 : swd_mode == BH_SWD_TEAM128 ? 128
-                    : swd_mode == BH_SWD_TEAM256 ? 256 : swd_mode == BH_SWD_TEAM512 ? 512 : 64;
+        int w = 64;
+        for (int k = 0; k < bh::kSwdForms; k++)
+            if (bh::swd_forms()[k].mode == swd_mode) w = bh::kFormWidth[k];
         for (int t = 0; t < ntargets; t++) width[t] = w;
         return;
     }
@@ -433,27 +433,16 @@ void plan_forms(int B, int Lmax, int ntargets, const bh_swd_target *targets, lon
         if (team_threshold() > 0 && searches > team_threshold()) return false;
         return bh::swd_team_lds_bytes(Lmax, bh::kFormWidth[k]) <= 160 * 1024;
     };
-    // measured range of form k, its time for s searches (1e300: beyond what a wide team was measured for)
-    auto measured = [&](int k) {
-        int n = bh::kFormSizes;
-        while (n > 1 && bh::kFormMs[regime][k][n - 1] < 0) n--;
-        return n;
-    };
-    auto form_ms_in = [&](int rg, int k, double s) {
-        const float *t = bh::kFormMs[rg][k], *S = bh::kFormSearches;
+    // measured range of a form's row t of the table, form k's time for s searches at the depths of regime rg (1e300:
+    // beyond what a wide team was measured for)
+    auto measured = [](const float *t) {
         int n = bh::kFormSizes;
         while (n > 1 && t[n - 1] < 0) n--;
-        if (s <= S[0]) return (double)t[0];
-        if (s > S[n - 1]) return n < bh::kFormSizes ? 1e300 : (double)t[n - 1] * s / S[n - 1];
-        if (s == S[n - 1]) return (double)t[n - 1];
-        int i = 0;
-        while (S[i + 1] <= s) i++;
-        const double f = (std::log(s) - std::log(S[i])) / (std::log(S[i + 1]) - std::log(S[i]));
-        return t[i] + f * (t[i + 1] - t[i]);
+        return n;
     };
-    auto form_ms = [&](int k, double s) {
-        const float *t = bh::kFormMs[regime][k], *S = bh::kFormSearches;
-        const int n = measured(k);
+    auto form_ms = [&](int rg, int k, double s) {
+        const float *t = bh::kFormMs[rg][k], *S = bh::kFormSearches;
+        const int n = measured(t);
         if (s <= S[0]) return (double)t[0];
         if (s > S[n - 1]) return n < bh::kFormSizes ? 1e300 : (double)t[n - 1] * s / S[n - 1];
         if (s == S[n - 1]) return (double)t[n - 1];
@@ -479,9 +468,8 @@ void plan_forms(int B, int Lmax, int ntargets, const bh_swd_target *targets, lon
     double best = 1e300;
     for (int k = 0; k < 8; k++) {
         if (!allowed(k)) continue;
-        double cost = std::fmax(heavy * (double)bh::kFormMs[regime][k][0], form_ms(k, eff));
-        if (regime_thr != regime || load > 1)         // ragged batch / shared chip: latency of the deepest | throughput
-            cost = std::fmax(heavy * (double)bh::kFormMs[regime][k][0], form_ms_in(regime_thr, k, eff * load));
+        // latency of the deepest model | throughput (ragged batch: at the mean depth; shared chip: of all calls in flight)
+        const double cost = std::fmax(heavy * (double)bh::kFormMs[regime][k][0], form_ms(regime_thr, k, eff * load));
         if (cost < best) { best = cost; uniform = k; }
     }
     int form[bh::BH_NT];
@@ -496,7 +484,7 @@ void plan_forms(int B, int Lmax, int ntargets, const bh_swd_target *targets, lon
         // latency (chip mostly idle) and saturation rate (searches per ms) of a form, from the table's ends
         auto lat = [&](int k) { return (double)bh::kFormMs[regime][k][0]; };
         auto thr = [&](int k) {
-            const int n = measured(k);
+            const int n = measured(bh::kFormMs[regime][k]);
             return (double)bh::kFormSearches[n - 1] / bh::kFormMs[regime][k][n - 1] / scale;
         };
         auto cost_of = [&](const int *fm) {
@@ -534,8 +522,6 @@ int pick_rf_M(int B, int Lmax, int nsamp)
     // profiles/r03_ab_rf_coresident.txt.)
     size_t per = bh::rf_lds_bytes(Lmax, nsamp, 1);
     int M = (int)((26 * 1024) / per);
-    static const char *force = std::getenv("BH_RF_M");       // A/B switch (diagnostic)
-    if (force && std::atoi(force) > 0) M = std::atoi(force);
     if (M > 8) M = 8;
     if (M < 1) M = 1;
     if (M > B) M = B;
@@ -682,13 +668,9 @@ int bh_swd_batch_ordered(int B, int Lmax, int model_stride, const int *nlay, con
             int w = l.width;
             while (w > 64 && bh::swd_team_lds_bytes(Lmax, w) > 160 * 1024) w /= 2;
             int team_resident = resident;
-#ifndef BH_NARROW_WAVES
-#define BH_NARROW_WAVES 2
-#endif
-            constexpr long BH_NARROW_WAVES_HOST = BH_NARROW_WAVES;     // waves per SIMD the narrow kernels are built for
             if (w < 64) {           // persistent waves of a narrow-team kernel that stay resident
                 long per_cu = (long)(160 * 1024 / bh::swd_team_lds_bytes(Lmax, w));
-                long waves = cus * (per_cu > 4 * BH_NARROW_WAVES_HOST ? 4 * BH_NARROW_WAVES_HOST : per_cu);
+                long waves = cus * (per_cu > 4 * bh::BH_NARROW_WAVES ? 4 * bh::BH_NARROW_WAVES : per_cu);
                 team_resident = (int)(waves > 0 ? waves : 1);
             }
             le = bh::launch_swd_team(A, w, team_resident, st);
@@ -739,7 +721,7 @@ int bh_swd_set_forms(const int *forms, int ntargets)
     int distinct = 0;
     for (int t = 0; t < ntargets; t++) {
         const int w = forms[t];
-        if (w != 0 && w != 8 && w != 16 && w != 32 && w != 64 && w != 128 && w != 256 && w != 512)
+        if (bh::swd_form_of_width(w) < 0)
             return fail_arg("bh_swd_set_forms: a form is 0 (lane kernel) or 8, 16, ..., 512 lanes per search");
         bool seen = false;
         for (int u = 0; u < t; u++) seen = seen || forms[u] == w;
@@ -854,7 +836,6 @@ int bh_voronoi_to_layers(int B, int Lmax, const int *nlay, const double *vs_nucl
     if (!nlay || !vs_nuclei || !z_nuclei || !vpvs || !pri || !model || !valid) return fail_arg("NULL pointer");
     int rc = ensure_device();
     if (rc) return rc;
-    if (B == 0) return BH_OK;
     bh::VoronoiArgs A;
     A.B = B; A.Lmax = Lmax; A.nlay = nlay; A.vs = vs_nuclei; A.z = z_nuclei; A.vpvs = vpvs;
     A.model = model; A.valid = valid;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "rf_core.h"
 #include "swd_core.h"
+#include "swd_form_table.h"
 
 namespace bh {
 
@@ -37,6 +38,22 @@ struct SwdArgs {
     int nsel;
     unsigned char tord[BH_NT];   // the launch's targets, heaviest first (narrow teams: the order in which every wave drains them)
 };
+
+// Kernel form k of the dispersion solver runs kFormWidth[k] lanes per search (swd_form_table.h; 0: the lane kernel):
+// the bh_swd_set_kernel mode that asks for it, and its kernel (null: the lane kernel, launch_swd).
+struct SwdForm {
+    int mode;
+    void (*kernel)(SwdArgs);
+};
+constexpr int kSwdForms = 8;
+const SwdForm *swd_forms();                      // [kSwdForms], kernels.hip
+inline int swd_form_of_width(int width)          // -1: no form has that many lanes per search
+{
+    for (int k = 0; k < kSwdForms; k++)
+        if (kFormWidth[k] == width) return k;
+    return -1;
+}
+constexpr int BH_NARROW_WAVES = 2;   // waves per SIMD the narrow-team kernels (8, 16, 32 lanes per search) are built for
 
 struct RfArgs {
     int B;

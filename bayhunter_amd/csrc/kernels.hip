@@ -11,7 +11,7 @@
 // and not MFMA-shaped ("Roofline").  HBM traffic is the algorithmic minimum: each model
 // byte is read once, each output written once; everything else lives in LDS/registers.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
+#include "../../include/bayhunter_amd.h"
 #include "kernels.h"
 #include "rf_core.h"
 #include "swd_core.h"
@@ -170,9 +170,7 @@ struct QueueSrc {
 
 // 2 waves per SIMD: the search state + one Dunkin layer need 189 VGPRs (250 while polynomial coefficients
 // were kept in VGPR pairs, bh_math.h); the allocator's budget is pinned to two waves
-#ifndef BH_SWD_WAVES
-#define BH_SWD_WAVES 2            // waves per SIMD the register budget of swd_kernel is set for
-#endif
+constexpr int BH_SWD_WAVES = 2;   // waves per SIMD the register budget of swd_kernel is set for
 // Diagnostic build only (-DBH_LANE_PROFILE, tools/lane_phase_profile.py): shader-clock cycles of the three
 // parts of swd_lane's loop -- driver (events, task fetch), period equation, control -- summed over all
 // lanes (a lane also counts the cycles it sits masked off while other lanes of its wave run their
@@ -356,54 +354,6 @@ __device__ unsigned long long g_team_prof[20];
 #define BH_TP_COUNT(i, n)
 #define BH_TP_FLUSH(rounds)
 #endif
-
-template <int TEAM>
-__device__ __forceinline__ void swd_team_body(const SwdArgs &A)
-{
-    extern __shared__ double tlds[];
-    constexpr int NSUB = SWD_T / TEAM;
-    static_assert(NSUB > 1, "64 lanes and more per search: swd_teamw_body");
-    const int sub = threadIdx.x / TEAM, lane = threadIdx.x % TEAM;
-    const int t = blockIdx.y;
-    if (!((A.tmask >> t) & 1u)) return;              // not a target of this launch (kernels.h)
-    const SwdTargetDev tg = A.tg[t];
-    const int nm = A.Lmax > TEAM ? A.Lmax : TEAM;
-    // per team: mats[nm][19], trials[16], dels[16] (doubles), then 4*Lmax floats (padded to doubles)
-    const int per_team = nm * SWD_NCA + 2 * SWD_TEAM_NT + (4 * A.Lmax + 1) / 2;
-    double *mats = tlds + (long)sub * per_team, *trials = mats + (long)nm * SWD_NCA, *dels = trials + SWD_TEAM_NT;
-    TeamLay lay{(float *)(dels + SWD_TEAM_NT), A.Lmax};
-    TeamSrc src{A, tg, t, lane, TEAM, 0, (long)blockIdx.x, A.counters + t, nullptr};
-    const double *per = A.periods + tg.per_off;
-    SwdState S;
-    swd_state_init(S);
-    NevRegs nv;
-    swd_nev_init(nv);
-    {
-        // A team whose search is over keeps walking through the phases with nt = 0 (no trial, no
-        // matrix, no value consumed): cheaper than predicating every phase on a per-team flag.
-        bool live = true;
-        for (;;) {
-            if (live) {
-                swd_events(S, lay, src, tg, per, A.B);
-                live = S.st != SWD_ST_DONE;
-            }
-            if (!__any(live)) break;
-            const int nt = live ? swd_team_plan(S, TEAM, trials) : 0;
-            __syncthreads();
-            swd_team_assemble(lay, lane, TEAM, tg.iwave, S, nt, trials, mats);
-            __syncthreads();
-            if (tg.iwave == 2 && 8 * nt <= TEAM) swd_team_chain_ray5(lay, lane, S, nt, trials, mats, dels);
-            else swd_team_chain(lay, lane, tg.iwave, S, nt, trials, mats, dels);
-            __syncthreads();
-            swd_team_consume(S, nv, nt, trials, dels);
-            __syncthreads();
-        }
-    }
-}
-
-// The narrower forms carry per-team liveness through the divergent driver call: ~199 registers, no
-// scratch, pinned to 2 waves per SIMD (with machine LICM on they wanted ~310 and spilled 48 bytes).
-// (the kernels swd_team32 / 16 / 8 are defined behind swd_tpl_body, further down)
 
 // ---------------------------------------------------------------------------------- SWD, wide teams
 // 64*W lanes (W waves, one workgroup) per search: swd_team.h, "Wide teams".  Per round
@@ -693,12 +643,8 @@ __device__ __forceinline__ void swd_teamw_body(const SwdArgs &A)
     // The one-wave team evaluates ONE TRIAL PER LANE -- 64 slots a round, each lane the whole period equation of its
     // trial (swd_dltar4 / swd_dltar1), no matrices in LDS -- like the narrow teams of swd_tpl_body, with the wave's
     // uniform control code.  (Until round 4 it spread the layers of 64 / nlm trials over its lanes like the wider
-    // teams; -DBH_TEAM64_LAYERS.)
-#if defined(BH_TEAM64_LAYERS)
-    constexpr bool TPL = false;
-#else
+    // teams.)
     constexpr bool TPL = W == 1;
-#endif
     const int lane = threadIdx.x, wl = lane & 63, wave = uni(lane >> 6);
     const bool ctl = W == 1 || wave == 0;
     const int t = blockIdx.y;
@@ -745,11 +691,6 @@ __device__ __forceinline__ void swd_teamw_body(const SwdArgs &A)
     for (;;) {
         bool fin = false;
         int nt = 1;
-#if defined(BH_TEAMW_USTATE)
-        S.c1 = uni(S.c1); S.c2 = uni(S.c2); S.c3 = uni(S.c3); S.del1 = uni(S.del1); S.del2 = uni(S.del2); S.del3 = uni(S.del3);
-        S.clow = uni(S.clow); S.del1st = uni(S.del1st); S.ceval = uni(S.ceval); S.omega = uni(S.omega);
-        S.cprev = uni(S.cprev); S.ck = uni(S.ck); S.cc = uni(S.cc); S.cfail = uni(S.cfail);
-#endif
         if (ctl) {
             // (no event pending in all but one round per search: do not even enter the driver's loop --
             // the copies between the two loop headers were 7 % of a round)
@@ -871,8 +812,8 @@ __device__ __forceinline__ void swd_teamw_body(const SwdArgs &A)
 // period of one full evaluation each.  For the batches in between -- a few thousand to a few ten thousand searches,
 // which fill the chip as 64 / K searches per wave but not as one search per lane.
 // (Until round 4 the narrow forms spread the LAYERS of one or two trials over the team's lanes, like the wide teams,
-// and speculated on the scan only: 4.5 searches/us on five layers where the lane kernel does 16.8.  swd_team_body
-// below, -DBH_NARROW_LAYERS.)
+// and speculated on the scan only: 4.5 searches/us on five layers where the lane kernel does 16.8.  That body is
+// no longer in the tree; swd_team.h keeps its building blocks as the host replay's baseline.)
 // Every lane of a team runs driver, plan and consuming loop on its own copy of the team's state; the teams of a wave
 // diverge there, and meet again for the evaluation.
 BH_HD int swd_tpl_team_doubles(int Lmax, int K)
@@ -960,29 +901,15 @@ __device__ __forceinline__ void swd_tpl_body(const SwdArgs &A)
 // Three waves per SIMD: <= 168 VGPRs (the body needs ~140; without the bound the register allocator spreads out
 // to 189 and, with the 12.9 KB of LDS a 64-lane team takes, the registers would be what limits a CU to eight teams).
 #define BH_TEAMW_ATTR __attribute__((amdgpu_waves_per_eu(3)))
-#if defined(BH_TEAM64_LAYERS)
-#define BH_TEAM64_ATTR BH_TEAMW_ATTR
-#else
-#define BH_TEAM64_ATTR __attribute__((amdgpu_waves_per_eu(3)))
-#endif
-__global__ __launch_bounds__(SWD_T) BH_TEAM64_ATTR void swd_team_kernel(SwdArgs A) { swd_teamw_body<1>(A); }
+__global__ __launch_bounds__(SWD_T) BH_TEAMW_ATTR void swd_team_kernel(SwdArgs A) { swd_teamw_body<1>(A); }
 __global__ __launch_bounds__(2 * SWD_T) BH_TEAMW_ATTR void swd_team128_kernel(SwdArgs A) { swd_teamw_body<2>(A); }
 __global__ __launch_bounds__(4 * SWD_T) BH_TEAMW_ATTR void swd_team256_kernel(SwdArgs A) { swd_teamw_body<4>(A); }
 __global__ __launch_bounds__(8 * SWD_T) BH_TEAMW_ATTR void swd_team512_kernel(SwdArgs A) { swd_teamw_body<8>(A); }
 
-#if defined(BH_NARROW_LAYERS)
-#define BH_NARROW_BODY swd_team_body
-#define BH_NARROW_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
-#else
-#define BH_NARROW_BODY swd_tpl_body
-#ifndef BH_NARROW_WAVES
-#define BH_NARROW_WAVES 2
-#endif
 #define BH_NARROW_ATTR __attribute__((amdgpu_waves_per_eu(BH_NARROW_WAVES)))
-#endif
-__global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team32_kernel(SwdArgs A) { BH_NARROW_BODY<32>(A); }
-__global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team16_kernel(SwdArgs A) { BH_NARROW_BODY<16>(A); }
-__global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team8_kernel(SwdArgs A) { BH_NARROW_BODY<8>(A); }
+__global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team32_kernel(SwdArgs A) { swd_tpl_body<32>(A); }
+__global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team16_kernel(SwdArgs A) { swd_tpl_body<16>(A); }
+__global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team8_kernel(SwdArgs A) { swd_tpl_body<8>(A); }
 
 // -------------------------------------------------------------------------------------------- RF
 // bit reversal (+ 1/sqrt(n)) and the butterfly passes (rf_core.h: one radix-2 stage when log2 n is odd, radix-4 passes
@@ -1019,9 +946,7 @@ __device__ __forceinline__ void rf_block_fft(double *S, int per_model, int Mb, i
 // 4 waves per SIMD (128 VGPRs, nothing spilled): alone the recursion is latency-bound at 2 and equally fast
 // at 3 or 4; at 128 VGPRs a workgroup also fits beside swd_kernel's two waves per SIMD (capi.hip: pick_rf_M).
 // ZR: also keep the filtered vertical/radial spectra and return their traces (synrf_cwrap's fz, fr).
-#ifndef BH_RF_WAVES
-#define BH_RF_WAVES 4
-#endif
+constexpr int BH_RF_WAVES = 4;
 // ROW: the per-row form -- every model at the slowness of its own set (RfArgs::set_p, set_id) instead of the launch's.
 // A second instantiation of the same source: the uniform form takes no argument, branch or register from it.
 template <bool ZR, bool ROW = false>
@@ -1156,36 +1081,30 @@ extern "C" int bh_debug_team_profile(unsigned long long *out, int reset)
 size_t swd_team_lds_bytes(int Lmax, int team)
 {
     if (team >= SWD_T) {           // wide teams: max(Lmax, lanes) matrix slots, dels, periods, layer stack
-#if defined(BH_TEAM64_LAYERS)
-        const int nm = Lmax > team ? Lmax : team;
-#else
         const int nm = team == SWD_T ? 0 : (Lmax > team ? Lmax : team);      // (the one-wave team keeps no matrices)
-#endif
         return ((size_t)swd_mat_off(nm) + 3 * SWD_TEAMW_NT + BH_NP + 24 * (team / SWD_T) + BH_NP / 2 + (4 * Lmax + 1) / 2) * sizeof(double);
     }
     const int nsub = SWD_T / team;
-#if defined(BH_NARROW_LAYERS)
-    const int nm = Lmax > team ? Lmax : team;
-    return (size_t)nsub * (nm * SWD_NCA + 2 * SWD_TEAM_NT + (4 * Lmax + 1) / 2) * sizeof(double);
-#else
     return ((size_t)BH_NP + (size_t)nsub * swd_tpl_team_doubles(Lmax, team)) * sizeof(double);
-#endif
 }
 
-static int team_index(int team)
+const SwdForm *swd_forms()
 {
-    return team == 8 ? 0 : team == 16 ? 1 : team == 32 ? 2 : team == 128 ? 4 : team == 256 ? 5 : team == 512 ? 6 : 3;
+    static const SwdForm forms[kSwdForms] = {
+        {BH_SWD_LANE, nullptr},               {BH_SWD_TEAM8, swd_team8_kernel},   {BH_SWD_TEAM16, swd_team16_kernel},
+        {BH_SWD_TEAM32, swd_team32_kernel},   {BH_SWD_TEAM, swd_team_kernel},     {BH_SWD_TEAM128, swd_team128_kernel},
+        {BH_SWD_TEAM256, swd_team256_kernel}, {BH_SWD_TEAM512, swd_team512_kernel}};
+    return forms;
 }
 
 hipError_t launch_swd_team(const SwdArgs &A, int team, int resident_waves, hipStream_t stream)
 {
-    if (team != 8 && team != 16 && team != 32 && team != 128 && team != 256 && team != 512) team = 64;
+    int form = swd_form_of_width(team);
+    if (form < 1) { team = SWD_T; form = swd_form_of_width(team); }      // not a team width: one wave per search
     size_t lds = swd_team_lds_bytes(A.Lmax, team);
-    static size_t lds_set[7][16] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}};
-    void (*kern)(SwdArgs) = team == 8 ? swd_team8_kernel : team == 16 ? swd_team16_kernel
-                          : team == 32 ? swd_team32_kernel : team == 128 ? swd_team128_kernel
-                          : team == 256 ? swd_team256_kernel : team == 512 ? swd_team512_kernel : swd_team_kernel;
-    hipError_t e = ensure_dyn_lds((const void *)kern, lds, lds_set[team_index(team)]);
+    static size_t lds_set[kSwdForms][16] = {{0}};
+    void (*kern)(SwdArgs) = swd_forms()[form].kernel;
+    hipError_t e = ensure_dyn_lds((const void *)kern, lds, lds_set[form]);
     if (e != hipSuccess) return e;
     if (team >= SWD_T) {           // one workgroup per search; the hardware back-fills them
         hipLaunchKernelGGL(kern, dim3(A.B, A.ntargets), dim3(team), lds, stream, A);
@@ -1212,8 +1131,7 @@ hipError_t launch_swd(const SwdArgs &A, int resident_waves, hipStream_t stream)
     const size_t perbytes = (size_t)BH_NP * sizeof(double);                      // the target's periods
     const size_t staged = lds + (size_t)maxper * SWD_T * sizeof(float);
     SwdArgs B = A;
-    static const bool no_stage = std::getenv("BH_SWD_NO_STAGE") != nullptr;      // A/B switch (diagnostic)
-    B.stage = (!no_stage && maxper > 0 && 8 * (staged + perbytes) <= 160 * 1024) ? maxper : 0;   // periods staged per lane
+    B.stage = (maxper > 0 && 8 * (staged + perbytes) <= 160 * 1024) ? maxper : 0;   // periods staged per lane
     if (B.stage) lds = staged;
     lds += perbytes;
     static size_t lds_set[16] = {0};

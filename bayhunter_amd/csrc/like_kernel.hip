@@ -10,7 +10,6 @@
 // One workgroup = LIKE_M models, LIKE_T threads.  HBM traffic: the model's output row is read once
 // (it is what swd_kernel/rf_kernel just wrote), 8*(ntargets+2) bytes are written per model.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include "kernels.h"
 #include "like_core.h"
 
@@ -611,9 +610,7 @@ hipError_t launch_like(const LikeArgs &A, int nmax, hipStream_t stream, int stag
                 const dim3 b(64 * GQ_WAVES);
                 const unsigned gx = (unsigned)((A.B + 16 * GQ_WAVES - 1) / (16 * GQ_WAVES));
                 double *gq = A.gq + (long)t * A.B * 2 * A.gq_groups;
-                static const char *force = std::getenv("BH_GQ_FORM");        // "split" | "fused" (A/B)
-                const bool split = force ? force[0] == 's' : A.B <= 32768;
-                if (split) {
+                if (A.B <= 32768) {              // SPLIT (small batches), else fused
                     const size_t lds = (size_t)2 * GQ_KC * GQ_NTG * 16 * sizeof(double);
                     hipLaunchKernelGGL((gauss_q_kernel<GQ_NTG, true>), dim3(gx, gq_groups_of(A.tg[t].n)), b, lds, stream, A, t, gq);
                 } else {

@@ -26,9 +26,7 @@
 
 namespace bh {
 
-#ifndef BH_PI
 #define BH_PI 3.14159265358979323846 /* M_PI */
-#endif
 
 // Host-prepared, launch-uniform parameters.  The derived constants are computed on the host with
 // the reference's own expressions so that they are bit-identical to what rfmini uses.

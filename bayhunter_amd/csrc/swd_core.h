@@ -729,7 +729,7 @@ BH_DEV void swd_driver(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
     }
 }
 
-// The pending event(s) of a search for the team kernels (swd_team_body, swd_teamw_consume), the common chain first:
+// The pending event(s) of a search for the team kernels (swd_teamw_consume), the common chain first:
 // "root found -> value stored -> next period" is two straight-line blocks; only the rare events (task fetch, no root,
 // end of the periods / of a mode) enter the driver's loop.  Same operations in the same order as swd_driver alone.
 // (The throughput kernel, for which the fast blocks were written -- some lane of a wave ends a period in 86 % of its
@@ -738,12 +738,9 @@ template <class Lay, class Src>
 BH_DEV void swd_events(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
                        const double *BH_RESTRICT per, int wss, bool allow_fetch = true)
 {
-#if !defined(BH_NO_FAST_EVENTS)                   // (A/B switch: the driver's loop for every event)
     if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) swd_on_solved(S, src, tg, wss);
     if (S.ev == SWD_EV_BEGIN_PERIOD && S.k <= tg.nper && S.k < S.ift) swd_on_begin_period(S, tg, per, wss);
-    if (S.ev != SWD_EV_NONE)
-#endif
-        swd_driver(S, lay, src, tg, per, wss, allow_fetch);
+    if (S.ev != SWD_EV_NONE) swd_driver(S, lay, src, tg, per, wss, allow_fetch);
 }
 
 // The same events for the throughput kernel, without the driver's loop: one straight-line pass whose arms stand in
@@ -852,8 +849,8 @@ BH_DEV void swd_control(SwdState &S, double del, Nev &nv)
 // by selects, at the top level.  Written as nested arms like above, each join of divergent arms keeps an old and
 // a new copy of whatever the arms assign -- the Neville table and half the state -- and a third of the control
 // code's vector instructions were register moves.  Same operations on the same values as
-// the generic form; tests/hostsim/control_paths_sim.cpp runs the two side by side.  Only swd_kernel (and
-// swd_team_body, a diagnostic build) keeps its table in registers.  The narrow teams (swd_tpl_body: 8, 16, 32
+// the generic form; tests/hostsim/control_paths_sim.cpp runs the two side by side.  Only swd_kernel keeps its
+// table in registers.  The narrow teams (swd_tpl_body: 8, 16, 32
 // lanes per search) keep theirs in LDS and run the generic form, although their teams diverge in control too and
 // carry as many moves (about 1 090 of 3 950 vector instructions): they sit at 195-199 of 200 allocated VGPRs, and
 // what the flat form does to that budget has not been measured.  They were left as they are.

@@ -220,3 +220,66 @@ def test_form_plan_follows_the_measured_table():
             f = plan(B, L, cfg3)
             assert len(set(f)) <= 3 and all(w in (0, 8, 16, 32, 64, 128, 256, 512) for w in f)
     assert lib.bh_swd_plan_forms(8192, 10, 0, None, 256, None) != 0
+
+
+def test_form_plans_are_the_recorded_ones():
+    """The planner over a grid of calls -- batch sizes x depths x CU counts x target sets x hints, every bh_swd_set_kernel
+    mode, the widths bh_swd_set_forms takes and the text with which it refuses the others -- against
+    tests/golden/form_plans.json, which the library of the commit before the planner's clean-up recorded
+    (tests/golden/make_golden_form_plans.py): every entry equal."""
+    import json
+    from bayhunter_amd import _lib
+    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
+    import make_golden_form_plans as gen
+    with open(os.path.join(ROOT, 'tests', 'golden', 'form_plans.json')) as fh:
+        want = json.load(fh)
+    assert len(want['plans']) == len(gen.CUS) * len(gen.TARGET_SETS) * len(gen.HINTS) * len(gen.BATCHES)
+    assert all(len(rows) == len(gen.DEPTHS) for rows in want['plans'].values())
+    got = gen.record(_lib.load())
+    assert sorted(got) == sorted(want)
+    for section in want:
+        assert sorted(got[section]) == sorted(want[section]), section
+        for key in want[section]:
+            assert got[section][key] == want[section][key], (section, key)
+
+
+def test_no_switches_beyond_the_kept_ones():
+    """The library's sources switch on these names and no others: every identifier of an #if / #ifdef / #ifndef / #elif
+    line and every getenv name under bayhunter_amd/csrc (names the compiler predefines aside).  A measured-and-dropped
+    experiment leaves the tree with its switch; the ones that were removed stay out of the package and the tools."""
+    keep = {
+        'BH_HOSTSIM', 'BH_HOSTSIM_GLIBC_MATH', 'BH_SRC_HASH',              # structural
+        'BH_LANE_PROFILE', 'BH_TEAM_PROFILE',                              # tools/lane_phase_profile.py, team_phase_profile.py
+        'BH_RF_EXP', 'BH_RF_NO_PAD',                                       # tools/rf_probe.py
+        'SWD_TEAMW_MIDROOM', 'SWD_TEAMW_CHAIN_MAX', 'SWD_TEAMW_NPM',       # tools/replay_rounds.py
+        'BH_SWD_QUEUE_SLOTS', 'BH_SWD_RESIDENT_WAVES',                     # test hooks of the GPU tests
+        'BH_SWD_NO_MIXED',                                                 # tools/auto_forms.py
+        'BH_SWD_TEAM_MAX', 'BH_CHAIN_SPIN_US', 'BH_CHAIN_THREADS',         # operator knobs
+    }
+    removed = ['BH_NARROW_LAYERS', 'BH_NARROW_BODY', 'BH_TEAM64_LAYERS', 'BH_TEAM64_ATTR', 'BH_TEAMW_USTATE',
+               'BH_TEAMW_NO_LONE', 'BH_TEAMW_NO_CHAINS', 'BH_NO_FAST_EVENTS', 'BH_NO_FMA_K', 'BH_SWD_NO_STAGE', 'BH_RF_M',
+               'BH_GQ_FORM', 'swd_team_body', 'swd_team_chain_ray5']
+    csrc = os.path.join(ROOT, 'bayhunter_amd', 'csrc')
+    found = {}
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith(('.h', '.hip', '.cpp')):
+            continue
+        src = open(os.path.join(csrc, f)).read()
+        for line in re.findall(r'^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$', src, flags=re.M):
+            line = re.sub(r'//.*|/\*.*?\*/', '', line)
+            for name in re.findall(r'[A-Za-z_]\w*', line):
+                if name != 'defined' and not name.startswith('__'):
+                    found.setdefault(name, f)
+        for name in re.findall(r'getenv\s*\(\s*"([^"]*)"', src):
+            found.setdefault(name, f)
+        assert len(re.findall(r'getenv\s*\(', src)) == len(re.findall(r'getenv\s*\(\s*"', src)), f   # literal names only
+    assert set(found) == keep, {n: found[n] for n in set(found) ^ keep if n in found} or keep - set(found)
+    files = [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(ROOT, 'bayhunter_amd')) for f in fs
+             if f.endswith(('.py', '.h', '.hip', '.cpp'))]
+    files += [os.path.join(dp, f) for dp, _, fs in os.walk(os.path.join(ROOT, 'tools')) for f in fs
+              if f.endswith(('.py', '.sh'))]
+    assert len(files) > 40
+    for path in files:
+        src = open(path).read()
+        for name in removed:
+            assert not re.search(r'\b%s\b' % name, src), (name, path)
