@@ -132,6 +132,16 @@ BH_DEV Recip recip_sq(const Recip &R)
 }
 #endif
 
+// bh_fma_exact2(a, k, c) = fma(a, k, c) for k = +-2^n: the bits of the unfused `a * k + c`, and of `(a + c / k) * k`, in
+// one instruction instead of two.  A product with a power of two is exact unless it over- or underflows, so either unfused
+// form rounds once -- the sum -- and rounding commutes with the scaling: round(a + c / k) k = round(a k + c), which
+// is what the fused form returns.  Where a is itself a rounded product, round(x y) k = round(x y k) for the same
+// reason: an exact factor may be taken out of a product and handed to the fused form.  The fused form never rounds
+// a * k, so the one condition is that the UNFUSED form did not either: at each use the caller states why the scaled
+// term (and, for a factor taken out of a product, the product) is zero or normal and far from overflow.  The library
+// is compiled with -ffp-contract=off: nothing is fused that is not written as a fusion.
+BH_DEV double bh_fma_exact2(double a, double k, double c) { return __builtin_fma(a, k, c); }
+
 BH_DEV double dsign1(double x) { return copysign(1.0, x); }
 // dsign(1, a) != dsign(1, b), equivalently dsign(1, a) * dsign(1, b) < 0 (the reference's sign tests,
 // surfdisp96.f:431,461,600,616): the sign bits differ.  One xor instead of two copysigns and a product;

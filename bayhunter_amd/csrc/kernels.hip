@@ -178,7 +178,7 @@ constexpr int BH_SWD_WAVES = 2;   // waves per SIMD the register budget of swd_k
 #if defined(BH_LANE_PROFILE)
 __device__ unsigned long long g_lane_prof[8];
 template <class Lay, class Src>
-__device__ __forceinline__ void swd_lane_prof(Lay &lay, Src &src, const SwdTargetDev &tg, const double *BH_RESTRICT per, int wss)
+__device__ __forceinline__ void swd_lane_prof(Lay &lay, Src &src, const SwdTargetDev &tg, const SwdPerTab &per, int wss)
 {
     SwdState S;
     swd_state_init(S);
@@ -223,15 +223,18 @@ __global__ __launch_bounds__(SWD_T) __attribute__((amdgpu_waves_per_eu(BH_SWD_WA
     const SwdTargetDev tg = A.tg[t];
     LdsLay lay{lds + threadIdx.x, A.Lmax};
     QueueSrc src{A, tg, A.counters + t, t, 0, A.stage ? lds + 4 * A.Lmax * SWD_T + threadIdx.x : nullptr};
-    // the target's periods in LDS, behind the model and result images: a lane reads one whenever it
-    // starts a period, and in most loop trips some lane of the wave does
+    // what the searches take from the target's periods (swd_core.h: SwdPerTab), in LDS behind the model and result
+    // images: a lane reads an entry whenever it starts a solve, and in most loop trips some lane of the wave does.
+    // Worked out here, once per wave and launch: two or three IEEE divisions per period, which every search used to
+    // repeat at every period.
     double *perl = (double *)(lds + (4 * A.Lmax + A.stage) * SWD_T);
-    for (int k = threadIdx.x; k < tg.nper; k += SWD_T) perl[k] = A.periods[tg.per_off + k];
+    for (int k = threadIdx.x; k < tg.nper; k += SWD_T) swd_pertab_put(perl, tg.nper, k, A.periods[tg.per_off + k], tg.igr);
     __syncthreads();
+    const SwdPerTab pert{perl, tg.nper};
 #if defined(BH_LANE_PROFILE)
-    swd_lane_prof(lay, src, tg, perl, A.B);
+    swd_lane_prof(lay, src, tg, pert, A.B);
 #else
-    swd_lane(lay, src, tg, perl, A.B, nullptr);
+    swd_lane(lay, src, tg, pert, A.B, nullptr);
 #endif
 }
 
@@ -1126,9 +1129,13 @@ hipError_t launch_swd(const SwdArgs &A, int resident_waves, hipStream_t stream)
     // (the register-limited residency) still fit 160 KiB with it
     size_t lds = (size_t)4 * A.Lmax * SWD_T * sizeof(float);
     int maxper = 0;
+    bool group = false;
     for (int t = 0; t < A.ntargets; t++)
-        if ((A.tmask >> t) & 1u) maxper = A.tg[t].nper > maxper ? A.tg[t].nper : maxper;
-    const size_t perbytes = (size_t)BH_NP * sizeof(double);                      // the target's periods
+        if ((A.tmask >> t) & 1u) {
+            maxper = A.tg[t].nper > maxper ? A.tg[t].nper : maxper;
+            group = group || A.tg[t].igr > 0;
+        }
+    const size_t perbytes = (size_t)swd_pertab_doubles(maxper, group) * sizeof(double);   // the longest period table
     const size_t staged = lds + (size_t)maxper * SWD_T * sizeof(float);
     SwdArgs B = A;
     B.stage = (maxper > 0 && 8 * (staged + perbytes) <= 160 * 1024) ? maxper : 0;   // periods staged per lane

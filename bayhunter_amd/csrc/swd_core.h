@@ -44,8 +44,8 @@ BH_DEV void swd_var(double p, double q, const Recip &by_ra, const Recip &by_rb, 
         pex = p;
         fac = 0.0;
         if (p < 16) fac = bh_exp_bounded(-2.0 * p);
-        cosp = (1.0 + fac) * 0.5;
-        sinp = (1.0 - fac) * 0.5;
+        cosp = bh_fma_exact2(fac, 0.5, 0.5);         // (1 + fac) * 0.5: fac in [0, 1], the sum lies in [1, 2]
+        sinp = bh_fma_exact2(-fac, 0.5, 0.5);        // (1 - fac) * 0.5: the difference is 0 or >= 2^-53
         w = qdiv(sinp, by_ra);
         x = ra * sinp;
     }
@@ -59,8 +59,8 @@ BH_DEV void swd_var(double p, double q, const Recip &by_ra, const Recip &by_rb, 
         sex = q;
         fac = 0.0;
         if (q < 16) fac = bh_exp_bounded(-2.0 * q);
-        cosq = (1.0 + fac) * 0.5;
-        sinq = (1.0 - fac) * 0.5;
+        cosq = bh_fma_exact2(fac, 0.5, 0.5);         // (1 + fac) * 0.5, as above
+        sinq = bh_fma_exact2(-fac, 0.5, 0.5);        // (1 - fac) * 0.5
         y = qdiv(sinq, by_rb);
         z = rb * sinq;
     }
@@ -87,12 +87,17 @@ BH_DEV void swd_dnka(Dunkin &a, double wvno2, double gam, double gammk, double r
     const double one = 1.0, two = 2.0;
     double gamm1 = gam - one, twgm1 = gam + gamm1, gmgmk = gam * gammk, gmgm1 = gam * gamm1,
            gm1sq = gamm1 * gamm1, rho2 = rho * rho, a0pq = v.a0 - v.cpcq;
-    a.c11 = v.cpcq - two * gmgm1 * a0pq - gmgmk * v.xz - wvno2 * gm1sq * v.wy;
+    // v.cpcq - two * gmgm1 * a0pq: the factor two moves from gmgm1 to the rounded product gmgm1 * a0pq.  A product that
+    // is not zero is normal: |gmgm1| >= 2^-53 |gam| (gam - 1 is 0 or >= 2^-53 max(gam, 1)) with gam = 2 (b / c)^2 >= 2^-553
+    // for fp32 velocities, and |a0pq| >= 2^-180, the difference of two values that are each 0 or >= 2^-124 (a0 >= e^-60;
+    // cpcq a product of cosines, none below 2^-62 for an fp64 argument).
+    a.c11 = bh_fma_exact2(gmgm1 * a0pq, -two, v.cpcq) - gmgmk * v.xz - wvno2 * gm1sq * v.wy;
     const Recip by_rho = recip_of(rho);
     a.c12 = qdiv(wvno2 * v.cpy - v.cqx, by_rho);
     a.c13 = qdiv(-(twgm1 * a0pq + gammk * v.xz + wvno2 * gamm1 * v.wy), by_rho);
     a.c14 = qdiv(v.cpz - wvno2 * v.cqw, by_rho);
-    a.c15 = qdiv(-(two * wvno2 * a0pq + v.xz + wvno2 * wvno2 * v.wy), recip_sq(by_rho));   // by rho2: exact square
+    // two * wvno2 * a0pq + v.xz: two moves to the rounded product wvno2 * a0pq, 0 or normal (wvno2 = (omega / c)^2 >= 2^-300)
+    a.c15 = qdiv(-(bh_fma_exact2(wvno2 * a0pq, two, v.xz) + wvno2 * wvno2 * v.wy), recip_sq(by_rho));   // by rho2: exact square
     a.c21 = (gmgmk * v.cpz - gm1sq * v.cqw) * rho;
     a.c22 = v.cpcq;
     a.c23 = gammk * v.cpz - gamm1 * v.cqw;
@@ -100,12 +105,14 @@ BH_DEV void swd_dnka(Dunkin &a, double wvno2, double gam, double gammk, double r
     a.c41 = (gm1sq * v.cpy - gmgmk * v.cqx) * rho;
     a.c42 = -v.xy;
     a.c43 = gamm1 * v.cpy - gammk * v.cqx;
-    a.c51 = -(two * gmgmk * gm1sq * a0pq + gmgmk * gmgmk * v.xz + gm1sq * gm1sq * v.wy) * rho2;
+    // two * gmgmk * gm1sq * a0pq + gmgmk * gmgmk * v.xz: two moves from gmgmk to the twice-rounded product; as for c11 the
+    // products are 0 or normal (gmgmk * gm1sq >= 2^-106 gmgmk, gmgmk = gam gammk of the same range as gam's square)
+    a.c51 = -(bh_fma_exact2(gmgmk * gm1sq * a0pq, two, gmgmk * gmgmk * v.xz) + gm1sq * gm1sq * v.wy) * rho2;
     a.c53 = -(gammk * gamm1 * twgm1 * a0pq + gam * gammk * gammk * v.xz + gamm1 * gm1sq * v.wy) * rho;
     double t = -two * wvno2;
     a.c31 = t * a.c53;
     a.c32 = t * a.c43;
-    a.c33 = v.a0 + two * (v.cpcq - a.c11);
+    a.c33 = bh_fma_exact2(v.cpcq - a.c11, two, v.a0);       // v.a0 + two * (v.cpcq - a.c11): twice a difference is exact
     a.c34 = t * a.c23;
     a.c35 = t * a.c13;
 }
@@ -236,8 +243,8 @@ BH_DEV void swd_love_layer(const Lay &lay, int i0, double wvno, double omega, Lo
     } else {
         fac = 0.0;
         if (q < 16) fac = bh_exp_bounded(-2.0 * q);
-        o.cosq = (1.0 + fac) * 0.5;
-        sinq = (1.0 - fac) * 0.5;
+        o.cosq = bh_fma_exact2(fac, 0.5, 0.5);       // (1 + fac) * 0.5: fac in [0, 1], as in swd_var
+        sinq = bh_fma_exact2(-fac, 0.5, 0.5);        // (1 - fac) * 0.5
         o.y = qdiv(sinq, by_rb);
         o.z = rb * sinq;
     }
@@ -560,24 +567,84 @@ BH_DEV double swd_bracket_next(double &c1, int &idir, double clow, double dc)
     return c2;
 }
 
-// ---- the two common events of a search (bodies of swd_driver's branches) ---------------------------
-// A period begins (k <= kmax, k < ift): periods, start value and lower bound of the search,
-// surfdisp96.f:231-271.
-BH_DEV void swd_on_begin_period(SwdState &S, const SwdTargetDev &tg, const double *BH_RESTRICT per, int wss)
+// ---- what a search takes from a period ---------------------------------------------------------------
+// The angular frequency of a solve and, for group velocity, the two real*4 periods of the pair (surfdisp96.f:233-240,
+// 283, 296): they depend on the target alone, yet each takes a full IEEE division where it is needed -- in an arm of
+// the event pass that a wave of swd_kernel enters in most loop trips, with one or two lanes of 64 alive.
+//   const double *per  the periods; the quantities are worked out at the event (team kernels, where the whole team
+//                      takes the event together)
+//   SwdPerTab          the same expressions evaluated once per workgroup, by swd_pertab_put, into a table beside the
+//                      model image; the event reads them (swd_kernel).  IEEE division rounds correctly wherever it
+//                      runs, so a table entry has the bits of the division it replaces, and the result of a search
+//                      does not depend on which source its kernel form uses (tests/test_swd_exact_rewrites.py,
+//                      tests/test_gpu_exact_rewrites.py).
+struct SwdPeriod {
+    float t1a, t1b;               // t1b: group velocity only
+    double oma, omb;              // 2 pi / t1a (phase velocity: 2 pi / the period itself), 2 pi / t1b
+};
+BH_DEV SwdPeriod swd_period_of(double t1, int igr)
 {
     const double TWOPI = 2.0 * 3.141592653589793;
+    const float h = 0.005f;
+    SwdPeriod P;
+    if (igr > 0) {
+        P.t1a = (float)(t1 / (double)(1.f + h));
+        P.t1b = (float)(t1 / (double)(1.f - h));
+        P.oma = TWOPI / (double)P.t1a;
+        P.omb = TWOPI / (double)P.t1b;
+    } else {
+        P.t1a = (float)t1; P.t1b = 0.f;
+        P.oma = TWOPI / t1; P.omb = 0.0;
+    }
+    return P;
+}
+// Table of a target of n periods: [oma: n doubles], and for group velocity [omb: n doubles][t1a: n floats][t1b: n floats]
+struct SwdPerTab {
+    const double *tab;
+    int n;
+};
+BH_HD int swd_pertab_doubles(int n, bool group) { return group ? 3 * n : n; }
+BH_DEV void swd_pertab_put(double *tab, int n, int k0, double t1, int igr)      // k0: 0-based period
+{
+    const SwdPeriod P = swd_period_of(t1, igr);
+    tab[k0] = P.oma;
+    if (igr > 0) {
+        tab[n + k0] = P.omb;
+        float *f = (float *)(tab + 2 * n);
+        f[k0] = P.t1a; f[n + k0] = P.t1b;
+    }
+}
+// first solve of period S.k: the angular frequency; the direct source leaves the real*4 periods in the state
+BH_DEV double swd_period_begin(SwdState &S, const SwdTargetDev &tg, const double *per)
+{
+    const SwdPeriod P = swd_period_of(per[S.k - 1], tg.igr);
+    S.t1a = P.t1a;
+    if (tg.igr > 0) S.t1b = P.t1b;
+    return P.oma;
+}
+BH_DEV double swd_period_begin(SwdState &S, const SwdTargetDev &, const SwdPerTab &T) { return T.tab[S.k - 1]; }
+// second solve (group velocity)
+BH_DEV double swd_period_second(const SwdState &S, const double *)
+{
+    const double TWOPI = 2.0 * 3.141592653589793;
+    return TWOPI / (double)S.t1b;
+}
+BH_DEV double swd_period_second(const SwdState &S, const SwdPerTab &T) { return T.tab[T.n + S.k - 1]; }
+BH_DEV float swd_period_t1a(const SwdState &S, const double *) { return S.t1a; }
+BH_DEV float swd_period_t1b(const SwdState &S, const double *) { return S.t1b; }
+BH_DEV float swd_period_t1a(const SwdState &S, const SwdPerTab &T) { return ((const float *)(T.tab + 2 * T.n))[S.k - 1]; }
+BH_DEV float swd_period_t1b(const SwdState &S, const SwdPerTab &T) { return ((const float *)(T.tab + 2 * T.n))[T.n + S.k - 1]; }
+
+// ---- the two common events of a search (bodies of swd_driver's branches) ---------------------------
+// A period begins (k <= kmax, k < ift): periods, start value and lower bound of the search,
+// surfdisp96.f:231-271.  Per: const double * or SwdPerTab, above.
+template <class Per>
+BH_DEV void swd_on_begin_period(SwdState &S, const SwdTargetDev &tg, const Per &per, int wss)
+{
     const double one = 1.0e-2;
     const double onea = 1.5;                        // dble(sone), sone = 1.5 (real*4)
     const double dc = (double)0.005f;               // dabs(dble(ddc)), ddc = 0.005 (real*4)
-    const float h = 0.005f;
-    double t1 = per[S.k - 1];
-    if (tg.igr > 0) {
-        S.t1a = (float)(t1 / (double)(1.f + h));
-        S.t1b = (float)(t1 / (double)(1.f - h));
-        t1 = (double)S.t1a;
-    } else {
-        S.t1a = (float)t1;
-    }
+    const double omega = swd_period_begin(S, tg, per);
     if (S.k == 1 && S.iq == 1) { S.c1 = S.cc; S.clow = S.cc; S.ifirst = 1; }
     else if (S.k == 1) { S.c1 = S.cws[0] + one * dc; S.clow = S.c1; S.ifirst = 1; }
     else if (S.iq > 1) {
@@ -591,7 +658,7 @@ BH_DEV void swd_on_begin_period(SwdState &S, const SwdTargetDev &tg, const doubl
         S.clow = S.cc;                        // clow = cm
     }
     S.pass = 0;
-    S.omega = TWOPI / t1;
+    S.omega = omega;
     S.ceval = S.c1;
     S.st = SWD_ST_A;
     S.ev = SWD_EV_NONE;
@@ -600,10 +667,9 @@ BH_DEV void swd_on_begin_period(SwdState &S, const SwdTargetDev &tg, const doubl
 // A root search has ended (SOLVED, or NOROOT on the second solve of a group-velocity pair): the
 // second solve is set up, or the period's value is stored and the next period announced,
 // surfdisp96.f:273-312.
-template <class Src>
-BH_DEV void swd_on_solved(SwdState &S, Src &src, const SwdTargetDev &tg, int wss)
+template <class Src, class Per>
+BH_DEV void swd_on_solved(SwdState &S, Src &src, const SwdTargetDev &tg, const Per &per, int wss)
 {
-    const double TWOPI = 2.0 * 3.141592653589793;
     const double one = 1.0e-2;
     const double onea = 1.5;
     const double dc = (double)0.005f;
@@ -613,12 +679,11 @@ BH_DEV void swd_on_solved(SwdState &S, Src &src, const SwdTargetDev &tg, int wss
         S.ck = S.c1;                          // c(k) = c1
         if (multimode) S.cws[(S.k - 1) * wss] = S.ck;
         if (igr > 0) {                        // second solve at t1b, surfdisp96.f:282-294
-            double t1 = (double)S.t1b;
             S.ifirst = 0;
             S.clow = (multimode ? S.cbws[(S.k - 1) * wss] : 0.0) + one * dc;
             S.c1 = S.c1 - onea * dc;
             S.pass = 1;
-            S.omega = TWOPI / t1;
+            S.omega = swd_period_second(S, per);
             S.ceval = S.c1;
             S.st = SWD_ST_A;
             S.ev = SWD_EV_NONE;
@@ -633,7 +698,8 @@ BH_DEV void swd_on_solved(SwdState &S, Src &src, const SwdTargetDev &tg, int wss
     if (igr == 0) {
         src.put(S, S.k, kmax, cc0);
     } else {
-        float gvel = (1 / S.t1a - 1 / S.t1b) / (1 / (S.t1a * cc0) - 1 / (S.t1b * cc1b));
+        const float t1a = swd_period_t1a(S, per), t1b = swd_period_t1b(S, per);
+        float gvel = (1 / t1a - 1 / t1b) / (1 / (t1a * cc0) - 1 / (t1b * cc1b));
         src.put(S, S.k, kmax, gvel);
     }
     S.cprev = S.ck;
@@ -722,7 +788,7 @@ BH_DEV void swd_driver(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
             if (S.k >= S.ift) { S.ev = SWD_EV_NOROOT; S.pass = 0; continue; }
             swd_on_begin_period(S, tg, per, wss);
         } else if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) {
-            swd_on_solved(S, src, tg, wss);
+            swd_on_solved(S, src, tg, per, wss);
         } else {
             swd_on_noroot(S, src, tg);
         }
@@ -738,7 +804,7 @@ template <class Lay, class Src>
 BH_DEV void swd_events(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
                        const double *BH_RESTRICT per, int wss, bool allow_fetch = true)
 {
-    if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) swd_on_solved(S, src, tg, wss);
+    if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) swd_on_solved(S, src, tg, per, wss);
     if (S.ev == SWD_EV_BEGIN_PERIOD && S.k <= tg.nper && S.k < S.ift) swd_on_begin_period(S, tg, per, wss);
     if (S.ev != SWD_EV_NONE) swd_driver(S, lay, src, tg, per, wss, allow_fetch);
 }
@@ -753,12 +819,11 @@ BH_DEV void swd_events(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
 // (As a loop inside the hot loop the driver kept a second set of registers for the search state and copied
 // the state into it and back at the loop's headers: 78 register moves and nothing else in three blocks,
 // DESIGN.md section 4.1.)
-template <class Lay, class Src>
-BH_DEV void swd_events_pass(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg,
-                            const double *BH_RESTRICT per, int wss)
+template <class Lay, class Src, class Per>
+BH_DEV void swd_events_pass(SwdState &S, Lay &lay, Src &src, const SwdTargetDev &tg, const Per &per, int wss)
 {
     const int kmax = tg.nper;
-    if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) swd_on_solved(S, src, tg, wss);
+    if (S.ev == SWD_EV_SOLVED || (S.ev == SWD_EV_NOROOT && S.pass == 1)) swd_on_solved(S, src, tg, per, wss);
     if (S.ev == SWD_EV_BEGIN_PERIOD && (S.k > kmax || S.k >= S.ift)) {
         if (S.k > kmax) swd_on_periods_done(S, src, tg);
         else { S.ev = SWD_EV_NOROOT; S.pass = 0; }
@@ -924,10 +989,9 @@ BH_DEV void swd_control(SwdState &S, double del, NevRegs &nv)
 // On the GPU `src` is a per-target atomic work queue: a lane whose search ends early pulls the next
 // model instead of idling until the slowest lane of its wave is done (searches take 388..851
 // evaluations on the bench models; static assignment wastes 15 % of the lane-cycles).
-// *ncalls (optional) counts period-equation evaluations.
-template <class Lay, class Src>
-BH_DEV void swd_lane(Lay &lay, Src &src, const SwdTargetDev &tg, const double *BH_RESTRICT per,
-                     int wss, long *ncalls)
+// *ncalls (optional) counts period-equation evaluations.  per: the target's periods or their table (SwdPerTab).
+template <class Lay, class Src, class Per>
+BH_DEV void swd_lane(Lay &lay, Src &src, const SwdTargetDev &tg, const Per &per, int wss, long *ncalls)
 {
     SwdState S;
     swd_state_init(S);
