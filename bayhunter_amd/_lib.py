@@ -12,10 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
-           "posterior_sets.hip", "datafits.hip", "math_probe.hip"]
+           "posterior_sets.hip", "datafits.hip", "moho.hip", "math_probe.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "stats_core.h",
-           "stats_host.h", "math_probe.h"]
+           "stats_host.h", "moho_core.h", "math_probe.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->
@@ -248,6 +248,10 @@ _SIGS = {
     "bh_datafits_scan": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _vp, _vp, _vp]),
     "bh_datafits_finish": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "bh_datafits_destroy": (None, [_vp]),
+    "bh_moho_rows": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double,
+                               _vp, _vp]),
+    "bh_moho_hist2d": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp, C.c_int, _vp, _vp]),
+    "bh_moho_sets": (C.c_int, [_vp, C.c_longlong, _vp, _vp, C.c_int, _vp, C.c_int] + [_vp] * 10),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -569,6 +569,15 @@ class ChainPool(object):
         from .datafits import pool_datafits
         return pool_datafits(self, selection, dev, exclude_outliers, q, nbins, device)
 
+    def moho(self, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50, device=None):
+        """Moho depth and crustal velocity over the rows posterior() uses (moho.summarize; the reference's
+        plot_moho_crustvel_tradeoff, src/Plotting.py:753-902, without the figure): per model the shallowest interface
+        inside the depth window `moho` = (zlo, zhi) -- default the depth prior, as there -- below which Vs exceeds
+        `mohovs`.  -> summarize()'s dict (median / mean / std / min / max / histogram of moho, vs_crust, vs_last,
+        vs_jump, the three joint histograms with their modes, nmodels, nexcluded) plus 'chains' (global indices used)."""
+        from .moho import pool_moho
+        return pool_moho(self, moho, mohovs, selection, dev, exclude_outliers, nbins, device)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

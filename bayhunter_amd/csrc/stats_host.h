@@ -120,6 +120,7 @@ struct DeviceSelect : RadixSelect {
 };
 
 // what is wrong with a scan's counts, in the words every entry point reports it (NULL: nothing)
+// (bayhunter_amd/moho.py recognises "empty selection" in a bh_datafits_scan error as "no row has a Moho": keep the words)
 inline const char *scan_fault(u64 included, u64 negative)
 {
     return negative ? "negative weight"

@@ -1,0 +1,206 @@
+"""Moho depth and crustal velocity of a block of sampled models, on the device (include/bayhunter_amd.h, bh_moho_*).
+
+What the reference computes in PlotFromStorage.plot_moho_crustvel_tradeoff (src/Plotting.py:753-902): per posterior
+model the Moho -- the shallowest interface inside a depth window below which Vs exceeds `mohovs` -- with the mean
+crustal Vs above it, the Vs of the last crustal layer and the Vs jump (:766-798); then medians, a standard deviation,
+four histograms and three joint histograms against the Moho depth with their modes (:813-865).
+
+Every row carries an integer weight; the result equals the reference's on the matrix in which each row is repeated
+`weight` times.  The per-row values are bit for bit numpy's on the row in its own dtype (csrc/moho_core.h); the
+statistics of one set of rows go through the weighted column reduction of datafits (bh_datafits_* over the four
+derived columns), the joint histograms and the per-station form through kernels of their own (csrc/moho.hip).
+Edges are made here with numpy as np.histogram / np.histogram2d make them.
+"""
+import numpy as np
+
+from . import _lib
+from .datafits import _Fits
+from .posterior import _to_device, _torch_device, pool_rows, station_rows
+
+NAMES = ('moho', 'vs_crust', 'vs_last', 'vs_jump')          # the columns of the derived matrix
+TRADEOFF = ('vs_last', 'vs_crust', 'vs_jump')               # x axes of the joint histograms, in the reference's order
+_COL = {name: c for c, name in enumerate(NAMES)}
+
+
+def _window(moho, mohovs, nbins):
+    zlo, zhi = (float(v) for v in moho)
+    mohovs = float(mohovs)
+    if not zlo < zhi or np.isnan(mohovs):
+        raise ValueError("moho: a depth window (zlo, zhi) with zlo < zhi; mohovs: a velocity")
+    if int(nbins) < 1:
+        raise ValueError("nbins >= 1")
+    return zlo, zhi, mohovs, int(nbins)
+
+
+def _rows_weights(models, weights, dev):
+    import torch
+    if not isinstance(models, torch.Tensor):
+        models = np.asarray(models)
+    if models.ndim != 2:
+        raise ValueError("models: [rows, 2*maxlayers]")
+    fdtype = torch.float32 if str(models.dtype).endswith('float32') else torch.float64
+    rows = _to_device(models, fdtype, dev)
+    w = None if weights is None else _to_device(weights, torch.int32, dev)
+    if w is not None and w.numel() != rows.shape[0]:
+        raise ValueError("one weight per row")
+    return rows, w
+
+
+def derive(rows, zlo, zhi, mohovs, stream):
+    """bh_moho_rows over a device tensor of rows -> D [rows, 4] float64 on the same device, queued on `stream`."""
+    import torch
+    if not (isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 2 and rows.shape[0] > 0
+            and rows.dtype in (torch.float32, torch.float64) and rows.stride(1) == 1 and rows.stride(0) >= rows.shape[1]):
+        raise ValueError("rows: a device tensor [rows, 2*maxlayers], float32 or float64, at least one row, "
+                         "contiguous along a row")
+    D = torch.empty((rows.shape[0], 4), dtype=torch.float64, device=rows.device)
+    _lib.check(_lib.load().bh_moho_rows(rows.data_ptr(), int(rows.dtype.itemsize == 8), rows.shape[0], rows.stride(0),
+                                        rows.shape[1], zlo, zhi, mohovs, D.data_ptr(), stream))
+    return D
+
+
+def outer_edges(vmin, vmax, nbins):
+    """np.histogram's / np.histogram2d's edges for `bins=nbins`: linspace(min, max), +-0.5 when they are equal."""
+    if vmin == vmax:
+        vmin, vmax = vmin - 0.5, vmax + 0.5
+    return np.linspace(vmin, vmax, nbins + 1)
+
+
+def _no_moho(zlo, zhi, mohovs):
+    return ValueError("no model has a Moho: no interface in the depth window (%g, %g) km with Vs > mohovs = %g km/s below it"
+                      % (zlo, zhi, mohovs))
+
+
+def summarize(models, weights=None, moho=(0., 100.), mohovs=4.2, nbins=50, device=None):
+    """Moho statistics of `models` ([rows, 2*maxlayers], reference layout, float32 or float64; numpy or a torch
+    tensor) with integer `weights` (>= 0, default 1 each), for the depth window moho = (zlo, zhi) and `mohovs`.
+
+    -> dict(nmodels (weighted rows with a Moho), nexcluded (weighted rows without one),
+            moho, vs_crust, vs_last, vs_jump = dict(median, mean, std, min, max, hist = (counts, edges)) each,
+            tradeoff = {vs_last, vs_crust, vs_jump: dict(counts [nbins, nbins] (x index first, as np.histogram2d),
+                        xedges, yedges, mode = (x, y): the cell centres of the first maximum in C order)})
+    ValueError when no row has a Moho."""
+    import torch
+    dev = _torch_device(device)
+    zlo, zhi, mohovs, nbins = _window(moho, mohovs, nbins)
+    rows, w = _rows_weights(models, weights, dev)
+    if rows.shape[0] == 0:
+        raise ValueError("empty selection: no models")
+    lib = _lib.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        D = derive(rows, zlo, zhi, mohovs, stream)
+        with _Fits(D, 4, w, None, stream) as f:
+            try:
+                s = f.scan()
+            except _lib.BayHunterAmdError as e:
+                if 'empty selection' in str(e):          # scan_fault()'s words (csrc/stats_host.h)
+                    raise _no_moho(zlo, zhi, mohovs)
+                raise
+            W = s['total']
+            edges = np.stack([outer_edges(s['vmin'][c], s['vmax'][c], nbins) for c in range(4)])
+            ost, hist, std = f.finish(np.array([(W - 1) // 2, W // 2], dtype=np.int64), edges, np.arange(4, dtype=np.int32))
+        xedges = np.ascontiguousarray(edges[[_COL[n] for n in TRADEOFF]])
+        h2 = np.zeros((3, nbins, nbins), dtype=np.int64)
+        _lib.check(lib.bh_moho_hist2d(D.data_ptr(), D.shape[0], None if w is None else w.data_ptr(), xedges.ctypes.data,
+                                      edges[0].ctypes.data, nbins + 1, h2.ctypes.data, stream))
+    median = (ost[0] + ost[1]) / 2.
+    res = dict(nmodels=W, nexcluded=s['excluded'], tradeoff={})
+    for c, name in enumerate(NAMES):
+        res[name] = dict(median=median[c], mean=s['mean'][c], std=std[c], min=s['vmin'][c], max=s['vmax'][c],
+                         hist=(hist[c], edges[c]))
+    yc = (edges[0][:-1] + edges[0][1:]) / 2.
+    for i, name in enumerate(TRADEOFF):
+        xi, yi = np.unravel_index(h2[i].argmax(), h2[i].shape)
+        xc = (xedges[i][:-1] + xedges[i][1:]) / 2.
+        res['tradeoff'][name] = dict(counts=h2[i], xedges=xedges[i], yedges=edges[0], mode=(xc[xi], yc[yi]))
+    return res
+
+
+def summarize_sets(models, set_start, weights=None, moho=(0., 100.), mohovs=4.2, nbins=50, device=None):
+    """summarize()'s numbers for every set of rows in one pass: set s is models[set_start[s]:set_start[s + 1]]
+    (set_start [sets + 1], ascending from 0 to the number of rows; a set may be empty).  One derivation launch and one
+    launch for the statistics of all sets.
+
+    -> dict(nmodels, nexcluded [sets] (weighted rows with / without a Moho), fraction [sets] (nmodels over both; NaN for
+            a set without weight), moho, vs_crust, vs_last, vs_jump = dict(median, mean, std, min, max [sets]) each,
+            hist [sets, nbins] of the Moho depth over the shared `edges` = linspace(zlo, zhi, nbins + 1)).
+    A set without a row that has a Moho is no error: nmodels 0, its statistics NaN, its histogram empty.  A negative
+    weight fails the call."""
+    import torch
+    dev = _torch_device(device)
+    zlo, zhi, mohovs, nbins = _window(moho, mohovs, nbins)
+    set_start = np.ascontiguousarray(set_start, dtype=np.int64)
+    S = set_start.size - 1
+    if not isinstance(models, torch.Tensor):
+        models = np.asarray(models)
+    nrows = models.shape[0] if models.ndim == 2 else -1
+    if set_start.ndim != 1 or S < 1 or set_start[0] != 0 or set_start[-1] != nrows or np.any(np.diff(set_start) < 0):
+        raise ValueError("set_start: [sets + 1], ascending from 0 to the number of rows")
+    rows, w = _rows_weights(models, weights, dev)
+    edges = np.linspace(zlo, zhi, nbins + 1)
+    cnt, nex = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64)
+    st = {k: np.full((S, 4), np.nan) for k in ('min', 'max', 'mean', 'std', 'lo', 'hi')}
+    hist = np.zeros((S, nbins), dtype=np.int64)
+    if rows.shape[0]:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        with torch.cuda.device(dev):
+            D = derive(rows, zlo, zhi, mohovs, stream)
+            _lib.check(_lib.load().bh_moho_sets(
+                D.data_ptr(), D.shape[0], None if w is None else w.data_ptr(), set_start.ctypes.data, S,
+                edges.ctypes.data, nbins + 1, cnt.ctypes.data, nex.ctypes.data, st['min'].ctypes.data,
+                st['max'].ctypes.data, st['mean'].ctypes.data, st['std'].ctypes.data, st['lo'].ctypes.data,
+                st['hi'].ctypes.data, hist.ctypes.data, stream))
+    median = (st['lo'] + st['hi']) / 2.
+    with np.errstate(invalid='ignore', divide='ignore'):
+        fraction = np.where(cnt + nex > 0, cnt / (cnt + nex).astype(np.float64), np.nan)
+    res = dict(nmodels=cnt, nexcluded=nex, fraction=fraction, hist=hist, edges=edges)
+    for c, name in enumerate(NAMES):
+        res[name] = dict(median=median[:, c].copy(), mean=st['mean'][:, c].copy(), std=st['std'][:, c].copy(),
+                         min=st['min'][:, c].copy(), max=st['max'][:, c].copy())
+    return res
+
+
+def _widened(models, device):
+    """A pool's float32 rows on the device as float64: save() writes them as float64 (the reference fills float64
+    matrices, src/Models.py:228-274), so that is the dtype in which PlotFromStorage derives the Moho from them."""
+    import torch
+    return _to_device(models, torch.float32 if models.dtype == np.float32 else torch.float64,
+                      _torch_device(device)).to(torch.float64)
+
+
+def pool_moho(pool, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50, device=None):
+    """ChainPool.moho: summarize() over the rows ChainPool.posterior uses, plus 'chains' (global indices used)."""
+    ci, ri, w = pool_rows(pool, selection, dev, exclude_outliers)
+    res = summarize(_widened(pool.models[ci, ri], device), w.astype(np.int32), pool.priors['z'] if moho is None else moho,
+                    mohovs, nbins, device)
+    res['chains'] = np.unique(ci) + pool.first
+    return res
+
+
+class StationMoho(object):
+    """StationPool.moho's result, every array in the pool's station order.
+
+    names      the stations
+    moho, vs_crust, vs_last, vs_jump   dict(median, mean, std, min, max [nstations]) each; NaN for a station without a
+               model that has a Moho (a hole of the Moho map) and for a failed one
+    nmodels, nexcluded [nstations]     weighted rows with / without a Moho
+    fraction [nstations]               nmodels / (nmodels + nexcluded)
+    hist [nstations, nbins], edges     the Moho depth over edges all stations share: linspace(zlo, zhi, nbins + 1)
+    failed     {station name: message}, as StationPool.posterior reports it (such a station has no rows)"""
+
+    def __init__(self, names, res, failed):
+        self.names = list(names)
+        self.failed = {names[z]: msg for z, msg in failed.items()}
+        for k, v in res.items():
+            setattr(self, k, v)
+
+
+def stations_moho(spool, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50,
+                  device=None):
+    """StationPool.moho: summarize_sets() over every station's main-phase rows."""
+    pool, c = spool.pool, spool.chains_per_station
+    ci, ri, w, set_start, failed = station_rows(pool, c, selection, dev, exclude_outliers)
+    res = summarize_sets(_widened(pool.models[ci, ri], device), set_start, w.astype(np.int32),
+                         pool.priors['z'] if moho is None else moho, mohovs, nbins, device)
+    return StationMoho(spool.names, res, failed)

@@ -221,7 +221,7 @@ def _takes_station(fn):
 class StationView(ChainPool):
     """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
     noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
-    datafits(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
+    datafits(), moho(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
 
     def __init__(self, pool, s):
         inner, c = pool.pool, pool.chains_per_station
@@ -422,6 +422,16 @@ class StationPool(object):
         failed station is a ValueError naming the first one."""
         from .posterior import stations_posterior
         return stations_posterior(self, dep_int, depint, dev, exclude_outliers, selection, device, strict)
+
+    def moho(self, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50, device=None):
+        """Moho depth +- std, crustal Vs and the share of models with a Moho of every station in one pass over the
+        pool's rows (moho.summarize_sets: one launch derives every row, one reduces all stations): per station the
+        numbers station(s).moho(...) reports.  -> moho.StationMoho: `names`, `moho / vs_crust / vs_last / vs_jump`
+        = dict(median, mean, std, min, max [nstations]), `nmodels`, `nexcluded`, `fraction [nstations]`, `hist
+        [nstations, nbins]` of the Moho depth over the shared `edges`, `failed` {name: message}.  A station without a
+        model that has a Moho is a hole of the map (NaN, nmodels 0), not an error."""
+        from .moho import stations_moho
+        return stations_moho(self, moho, mohovs, selection, dev, exclude_outliers, nbins, device)
 
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone

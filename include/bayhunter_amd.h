@@ -647,6 +647,41 @@ int  bh_datafits_finish(bh_datafits *fits, const long long *ranks, int nranks, d
                         double *stdev);
 void bh_datafits_destroy(bh_datafits *fits);
 
+/* ---- Moho depth and crustal velocity ------------------------------------------------------ */
+/* What PlotFromStorage.plot_moho_crustvel_tradeoff (src/Plotting.py:753-902) derives from every posterior model
+ * and then summarises, over rows that each carry an integer weight.
+ *
+ *   bh_moho_rows     rows as for bh_posterior_create (DEVICE, reference layout, float32 or float64) -> out, DEVICE
+ *                    float64 [nrows][4] = (moho, vs_crust, vs_last, vs_jump) per row: the Moho is the first
+ *                    interface i with zlo < depth_i < zhi and vs[i+1] > mohovs (both strict, the velocity compared
+ *                    in the rows' type), vs_crust the thickness-weighted mean Vs above it, vs_last = vs[i],
+ *                    vs_jump = vs[i+1] - vs[i]; four NaN for a row without one.  Bit for bit what numpy computes
+ *                    from the row in the row's own type (Plotting.py:766-798).  Queued on `stream`, not waited for.
+ *                    BH_ERR_ARG for no rows, width / stride as there, zlo >= zhi, a NaN parameter.
+ *   bh_moho_hist2d   the three joint histograms of Plotting.py:830-835 over D = bh_moho_rows' out with DEVICE int32
+ *                    weights (NULL: ones): HOST xedges[3][nedges] for vs_last, vs_crust, vs_jump, yedges[nedges]
+ *                    for moho (ascending; numpy's bin rule as in bh_datafits_finish) -> HOST hist[3][nb][nb],
+ *                    nb = nedges - 1, the x bin first.  Rows with a NaN or weight 0 are skipped; a negative weight
+ *                    is BH_ERR_ARG.
+ *   bh_moho_sets     the rows in nsets contiguous sets (HOST set_start[nsets + 1], from 0 to nrows, ascending; a
+ *                    set may be empty), all in one launch.  HOST outputs, each optional: with_moho / without
+ *                    [nsets] the weight of the set's rows with and without a Moho; vmin, vmax, mean, stdev
+ *                    (population), medlo, medhi [nsets][4] per column of D -- the last two the order statistics of
+ *                    0-based ranks (W - 1) / 2 and W / 2 of the expanded column, whose mean is numpy's median;
+ *                    with HOST edges[nedges] (ascending, shared by all sets), hist[nsets][nedges - 1] of the Moho
+ *                    depth.  A set without a row that has a Moho is no error: its counts are 0, its statistics
+ *                    NaN.  A negative weight anywhere is BH_ERR_ARG.
+ * The statistics of one set of rows are bh_datafits_* over D (Y = D, stride = ncols = 4, no err flags): a row of
+ * NaN is an excluded row there.  Host outputs are there when a call returns; two runs are bit-identical. */
+int  bh_moho_rows(const void *rows, int fp64, long long nrows, long long stride, int width, double zlo, double zhi,
+                  double mohovs, double *out, void *stream);
+int  bh_moho_hist2d(const double *D, long long nrows, const int *weights, const double *xedges,
+                    const double *yedges, int nedges, long long *hist, void *stream);
+int  bh_moho_sets(const double *D, long long nrows, const int *weights, const long long *set_start, int nsets,
+                  const double *edges, int nedges, long long *with_moho, long long *without, double *vmin,
+                  double *vmax, double *mean, double *stdev, double *medlo, double *medhi, long long *hist,
+                  void *stream);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);

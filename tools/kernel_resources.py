@@ -13,7 +13,8 @@ from bayhunter_amd import _lib  # noqa: E402
 
 
 def kernel_resources(source='kernels.hip'):
-    """{demangled-ish kernel name: dict(vgpr, sgpr, scratch)} from the .amdhsa_kernel descriptors."""
+    """{demangled-ish kernel name: dict(vgpr, sgpr, scratch, lds)} from the .amdhsa_kernel descriptors (lds: the
+    static LDS of a workgroup in bytes; what a launch adds dynamically is not in the descriptor)."""
     with tempfile.TemporaryDirectory() as td:
         asm = os.path.join(td, 'k.s')
         flags = [f for f in _lib.HIPCC_FLAGS if f not in ('-shared', '-fPIC')]
@@ -29,7 +30,7 @@ def kernel_resources(source='kernels.hip'):
         # 'rf_kernel<false, true>'
         name = name.replace('ILb0ELb0EE', '<false>').replace('ILb1ELb0EE', '<true>').replace('ILb0ELb1EE', '<false, true>')
         out[name] = dict(vgpr=field('next_free_vgpr'), sgpr=field('next_free_sgpr'),
-                         scratch=field('private_segment_fixed_size'))
+                         scratch=field('private_segment_fixed_size'), lds=field('group_segment_fixed_size'))
     return out
 
 
