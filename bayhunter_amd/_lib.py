@@ -12,10 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
-           "posterior_sets.hip", "datafits.hip", "moho.hip", "math_probe.hip"]
+           "posterior_sets.hip", "datafits.hip", "moho.hip", "math_probe.hip", "rf_probe.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "stats_core.h",
-           "stats_host.h", "moho_core.h", "math_probe.h"]
+           "stats_host.h", "moho_core.h", "math_probe.h", "rf_fft.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->
@@ -222,6 +222,8 @@ _SIGS = {
                            C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bh_selftest_division": (C.c_int, [C.c_long, C.c_uint, C.c_int, C.POINTER(C.c_long)]),
     "bh_selftest_math": (C.c_int, [C.c_int, C.c_long, _vp, _vp]),
+    "bh_rf_twiddles": (C.c_int, [C.c_int, _vp]),
+    "bh_selftest_rf_transform": (C.c_int, [C.c_int] * 5 + [_vp, C.c_int, _vp]),
     "bh_malloc": (C.c_int, [C.POINTER(_vp), C.c_size_t]),
     "bh_free": (C.c_int, [_vp]),
     "bh_memcpy_h2d": (C.c_int, [_vp, _vp, C.c_size_t, _vp]),

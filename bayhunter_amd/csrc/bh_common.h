@@ -169,7 +169,20 @@ BH_DEV cd mk(double re, double im) { cd r; r.re = re; r.im = im; return r; }
 BH_DEV cd operator+(cd a, cd b) { return mk(a.re + b.re, a.im + b.im); }
 BH_DEV cd operator-(cd a, cd b) { return mk(a.re - b.re, a.im - b.im); }
 BH_DEV cd operator-(cd a) { return mk(-a.re, -a.im); }
+#if defined(BH_HOSTSIM) && defined(BH_HOSTSIM_FUSED_CMUL)
+// The device compiles this operator under contract(fast) above, and the flag goes with the operator's instructions into
+// every caller -- phase 4's butterflies included, whose own sums stay separate additions (rf_core.h).  What the compiler
+// makes of the two halves there (the listing of rf_block_fft: v_mul, v_mul, v_fma, v_fmac per product) is
+// fma(a.re, b.re, -(a.im b.im)) and fma(a.im, b.re, a.re b.im) -- the real part as cmul (below) writes it, the imaginary
+// part with the other product rounded.  A host build that is to return the device's bits for a sequence of such products
+// (tests/hostsim/rf_transform_sim.cpp) asks for that form; tests/test_gpu_rf_transform.py is what holds it to the device.
+BH_DEV cd operator*(cd a, cd b)
+{
+    return mk(__builtin_fma(a.re, b.re, -(a.im * b.im)), __builtin_fma(a.im, b.re, a.re * b.im));
+}
+#else
 BH_DEV cd operator*(cd a, cd b) { return mk(a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re); }
+#endif
 BH_DEV cd operator*(cd a, double r) { return mk(a.re * r, a.im * r); }
 BH_DEV cd operator*(double r, cd a) { return mk(a.re * r, a.im * r); }
 BH_DEV cd operator/(cd a, double r) { return mk(a.re / r, a.im / r); }

@@ -1171,6 +1171,53 @@ int bh_selftest_math(int op, long n, const double *in, double *out)
     return BH_OK;
 }
 
+// The twiddle table as this library's host code builds it (rf_host.h: rf_fill_twiddles; get_twiddles uploads the same
+// doubles).  No device work.  The values are glibc's, but which of its functions a compiler calls for std::exp(complex)
+// is the compiler's choice, and two builds of rf_fill_twiddles need not agree in the last bit of every entry: a test
+// that wants the device's bits takes the table from here.
+int bh_rf_twiddles(int nsamp, double *tw)
+{
+    if (nsamp < 8 || nsamp > 4096 || (nsamp & (nsamp - 1))) return fail_arg("nsamp must be a power of two in 8..4096");
+    if (!tw) return fail_arg("NULL pointer");
+    bh::rf_fill_twiddles(tw, nsamp);
+    return BH_OK;
+}
+
+// Phase 4 of rf_kernel alone (rf_probe.hip) on B half spectra, M per workgroup, with the launch constants of
+// rf_fill_launch and the cached twiddle table that bh_rf_batch's launches use.  The output buffer is NaN (all bits set)
+// where the kernel does not write.
+int bh_selftest_rf_transform(int nsamp, int Lmax, int M, int B, int paired, const double *spec, int nout, double *out)
+{
+    if (nsamp < 8 || nsamp > 4096 || (nsamp & (nsamp - 1))) return fail_arg("nsamp must be a power of two in 8..4096");
+    if (Lmax < 1 || Lmax > BH_MAX_LAYERS) return fail_arg("Lmax out of range");
+    if (M < 1 || M > 8) return fail_arg("M must be 1..8");
+    if (B < 0 || B > (1 << 20)) return fail_arg("B out of range");
+    if (nout < 1 || nout > nsamp) return fail_arg("nout out of range");
+    if (!spec || !out) return fail_arg("NULL pointer");
+    if (bh::rf_lds_bytes(Lmax, nsamp, M, paired != 0) > 160 * 1024) return fail_arg("buffers do not fit LDS");
+    int rc = ensure_device();
+    if (rc) return rc;
+    if (B == 0) return BH_OK;
+    bh::RfLaunch P = bh::RfLaunch();
+    bh::rf_fill_launch(P, 0.0, 1.0, nsamp, 1.0, 0.0, -1.0, 0, nout);      // sc, qn, log2n, nfreq: all phase 4 reads
+    P.Lmax = Lmax;
+    P.M = M;
+    const double *tw = nullptr;
+    rc = get_twiddles(nsamp, &tw);
+    if (rc) return rc;
+    const size_t nch = paired ? 2 : 1;
+    const size_t bin = (size_t)B * nch * P.nfreq * 2 * sizeof(double), bout = (size_t)B * nch * nout * sizeof(double);
+    char *d = nullptr;
+    BH_HIP(hipMalloc((void **)&d, bin + bout));
+    hipError_t e = hipMemset(d + bin, 0xff, bout);
+    if (e == hipSuccess) e = hipMemcpy(d, spec, bin, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = bh::launch_rf_probe(P, B, paired ? 1 : 0, (const double *)d, tw, (double *)(d + bin), nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d + bin, bout, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    BH_HIP(e);
+    return BH_OK;
+}
+
 // ---- plumbing ----------------------------------------------------------------------------------
 int bh_malloc(void **dptr, size_t bytes)
 {

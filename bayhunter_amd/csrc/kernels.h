@@ -135,5 +135,9 @@ hipError_t launch_swd_team(const SwdArgs &A, int team_lanes, int resident_waves,
 size_t swd_team_lds_bytes(int Lmax, int team_lanes);
 hipError_t launch_rf(const RfArgs &A, hipStream_t stream);
 size_t rf_lds_bytes(int Lmax, int nsamp, int M, bool zr = false);
+// Phase 4 of rf_kernel alone (rf_probe.hip, bh_selftest_rf_transform): B buffers, P.M per workgroup at the pitch of
+// rf_layout(P.Lmax, P.nsamp); spec [B][paired ? 2 : 1][P.nfreq][2], out [B][paired ? 2 : 1][P.nout], device pointers
+hipError_t launch_rf_probe(const RfLaunch &P, int B, int paired, const double *spec, const double *tw, double *out,
+                           hipStream_t stream);
 
 }  // namespace bh

@@ -14,6 +14,7 @@
 #include "../../include/bayhunter_amd.h"
 #include "kernels.h"
 #include "rf_core.h"
+#include "rf_fft.h"
 #include "swd_core.h"
 #include "swd_team.h"
 
@@ -915,37 +916,7 @@ __global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team16_kernel(SwdArg
 __global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team8_kernel(SwdArgs A) { swd_tpl_body<8>(A); }
 
 // -------------------------------------------------------------------------------------------- RF
-// bit reversal (+ 1/sqrt(n)) and the butterfly passes (rf_core.h: one radix-2 stage when log2 n is odd, radix-4 passes
-// of two stages each for the rest) of Mb buffers in LDS; all threads of the group
-__device__ __forceinline__ void rf_block_fft(double *S, int per_model, int Mb, int n, const RfLaunch &P,
-                                             const double *tw, int tid)
-{
-#if !(defined(BH_RF_EXP) && BH_RF_EXP == 1)
-    for (int idx = tid; idx < Mb * n; idx += RF_T) {
-        int m = idx / n, i = idx - m * n;
-        rf_fft_bitrev_scale(S + (long)m * per_model, n, P.log2n, P.sc, i);
-    }
-    __syncthreads();
-#endif
-#if defined(BH_RF_EXP) && BH_RF_EXP == 2
-    return;
-#endif
-    if (rf_fft_radix2_first(P.log2n)) {              // odd log2 n: one radix-2 stage, the rest in pairs
-        for (int idx = tid; idx < Mb * (n / 2); idx += RF_T) {
-            int m = idx / (n / 2), bf = idx - m * (n / 2);
-            rf_fft_butterfly(S + (long)m * per_model, tw, 1, bf);
-        }
-        __syncthreads();
-    }
-    for (int l = rf_fft_radix4_first(P.log2n); 4 * l <= n; l <<= 2) {
-        for (int idx = tid; idx < Mb * (n / 4); idx += RF_T) {
-            int m = idx / (n / 4), bf = idx - m * (n / 4);
-            rf_fft_butterfly4(S + (long)m * per_model, tw, l, bf);
-        }
-        __syncthreads();
-    }
-}
-
+// (rf_block_fft, phase 4's transform of the workgroup's buffers: rf_fft.h, shared with rf_probe.hip)
 // 4 waves per SIMD (128 VGPRs, nothing spilled): alone the recursion is latency-bound at 2 and equally fast
 // at 3 or 4; at 128 VGPRs a workgroup also fits beside swd_kernel's two waves per SIMD (capi.hip: pick_rf_M).
 // ZR: also keep the filtered vertical/radial spectra and return their traces (synrf_cwrap's fz, fr).

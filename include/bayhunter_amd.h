@@ -343,6 +343,27 @@ int bh_selftest_division(long n, unsigned seed, int max_exp, long *mismatches);
  * and with extended precision. */
 int bh_selftest_math(int op, long n, const double *in /* host, [n][6] */, double *out /* host, [n][4] */);
 
+/* The inverse transform of the receiver-function kernel (phase 4 of rf_kernel: Hermitian extension, bit reversal with
+ * the 1/sqrt(n) scale, the radix-2 / radix-4 passes, the scaled output) alone, on half spectra the caller gives, by the
+ * kernel's own functions: workgroups of 256 threads hold M buffers each at the pitch a launch with Lmax layers and
+ * nsamp samples gives a model, B buffers in all (the last workgroup may be partial).  spec holds nsamp/2 + 1 complex
+ * bins (re, im) per buffer; out[b][0][i], i < nout, is sample i of the real inverse transform of buffer b,
+ * y[k] = (1/n) sum_j x[j] exp(+2 pi i j k / n) with x[n - j] = conj(x[j]), real part.  paired != 0: two spectra per buffer
+ * and the trace form's paired transform (iftr2) of x1 + i x2 behind the single one: out[b][0] its real and out[b][1] its
+ * imaginary part (the imaginary parts of x2's DC and Nyquist bins enter out[b][0] negated, those of x1 enter
+ * out[b][1]).  spec and out are host arrays; the call allocates, copies in, launches on the null stream, copies back and
+ * frees.  BH_ERR_ARG when nsamp is no power of two in 8 .. 4096, Lmax outside 1 .. BH_MAX_LAYERS, M outside 1 .. 8,
+ * nout outside 1 .. nsamp, B < 0, a pointer null, or M buffers need more than the 160 KiB of LDS the library's own
+ * launches allow.  A self-test, not part of the forward path: tests/test_gpu_rf_transform.py compares the result with
+ * the host build of the same functions bit for bit, tests/test_rf_transform.py that build with extended precision. */
+/* The table of twiddle factors the receiver-function kernel reads, as the library's host code computes it:
+ * tw[2 (l + m)], tw[2 (l + m) + 1] = exp(i pi m / l) for l = 1, 2, 4, .., nsamp / 2 and m < l; tw holds 2 nsamp doubles
+ * (host).  No device work.  BH_ERR_ARG for nsamp no power of two in 8 .. 4096 or a null pointer. */
+int bh_rf_twiddles(int nsamp, double *tw /* host, [2 nsamp] */);
+int bh_selftest_rf_transform(int nsamp, int Lmax, int M, int B, int paired,
+                             const double *spec /* host, [B][paired ? 2 : 1][nsamp/2 + 1][2] */, int nout,
+                             double *out /* host, [B][paired ? 2 : 1][nout] */);
+
 /* ---- lock-step chain pool (host side of the sampler) ------------------------------------ */
 /* Replaces the per-process loop `while iiter < iter_phase2: SingleChain.iterate()`
  * (src/SingleChain.py:511-589,591-606) for MANY chains advanced together, so that every iteration

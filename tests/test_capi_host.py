@@ -249,6 +249,7 @@ def test_no_switches_beyond_the_kept_ones():
     experiment leaves the tree with its switch; the ones that were removed stay out of the package and the tools."""
     keep = {
         'BH_HOSTSIM', 'BH_HOSTSIM_GLIBC_MATH', 'BH_SRC_HASH',              # structural
+        'BH_HOSTSIM_FUSED_CMUL',                                           # host builds only: tests/hostsim/rf_transform_sim.cpp
         'BH_LANE_PROFILE', 'BH_TEAM_PROFILE',                              # tools/lane_phase_profile.py, team_phase_profile.py
         'BH_RF_EXP', 'BH_RF_NO_PAD',                                       # tools/rf_probe.py
         'SWD_TEAMW_MIDROOM', 'SWD_TEAMW_CHAIN_MAX', 'SWD_TEAMW_NPM',       # tools/replay_rounds.py

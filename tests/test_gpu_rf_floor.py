@@ -87,7 +87,7 @@ def test_layer_counts(lib, L):
     assert _close(_gpu(lib, *m), _host(*m), 'L = %d' % L) == 4
 
 
-@pytest.mark.parametrize('nsamp', [128, 256, 512, 1024])
+@pytest.mark.parametrize('nsamp', [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096])
 def test_transform_lengths(lib, nsamp):
     """log2 n odd (128, 512: a radix-2 stage, then radix-4 passes) and even (256, 1024: radix-4 passes only)"""
     m = draw_models(4, (3, 10), seed=60 + nsamp, Lmax=10)
