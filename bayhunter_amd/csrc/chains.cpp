@@ -35,9 +35,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/bayhunter_amd.h"
-
-namespace bh { int fail_arg_(const char *what); }
+#include "host_common.h"
 
 namespace {
 

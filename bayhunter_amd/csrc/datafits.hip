@@ -21,6 +21,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include "host_common.h"
 #include "stats_host.h"
 
 namespace {
@@ -249,7 +250,7 @@ int launch(bh_datafits *p, const FitArgs &a, int gz, size_t lds)
 {
     dim3 grid((unsigned)p->G, (unsigned)((p->n + kCols - 1) / kCols), (unsigned)gz);
     hipLaunchKernelGGL((df_kernel<MODE>), grid, dim3(kThreads), lds, p->st, a);
-    STATS_HIP(hipGetLastError());
+    BH_HIP(hipGetLastError());
     return BH_OK;
 }
 
@@ -267,11 +268,7 @@ int bh_datafits_create(const double *Y, long long nrows, long long stride, int n
     if (ncols < 1) return bh::fail_arg_("bh_datafits_create: ncols < 1");
     if (stride < ncols) return bh::fail_arg_("bh_datafits_create: stride < ncols");
     if (err && nerr < 1) return bh::fail_arg_("bh_datafits_create: err flags given with nerr < 1");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
-        return BH_ERR_NO_DEVICE;
-    }
+    if (int rc = bh::require_device()) return rc;
     std::unique_ptr<bh_datafits> p(new (std::nothrow) bh_datafits);
     if (!p) return bh::fail_arg_("out of memory");
     p->Y = Y;
@@ -286,8 +283,8 @@ int bh_datafits_create(const double *Y, long long nrows, long long stride, int n
     p->G = (int)(g < kMaxBlocksX ? g : kMaxBlocksX);
     int rc = p->alloc_columns();
     if (rc) return rc;
-    STATS_HIP(p->bufs.alloc(p->wk, (size_t)nrows));
-    STATS_HIP(p->bufs.alloc(p->cnt, 3));
+    BH_HIP(p->bufs.alloc(p->wk, (size_t)nrows));
+    BH_HIP(p->bufs.alloc(p->cnt, 3));
     *fits = p.release();
     return BH_OK;
 }
@@ -306,13 +303,13 @@ int bh_datafits_scan(bh_datafits *p, long long *total, long long *excluded, doub
     if (!p) return bh::fail_arg_("fits is NULL");
     int rc = p->begin_scan();
     if (rc) return rc;
-    STATS_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 3, p->st));
+    BH_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 3, p->st));
     {
         long long waves = p->nrows;
         long long blocks = (waves + kThreads / 64 - 1) / (kThreads / 64);
         hipLaunchKernelGGL(df_mask_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kThreads), 0, p->st,
                            p->Y, p->nrows, p->stride, p->n, p->w, p->err, p->nerr, p->wk, p->cnt);
-        STATS_HIP(hipGetLastError());
+        BH_HIP(hipGetLastError());
     }
     FitArgs a = base_args(p);
     a.kmin = p->kmin;
@@ -320,7 +317,7 @@ int bh_datafits_scan(bh_datafits *p, long long *total, long long *excluded, doub
     rc = launch<MODE_SCAN>(p, a, 1, 0);
     if (rc) return rc;
     u64 cnt[3];                                    // included, excluded weight; rows with a negative weight
-    STATS_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
+    BH_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
     std::vector<double> sum;
     rc = p->reduce_slab(sum);                      // synchronises the stream
     if (rc) return rc;
@@ -364,12 +361,12 @@ int bh_datafits_finish(bh_datafits *p, const long long *ranks, int nranks, doubl
         if (want_hist) {
             double *ded = nullptr;
             int *dset = nullptr;
-            STATS_HIP(tmp.alloc(ded, (size_t)nsets * nedges));
-            STATS_HIP(tmp.alloc(dset, N));
-            STATS_HIP(tmp.alloc(a.hist, (size_t)N * nb));
-            STATS_HIP(hipMemcpyAsync(ded, edges, sizeof(double) * (size_t)nsets * nedges, hipMemcpyHostToDevice, p->st));
-            STATS_HIP(hipMemcpyAsync(dset, eset, sizeof(int) * N, hipMemcpyHostToDevice, p->st));
-            STATS_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * (size_t)N * nb, p->st));
+            BH_HIP(tmp.alloc(ded, (size_t)nsets * nedges));
+            BH_HIP(tmp.alloc(dset, N));
+            BH_HIP(tmp.alloc(a.hist, (size_t)N * nb));
+            BH_HIP(hipMemcpyAsync(ded, edges, sizeof(double) * (size_t)nsets * nedges, hipMemcpyHostToDevice, p->st));
+            BH_HIP(hipMemcpyAsync(dset, eset, sizeof(int) * N, hipMemcpyHostToDevice, p->st));
+            BH_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * (size_t)N * nb, p->st));
             a.edges = ded;
             a.nedges = nedges;
             a.eset = dset;

@@ -18,28 +18,9 @@
 #include <new>
 #include <string>
 #include <vector>
-#include "../../include/bayhunter_amd.h"
-
-namespace bh {   // capi.hip
-int fail_arg_(const char *what); int fail_hip_(int e, const char *what);
-int check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool zr);
-int like_gaps_derive(const char *who, int nsets, int set_stride, int ntargets, const bh_like_target *targets,
-                     const unsigned char *set_present, std::vector<int> &tables, bool *any_gap);
-int likelihood_sets_(int stages, int B, int ntargets, const bh_like_target *targets, const double *out, int out_stride,
-                     const int *err, int nflags, int nsets, const int *obs_id, const double *yobs, int set_stride,
-                     const double *set_scale, const double *set_logdet, const double *noise, const double *aux,
-                     double *logL, double *misfits, void *workspace, size_t workspace_bytes,
-                     const unsigned char *set_present, void *gaps_workspace, size_t gaps_workspace_bytes,
-                     const int *gap_cols, const int *gap_cnt, void *stream); }
-extern "C" const char *bh_last_error(void);
+#include "host_common.h"
 
 namespace {
-
-#define EP_HIP(call)                                                         \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) return bh::fail_hip_((int)e_, #call);          \
-    } while (0)
 
 constexpr int kOrderMin = 1024;   // up to this every team is resident at once: order is irrelevant (layout.py: ORDER_MIN)
 
@@ -141,8 +122,8 @@ static void plan_free(bh_eval_plan *p)
 template <class T>
 static int upload(T **d, const T *h, size_t n)
 {
-    EP_HIP(hipMalloc((void **)d, std::max<size_t>(n, 1) * sizeof(T)));
-    if (n) EP_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
+    BH_HIP(hipMalloc((void **)d, std::max<size_t>(n, 1) * sizeof(T)));
+    if (n) BH_HIP(hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice));
     return BH_OK;
 }
 
@@ -174,11 +155,7 @@ int bh_eval_create(int max_models, int Lmax, int row, int nswd, const bh_swd_tar
     if ((nswd && (!swd || !periods)) || (nrf && !rf) || (ninterp && !interp)) return bh::fail_arg_("NULL pointer");
     if (nflags != (nswd > 0 ? nswd : 1)) return bh::fail_arg_("nflags must be the number of dispersion targets (1 without any)");
     if (int rc = check_interp(nswd, swd, row, ninterp, interp)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
-        return BH_ERR_NO_DEVICE;
-    }
+    if (int rc = bh::require_device()) return rc;
     bh_eval_plan *p = new (std::nothrow) bh_eval_plan;
     if (!p) return bh::fail_arg_("out of memory");
     int rc = BH_OK;
@@ -307,12 +284,12 @@ static int forward_batch(int B, int Lmax, int model_stride, const int *nlay, con
             const long n = (long)B * interp[i].n_dst;
             hipLaunchKernelGGL(interp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B,
                                out, out_stride, periods + t.per_off, t.nper, t.out_off, interp[i]);
-            EP_HIP(hipGetLastError());
+            BH_HIP(hipGetLastError());
         }
     } else {
         hipLaunchKernelGGL(depth_flags_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B,
                            nlay, Lmax, err);
-        EP_HIP(hipGetLastError());
+        BH_HIP(hipGetLastError());
     }
     for (int i = 0; i < nrf; i++) {
         rc = rf_set_p ? bh_rf_batch_sets(B, Lmax, model_stride, nlay, h, vp, vs, rho, nullptr, nullptr, rf + i, nsets,
@@ -342,7 +319,7 @@ int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const d
 // the launches of one submission; `forked` tells the caller whether the side stream was made to wait
 static int submit_batch(bh_eval_plan *p, int count, bool *forked)
 {
-    EP_HIP(hipSetDevice(p->dev));
+    BH_HIP(hipSetDevice(p->dev));
     const int L = p->Lmax, T = p->T;
     const int *hnlay = (const int *)(p->hblock + p->off_nlay);
     int depth = 1;
@@ -363,16 +340,16 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
         }
     }
     if (p->rows <= 16384) {
-        EP_HIP(hipMemcpyAsync(p->dblock, p->hblock, (sets ? p->off_set : p->off_nlay) + (size_t)count * sizeof(int),
+        BH_HIP(hipMemcpyAsync(p->dblock, p->hblock, (sets ? p->off_set : p->off_nlay) + (size_t)count * sizeof(int),
                               hipMemcpyHostToDevice, p->st));
     } else {
         if (sets)
-            EP_HIP(hipMemcpyAsync(p->dblock + p->off_set, p->hblock + p->off_set, (size_t)count * sizeof(int),
+            BH_HIP(hipMemcpyAsync(p->dblock + p->off_set, p->hblock + p->off_set, (size_t)count * sizeof(int),
                                   hipMemcpyHostToDevice, p->st));
-        EP_HIP(hipMemcpyAsync(p->dblock, p->hblock, (size_t)count * 4 * L * sizeof(double), hipMemcpyHostToDevice, p->st));
-        EP_HIP(hipMemcpyAsync(p->dblock + p->off_noise, p->hblock + p->off_noise, (size_t)count * 2 * T * sizeof(double),
+        BH_HIP(hipMemcpyAsync(p->dblock, p->hblock, (size_t)count * 4 * L * sizeof(double), hipMemcpyHostToDevice, p->st));
+        BH_HIP(hipMemcpyAsync(p->dblock + p->off_noise, p->hblock + p->off_noise, (size_t)count * 2 * T * sizeof(double),
                               hipMemcpyHostToDevice, p->st));
-        EP_HIP(hipMemcpyAsync(p->dblock + p->off_nlay, p->hblock + p->off_nlay, (size_t)count * sizeof(int),
+        BH_HIP(hipMemcpyAsync(p->dblock + p->off_nlay, p->hblock + p->off_nlay, (size_t)count * sizeof(int),
                               hipMemcpyHostToDevice, p->st));
     }
     const double *dm = (const double *)p->dblock;
@@ -383,15 +360,15 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
     int rc;
     const bool overlap = p->nswd > 0 && p->nrf > 0;
     if (overlap) {
-        EP_HIP(hipEventRecord(p->fork, p->st));
-        EP_HIP(hipStreamWaitEvent(p->side, p->fork, 0));
+        BH_HIP(hipEventRecord(p->fork, p->st));
+        BH_HIP(hipStreamWaitEvent(p->side, p->fork, 0));
         *forked = true;
     }
     const int *order = nullptr;
     if (p->nswd && count > kOrderMin) {   // deepest first, longest searches first, alike neighbours (engine.reorder)
         if ((rc = bh_swd_order_keys(count, L, 4 * L, dnlay, h, vs, p->tmax, 1, p->keys, p->st))) return rc;
         size_t bytes = p->sort_bytes;
-        EP_HIP(rocprim::radix_sort_pairs(p->sort_tmp, bytes, p->keys, p->keys_out, p->iota, p->order,
+        BH_HIP(rocprim::radix_sort_pairs(p->sort_tmp, bytes, p->keys, p->keys_out, p->iota, p->order,
                                          (size_t)count, 0, 32, p->st));
         order = p->order;
     }
@@ -415,8 +392,8 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
                                              logL, mis, p->like_ws, p->like_bytes, nullptr, nullptr, 0, gcols, gcnt, rst)))
         return rc;
     if (overlap) {
-        EP_HIP(hipEventRecord(p->join, p->side));
-        EP_HIP(hipStreamWaitEvent(p->st, p->join, 0));
+        BH_HIP(hipEventRecord(p->join, p->side));
+        BH_HIP(hipStreamWaitEvent(p->st, p->join, 0));
         *forked = false;                  // joined
     }
     if ((rc = bh::likelihood_sets_(staged ? BH_LIKE_STAGE_REST : (BH_LIKE_STAGE_GAUSS | BH_LIKE_STAGE_REST), count, T,
@@ -425,8 +402,8 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
                                    nullptr, nullptr, 0, gcols, gcnt, p->st)))
         return rc;
     // results: [count] logL then [count][T+1] misfits, contiguous on both sides
-    EP_HIP(hipMemcpyAsync(p->hres, p->dres, (size_t)count * (T + 2) * sizeof(double), hipMemcpyDeviceToHost, p->st));
-    EP_HIP(hipEventRecord(p->done, p->st));
+    BH_HIP(hipMemcpyAsync(p->hres, p->dres, (size_t)count * (T + 2) * sizeof(double), hipMemcpyDeviceToHost, p->st));
+    BH_HIP(hipEventRecord(p->done, p->st));
     return BH_OK;
 }
 
@@ -473,7 +450,7 @@ int bh_eval_set_observations(bh_eval_plan *p, int nsets, const double *yobs, con
     for (const bh_like_target &t : p->like)
         if (t.cov == BH_COV_NOCORR_SCALED && !set_scale)
             return bh::fail_arg_("bh_eval_set_observations: a BH_COV_NOCORR_SCALED target needs set_scale and set_logdet");
-    EP_HIP(hipSetDevice(p->dev));
+    BH_HIP(hipSetDevice(p->dev));
     double *dy = nullptr, *ds = nullptr, *dl = nullptr;
     int rc = upload(&dy, yobs, (size_t)nsets * p->row);
     if (!rc && set_scale) rc = upload(&ds, set_scale, (size_t)nsets * p->row);
@@ -512,7 +489,7 @@ int bh_eval_set_rf_slowness(bh_eval_plan *p, int nsets, const double *table)
                                       "] is not finite").c_str());
             byrf[(size_t)i * nsets + s] = v;
         }
-    EP_HIP(hipSetDevice(p->dev));
+    BH_HIP(hipSetDevice(p->dev));
     double *d = nullptr;
     if (int rc = upload(&d, byrf.data(), byrf.size())) {
         if (d) (void)hipFree(d);
@@ -539,7 +516,7 @@ int bh_eval_set_gaps(bh_eval_plan *p, int nsets, const unsigned char *set_presen
     if (int rc = bh::like_gaps_derive("bh_eval_set_gaps", nsets, p->row, p->T, p->like.data(), set_present, tables, &any_gap))
         return rc;
     if (any_gap) {
-        EP_HIP(hipSetDevice(p->dev));
+        BH_HIP(hipSetDevice(p->dev));
         int *d = nullptr;
         if (int rc = upload(&d, tables.data(), tables.size())) {
             if (d) (void)hipFree(d);
@@ -565,7 +542,7 @@ int bh_eval_wait(bh_eval_plan *p, int *count)
         if (count) *count = 0;
         return bh::fail_arg_(("the last bh_eval_submit of this plan failed: " + p->failure).c_str());
     }
-    if (p->last_count > 0) EP_HIP(hipEventSynchronize(p->done));
+    if (p->last_count > 0) BH_HIP(hipEventSynchronize(p->done));
     if (count) *count = p->last_count;
     return BH_OK;
 }

@@ -1,4 +1,5 @@
-// kernels.h -- kernel argument blocks and launchers shared by kernels.hip and capi.hip.
+// kernels.h -- kernel argument blocks and launchers shared by kernels.hip, like_kernel.hip and the C ABI's host files
+// (capi.hip, rf_capi.hip, like_capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rf_core.h"

@@ -11,7 +11,7 @@
 // and not MFMA-shaped ("Roofline").  HBM traffic is the algorithmic minimum: each model
 // byte is read once, each output written once; everything else lives in LDS/registers.
 #include <hip/hip_runtime.h>
-#include "../../include/bayhunter_amd.h"
+#include "host_common.h"
 #include "kernels.h"
 #include "rf_core.h"
 #include "rf_fft.h"
@@ -918,7 +918,7 @@ __global__ __launch_bounds__(SWD_T) BH_NARROW_ATTR void swd_team8_kernel(SwdArgs
 // -------------------------------------------------------------------------------------------- RF
 // (rf_block_fft, phase 4's transform of the workgroup's buffers: rf_fft.h, shared with rf_probe.hip)
 // 4 waves per SIMD (128 VGPRs, nothing spilled): alone the recursion is latency-bound at 2 and equally fast
-// at 3 or 4; at 128 VGPRs a workgroup also fits beside swd_kernel's two waves per SIMD (capi.hip: pick_rf_M).
+// at 3 or 4; at 128 VGPRs a workgroup also fits beside swd_kernel's two waves per SIMD (rf_capi.hip: pick_rf_M).
 // ZR: also keep the filtered vertical/radial spectra and return their traces (synrf_cwrap's fz, fr).
 constexpr int BH_RF_WAVES = 4;
 // ROW: the per-row form -- every model at the slowness of its own set (RfArgs::set_p, set_id) instead of the launch's.
@@ -1109,7 +1109,7 @@ hipError_t launch_swd(const SwdArgs &A, int resident_waves, hipStream_t stream)
     const size_t perbytes = (size_t)swd_pertab_doubles(maxper, group) * sizeof(double);   // the longest period table
     const size_t staged = lds + (size_t)maxper * SWD_T * sizeof(float);
     SwdArgs B = A;
-    B.stage = (maxper > 0 && 8 * (staged + perbytes) <= 160 * 1024) ? maxper : 0;   // periods staged per lane
+    B.stage = (maxper > 0 && 8 * (staged + perbytes) <= kLdsLimit) ? maxper : 0;   // periods staged per lane
     if (B.stage) lds = staged;
     lds += perbytes;
     static size_t lds_set[16] = {0};

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 #include "moho_core.h"
+#include "host_common.h"
 #include "stats_host.h"
 
 namespace {
@@ -277,14 +278,6 @@ __global__ __launch_bounds__(kThreads) void moho_sets_kernel(SetsArgs a)
     if (tid < 8) st[(tid >> 1) * kStats + 4 + (tid & 1)] = bh::post_unkey64(s_pfx[tid]);
 }
 
-bool no_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return false;
-    bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -298,7 +291,7 @@ int bh_moho_rows(const void *rows, int fp64, long long nrows, long long stride, 
     if (width < 2 || width > 2 * BH_MAX_LAYERS + 2 || stride < width) return bh::fail_arg_("bh_moho_rows: width / stride");
     if (!(zlo < zhi)) return bh::fail_arg_("bh_moho_rows: the depth window needs zlo < zhi");
     if (!(mohovs == mohovs)) return bh::fail_arg_("bh_moho_rows: mohovs is NaN");
-    if (no_device()) return BH_ERR_NO_DEVICE;
+    if (int rc = bh::require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((nrows + kThreads - 1) / kThreads));
     if (fp64)
@@ -307,7 +300,7 @@ int bh_moho_rows(const void *rows, int fp64, long long nrows, long long stride, 
     else
         hipLaunchKernelGGL(moho_rows_kernel<float>, grid, dim3(kThreads), 0, st, (const float *)rows, nrows, stride,
                            width, zlo, zhi, mohovs, out);
-    STATS_HIP(hipGetLastError());
+    BH_HIP(hipGetLastError());
     return BH_OK;
 }
 
@@ -321,28 +314,28 @@ int bh_moho_hist2d(const double *D, long long nrows, const int *weights, const d
     for (int s = 0; s < 3; s++)
         if (!bh::ascending(xedges + (size_t)s * nedges, nedges)) return bh::fail_arg_("bh_moho_hist2d: edges must be ascending");
     if (!bh::ascending(yedges, nedges)) return bh::fail_arg_("bh_moho_hist2d: edges must be ascending");
-    if (no_device()) return BH_ERR_NO_DEVICE;
+    if (int rc = bh::require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int nb = nedges - 1;
     const size_t cells = 3 * (size_t)nb * nb;
     bh::CallBufs tmp(st);
     double *ded = nullptr;
     u64 *dh = nullptr, *dneg = nullptr;
-    STATS_HIP(tmp.alloc(ded, 4 * (size_t)nedges));
-    STATS_HIP(tmp.alloc(dh, cells));
-    STATS_HIP(tmp.alloc(dneg, 1));
-    STATS_HIP(hipMemcpyAsync(ded, xedges, sizeof(double) * 3 * nedges, hipMemcpyHostToDevice, st));
-    STATS_HIP(hipMemcpyAsync(ded + 3 * (size_t)nedges, yedges, sizeof(double) * nedges, hipMemcpyHostToDevice, st));
-    STATS_HIP(hipMemsetAsync(dh, 0, sizeof(u64) * cells, st));
-    STATS_HIP(hipMemsetAsync(dneg, 0, sizeof(u64), st));
+    BH_HIP(tmp.alloc(ded, 4 * (size_t)nedges));
+    BH_HIP(tmp.alloc(dh, cells));
+    BH_HIP(tmp.alloc(dneg, 1));
+    BH_HIP(hipMemcpyAsync(ded, xedges, sizeof(double) * 3 * nedges, hipMemcpyHostToDevice, st));
+    BH_HIP(hipMemcpyAsync(ded + 3 * (size_t)nedges, yedges, sizeof(double) * nedges, hipMemcpyHostToDevice, st));
+    BH_HIP(hipMemsetAsync(dh, 0, sizeof(u64) * cells, st));
+    BH_HIP(hipMemsetAsync(dneg, 0, sizeof(u64), st));
     const int use_lds = cells * sizeof(u64) <= (size_t)kHist2dLdsBytes;
     const long long blocks = (nrows + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(moho_hist2d_kernel, dim3((unsigned)(blocks < kHist2dBlocks ? blocks : kHist2dBlocks)),
                        dim3(kThreads), use_lds ? cells * sizeof(u64) : 0, st, D, nrows, weights, (const double *)ded,
                        (const double *)(ded + 3 * (size_t)nedges), nedges, dh, use_lds, dneg);
-    STATS_HIP(hipGetLastError());
+    BH_HIP(hipGetLastError());
     u64 neg = 0;
-    STATS_HIP(hipMemcpyAsync(&neg, dneg, sizeof(u64), hipMemcpyDeviceToHost, st));
+    BH_HIP(hipMemcpyAsync(&neg, dneg, sizeof(u64), hipMemcpyDeviceToHost, st));
     int rc = bh::read_hist(dh, cells, hist, st);           // synchronises
     if (rc) return rc;
     if (neg) return bh::fail_arg_("bh_moho_hist2d: negative weight");
@@ -364,7 +357,7 @@ int bh_moho_sets(const double *D, long long nrows, const int *weights, const lon
     const bool want_hist = edges != nullptr;
     if (want_hist && (nedges < 2 || !hist || !bh::ascending(edges, nedges)))
         return bh::fail_arg_("bh_moho_sets: edges must be ascending, two at least, with hist");
-    if (no_device()) return BH_ERR_NO_DEVICE;
+    if (int rc = bh::require_device()) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int nb = want_hist ? nedges - 1 : 0;
     const size_t S = (size_t)nsets;
@@ -373,16 +366,16 @@ int bh_moho_sets(const double *D, long long nrows, const int *weights, const lon
     std::memset(&a, 0, sizeof(a));
     long long *dstart = nullptr;
     double *ded = nullptr;
-    STATS_HIP(tmp.alloc(dstart, S + 1));
-    STATS_HIP(tmp.alloc(a.cnt, 2 * S));
-    STATS_HIP(tmp.alloc(a.stats, S * 4 * kStats));
-    STATS_HIP(tmp.alloc(a.flags, 2));
-    STATS_HIP(hipMemcpyAsync(dstart, set_start, sizeof(long long) * (S + 1), hipMemcpyHostToDevice, st));
-    STATS_HIP(hipMemsetAsync(a.flags, 0, sizeof(u64) * 2, st));
+    BH_HIP(tmp.alloc(dstart, S + 1));
+    BH_HIP(tmp.alloc(a.cnt, 2 * S));
+    BH_HIP(tmp.alloc(a.stats, S * 4 * kStats));
+    BH_HIP(tmp.alloc(a.flags, 2));
+    BH_HIP(hipMemcpyAsync(dstart, set_start, sizeof(long long) * (S + 1), hipMemcpyHostToDevice, st));
+    BH_HIP(hipMemsetAsync(a.flags, 0, sizeof(u64) * 2, st));
     if (want_hist) {
-        STATS_HIP(tmp.alloc(ded, nedges));
-        STATS_HIP(tmp.alloc(a.hist, S * nb));
-        STATS_HIP(hipMemcpyAsync(ded, edges, sizeof(double) * nedges, hipMemcpyHostToDevice, st));
+        BH_HIP(tmp.alloc(ded, nedges));
+        BH_HIP(tmp.alloc(a.hist, S * nb));
+        BH_HIP(hipMemcpyAsync(ded, edges, sizeof(double) * nedges, hipMemcpyHostToDevice, st));
     }
     a.D = D;
     a.w = weights;
@@ -391,18 +384,18 @@ int bh_moho_sets(const double *D, long long nrows, const int *weights, const lon
     a.ne = want_hist ? nedges : 0;
     a.hist_lds = nb <= kSetHistLdsBins;
     hipLaunchKernelGGL(moho_sets_kernel, dim3((unsigned)nsets), dim3(kThreads), a.hist_lds ? sizeof(u64) * nb : 0, st, a);
-    STATS_HIP(hipGetLastError());
+    BH_HIP(hipGetLastError());
     std::vector<u64> cnt(2 * S);
     std::vector<double> stt(S * 4 * kStats);
     u64 flags[2] = {0, 0};
-    STATS_HIP(hipMemcpyAsync(cnt.data(), a.cnt, sizeof(u64) * 2 * S, hipMemcpyDeviceToHost, st));
-    STATS_HIP(hipMemcpyAsync(stt.data(), a.stats, sizeof(double) * S * 4 * kStats, hipMemcpyDeviceToHost, st));
-    STATS_HIP(hipMemcpyAsync(flags, a.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
+    BH_HIP(hipMemcpyAsync(cnt.data(), a.cnt, sizeof(u64) * 2 * S, hipMemcpyDeviceToHost, st));
+    BH_HIP(hipMemcpyAsync(stt.data(), a.stats, sizeof(double) * S * 4 * kStats, hipMemcpyDeviceToHost, st));
+    BH_HIP(hipMemcpyAsync(flags, a.flags, sizeof(flags), hipMemcpyDeviceToHost, st));
     if (want_hist) {
         int rc = bh::read_hist(a.hist, S * nb, hist, st);   // synchronises
         if (rc) return rc;
     } else {
-        STATS_HIP(hipStreamSynchronize(st));
+        BH_HIP(hipStreamSynchronize(st));
     }
     if (flags[0]) return bh::fail_arg_("bh_moho_sets: negative weight");
     if (flags[1]) return bh::fail_arg_("bh_moho_sets: weight total above 2^53");

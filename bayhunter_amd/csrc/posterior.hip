@@ -18,6 +18,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include "host_common.h"
 #include "posterior_kernel.h"
 
 namespace {
@@ -53,7 +54,7 @@ int launch(bh_posterior *p, PostArgs &a, size_t lds_bytes)
 {
     dim3 grid((unsigned)p->G, (unsigned)((p->n + kTile - 1) / kTile));
     hipLaunchKernelGGL((post_kernel<T, MODE>), grid, dim3(kThreads), lds_bytes, p->st, a);
-    STATS_HIP(hipGetLastError());
+    BH_HIP(hipGetLastError());
     return BH_OK;
 }
 
@@ -96,11 +97,7 @@ int bh_posterior_create(const void *rows, int fp64, long long nrows, long long s
     if (!dep || ndep < 1 || !bh::ascending(dep, ndep)) return bh::fail_arg_("bh_posterior_create: the depth grid must be ascending");
     if (nifedges && (nifedges < 2 || !ifedges || !bh::ascending(ifedges, nifedges)))
         return bh::fail_arg_("bh_posterior_create: interface edges must be ascending");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
-        return BH_ERR_NO_DEVICE;
-    }
+    if (int rc = bh::require_device()) return rc;
     std::unique_ptr<bh_posterior> p(new (std::nothrow) bh_posterior);
     if (!p) return bh::fail_arg_("out of memory");
     p->fp64 = fp64 ? 1 : 0;
@@ -117,18 +114,18 @@ int bh_posterior_create(const void *rows, int fp64, long long nrows, long long s
     p->G = blocks_of(nrows);
     int rc = p->alloc_columns();
     if (rc) return rc;
-    STATS_HIP(p->bufs.alloc(p->dep, ndep));
-    STATS_HIP(p->bufs.alloc(p->cnt, 2));
-    STATS_HIP(p->bufs.alloc(p->nlay, p->maxn + 1));
-    STATS_HIP(p->bufs.alloc(p->mfkey, p->G));
-    STATS_HIP(p->bufs.alloc(p->mfrow, p->G));
-    STATS_HIP(hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st));
+    BH_HIP(p->bufs.alloc(p->dep, ndep));
+    BH_HIP(p->bufs.alloc(p->cnt, 2));
+    BH_HIP(p->bufs.alloc(p->nlay, p->maxn + 1));
+    BH_HIP(p->bufs.alloc(p->mfkey, p->G));
+    BH_HIP(p->bufs.alloc(p->mfrow, p->G));
+    BH_HIP(hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st));
     if (nifedges) {
-        STATS_HIP(p->bufs.alloc(p->ifedges, nifedges));
-        STATS_HIP(p->bufs.alloc(p->ifhist, nifedges - 1));
-        STATS_HIP(hipMemcpyAsync(p->ifedges, ifedges, sizeof(double) * nifedges, hipMemcpyHostToDevice, p->st));
+        BH_HIP(p->bufs.alloc(p->ifedges, nifedges));
+        BH_HIP(p->bufs.alloc(p->ifhist, nifedges - 1));
+        BH_HIP(hipMemcpyAsync(p->ifedges, ifedges, sizeof(double) * nifedges, hipMemcpyHostToDevice, p->st));
     }
-    STATS_HIP(hipStreamSynchronize(p->st));
+    BH_HIP(hipStreamSynchronize(p->st));
     *post = p.release();
     return BH_OK;
 }
@@ -147,9 +144,9 @@ int bh_posterior_scan(bh_posterior *p, long long *total, double *vmin, double *v
     if (!p) return bh::fail_arg_("post is NULL");
     int rc = p->begin_scan();
     if (rc) return rc;
-    STATS_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2, p->st));
-    STATS_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (p->maxn + 1), p->st));
-    if (p->nif) STATS_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (p->nif - 1), p->st));
+    BH_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2, p->st));
+    BH_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (p->maxn + 1), p->st));
+    if (p->nif) BH_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (p->nif - 1), p->st));
     PostArgs a = base_args(p);
     a.flags = F_ROWS;
     a.kmin = p->kmin;
@@ -169,12 +166,12 @@ int bh_posterior_scan(bh_posterior *p, long long *total, double *vmin, double *v
     u64 cnt[2];                                    // weight total, rows with a negative weight
     std::vector<u64> nl(p->maxn + 1), ih(p->nif > 1 ? p->nif - 1 : 0), mk(p->G);
     std::vector<long long> mr(p->G);
-    STATS_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
-    STATS_HIP(hipMemcpyAsync(nl.data(), p->nlay, sizeof(u64) * nl.size(), hipMemcpyDeviceToHost, p->st));
-    if (!ih.empty()) STATS_HIP(hipMemcpyAsync(ih.data(), p->ifhist, sizeof(u64) * ih.size(), hipMemcpyDeviceToHost, p->st));
+    BH_HIP(hipMemcpyAsync(cnt, p->cnt, sizeof(cnt), hipMemcpyDeviceToHost, p->st));
+    BH_HIP(hipMemcpyAsync(nl.data(), p->nlay, sizeof(u64) * nl.size(), hipMemcpyDeviceToHost, p->st));
+    if (!ih.empty()) BH_HIP(hipMemcpyAsync(ih.data(), p->ifhist, sizeof(u64) * ih.size(), hipMemcpyDeviceToHost, p->st));
     if (p->misfit) {
-        STATS_HIP(hipMemcpyAsync(mk.data(), p->mfkey, sizeof(u64) * p->G, hipMemcpyDeviceToHost, p->st));
-        STATS_HIP(hipMemcpyAsync(mr.data(), p->mfrow, sizeof(long long) * p->G, hipMemcpyDeviceToHost, p->st));
+        BH_HIP(hipMemcpyAsync(mk.data(), p->mfkey, sizeof(u64) * p->G, hipMemcpyDeviceToHost, p->st));
+        BH_HIP(hipMemcpyAsync(mr.data(), p->mfrow, sizeof(long long) * p->G, hipMemcpyDeviceToHost, p->st));
     }
     std::vector<double> sum;
     rc = p->reduce_slab(sum);                      // synchronises the stream
@@ -213,12 +210,12 @@ int bh_posterior_finish(bh_posterior *p, const double *vedges, int nvedges, cons
     if (want_hist) {
         double *dve = nullptr;
         int *ddb = nullptr;
-        STATS_HIP(tmp.alloc(dve, nvedges));
-        STATS_HIP(tmp.alloc(ddb, D));
-        STATS_HIP(tmp.alloc(a.hist, (size_t)ndbins * nvb));
-        STATS_HIP(hipMemcpyAsync(dve, vedges, sizeof(double) * nvedges, hipMemcpyHostToDevice, p->st));
-        STATS_HIP(hipMemcpyAsync(ddb, dbin, sizeof(int) * D, hipMemcpyHostToDevice, p->st));
-        STATS_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * (size_t)ndbins * nvb, p->st));
+        BH_HIP(tmp.alloc(dve, nvedges));
+        BH_HIP(tmp.alloc(ddb, D));
+        BH_HIP(tmp.alloc(a.hist, (size_t)ndbins * nvb));
+        BH_HIP(hipMemcpyAsync(dve, vedges, sizeof(double) * nvedges, hipMemcpyHostToDevice, p->st));
+        BH_HIP(hipMemcpyAsync(ddb, dbin, sizeof(int) * D, hipMemcpyHostToDevice, p->st));
+        BH_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * (size_t)ndbins * nvb, p->st));
         a.flags |= F_HIST;
         a.vedges = dve;
         a.nve = nvedges;

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <memory>
 #include <new>
+#include "host_common.h"
 #include "posterior_kernel.h"
 
 namespace {
@@ -122,7 +123,7 @@ int launch(bh_posterior_sets *p, PostArgs &a, SetArgs &s, int nc, size_t lds_byt
 {
     dim3 grid((unsigned)p->chunk_blocks(s.first, nc), (unsigned)((p->D + kTile - 1) / kTile), (unsigned)nc);
     hipLaunchKernelGGL((post_sets_kernel<T, MODE>), grid, dim3(kThreads), lds_bytes, p->st, a, s);
-    STATS_HIP(hipGetLastError());
+    BH_HIP(hipGetLastError());
     return BH_OK;
 }
 
@@ -137,7 +138,7 @@ int reduce_chunk(bh_posterior_sets *p, int first, int nc)
 {
     hipLaunchKernelGGL(sets_reduce_kernel, dim3((unsigned)((nc * p->D + 255) / 256)), dim3(256), 0, p->st,
                        (const double *)p->slab, (const long long *)p->dstart, first, nc, p->Gmax, p->D, p->red);
-    STATS_HIP(hipGetLastError());
+    BH_HIP(hipGetLastError());
     return BH_OK;
 }
 
@@ -162,7 +163,7 @@ template <typename T>
 int fetch(std::vector<T> &host, const T *dev, size_t count, hipStream_t st)
 {
     host.resize(count);
-    if (count) STATS_HIP(hipMemcpyAsync(host.data(), dev, sizeof(T) * count, hipMemcpyDeviceToHost, st));
+    if (count) BH_HIP(hipMemcpyAsync(host.data(), dev, sizeof(T) * count, hipMemcpyDeviceToHost, st));
     return BH_OK;
 }
 
@@ -204,11 +205,7 @@ int bh_posterior_sets_create(const void *rows, int fp64, long long nrows, long l
     if ((long long)nsets * ndep > 0x3fffffff) return bh::fail_arg_("bh_posterior_sets_create: more than 2^30 (set, depth) columns");
     if (nifedges && (nifedges < 2 || !ifedges || !bh::ascending(ifedges, nifedges)))
         return bh::fail_arg_("bh_posterior_sets_create: interface edges must be ascending");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        bh::fail_arg_("no usable HIP device (libbayhunter_amd has no CPU fallback)");
-        return BH_ERR_NO_DEVICE;
-    }
+    if (int rc = bh::require_device()) return rc;
     std::unique_ptr<bh_posterior_sets> p(new (std::nothrow) bh_posterior_sets);
     if (!p) return bh::fail_arg_("out of memory");
     p->fp64 = fp64 ? 1 : 0;
@@ -229,25 +226,25 @@ int bh_posterior_sets_create(const void *rows, int fp64, long long nrows, long l
     p->Gmax = p->chunk_blocks(0, nsets);
     (void)bh_posterior_sets_set_chunk_bytes(p.get(), 0);
     const size_t cols = (size_t)nsets * ndep;
-    STATS_HIP(p->bufs.alloc(p->dstart, (size_t)nsets + 1));
-    STATS_HIP(p->bufs.alloc(p->red, cols));
-    STATS_HIP(p->bufs.alloc(p->dmean, cols));
-    STATS_HIP(p->bufs.alloc(p->kmin, cols));
-    STATS_HIP(p->bufs.alloc(p->kmax, cols));
-    STATS_HIP(p->bufs.alloc(p->dep, ndep));
-    STATS_HIP(p->bufs.alloc(p->cnt, 2 * (size_t)nsets));
-    STATS_HIP(p->bufs.alloc(p->nlay, (size_t)nsets * (p->maxn + 1)));
-    STATS_HIP(p->bufs.alloc(p->mfkey, (size_t)nsets * p->Gmax));
-    STATS_HIP(p->bufs.alloc(p->mfrow, (size_t)nsets * p->Gmax));
-    STATS_HIP(p->bufs.alloc(p->sflags, nsets));
-    STATS_HIP(hipMemcpyAsync(p->dstart, p->start.data(), sizeof(long long) * (nsets + 1), hipMemcpyHostToDevice, p->st));
-    STATS_HIP(hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st));
+    BH_HIP(p->bufs.alloc(p->dstart, (size_t)nsets + 1));
+    BH_HIP(p->bufs.alloc(p->red, cols));
+    BH_HIP(p->bufs.alloc(p->dmean, cols));
+    BH_HIP(p->bufs.alloc(p->kmin, cols));
+    BH_HIP(p->bufs.alloc(p->kmax, cols));
+    BH_HIP(p->bufs.alloc(p->dep, ndep));
+    BH_HIP(p->bufs.alloc(p->cnt, 2 * (size_t)nsets));
+    BH_HIP(p->bufs.alloc(p->nlay, (size_t)nsets * (p->maxn + 1)));
+    BH_HIP(p->bufs.alloc(p->mfkey, (size_t)nsets * p->Gmax));
+    BH_HIP(p->bufs.alloc(p->mfrow, (size_t)nsets * p->Gmax));
+    BH_HIP(p->bufs.alloc(p->sflags, nsets));
+    BH_HIP(hipMemcpyAsync(p->dstart, p->start.data(), sizeof(long long) * (nsets + 1), hipMemcpyHostToDevice, p->st));
+    BH_HIP(hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st));
     if (nifedges) {
-        STATS_HIP(p->bufs.alloc(p->ifedges, nifedges));
-        STATS_HIP(p->bufs.alloc(p->ifhist, (size_t)nsets * (nifedges - 1)));
-        STATS_HIP(hipMemcpyAsync(p->ifedges, ifedges, sizeof(double) * nifedges, hipMemcpyHostToDevice, p->st));
+        BH_HIP(p->bufs.alloc(p->ifedges, nifedges));
+        BH_HIP(p->bufs.alloc(p->ifhist, (size_t)nsets * (nifedges - 1)));
+        BH_HIP(hipMemcpyAsync(p->ifedges, ifedges, sizeof(double) * nifedges, hipMemcpyHostToDevice, p->st));
     }
-    STATS_HIP(hipStreamSynchronize(p->st));
+    BH_HIP(hipStreamSynchronize(p->st));
     *post = p.release();
     return BH_OK;
 }
@@ -266,15 +263,15 @@ int bh_posterior_sets_scan(bh_posterior_sets *p, long long *total, double *vmin,
     if (!p) return bh::fail_arg_("post is NULL");
     if (!status) return bh::fail_arg_("bh_posterior_sets_scan: status is NULL");
     p->scanned = 0;
-    if (!p->slab) STATS_HIP(p->bufs.alloc(p->slab, (size_t)p->chunk * p->Gmax * p->D));   // the chunk is settled now
+    if (!p->slab) BH_HIP(p->bufs.alloc(p->slab, (size_t)p->chunk * p->Gmax * p->D));   // the chunk is settled now
     const int D = p->D, S = p->nsets, nl1 = p->maxn + 1, nih = p->nif > 1 ? p->nif - 1 : 0;
     const int cols = S * D;
     hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmin, cols, ~0ull);
     hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmax, cols, 0ull);
-    STATS_HIP(hipGetLastError());
-    STATS_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2 * S, p->st));
-    STATS_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (size_t)S * nl1, p->st));
-    if (nih) STATS_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (size_t)S * nih, p->st));
+    BH_HIP(hipGetLastError());
+    BH_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2 * S, p->st));
+    BH_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (size_t)S * nl1, p->st));
+    if (nih) BH_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (size_t)S * nih, p->st));
     PostArgs a = base_args(p);
     a.flags = F_ROWS;
     a.kmin = p->kmin;
@@ -312,7 +309,7 @@ int bh_posterior_sets_scan(bh_posterior_sets *p, long long *total, double *vmin,
     if (!rc) rc = fetch(kmn, p->kmin, (size_t)cols, p->st);
     if (!rc) rc = fetch(kmx, p->kmax, (size_t)cols, p->st);
     if (rc) return rc;
-    STATS_HIP(hipStreamSynchronize(p->st));
+    BH_HIP(hipStreamSynchronize(p->st));
     for (int z = 0; z < S; z++)
         if (cnt[2 * z + 1])
             return bh::fail_arg_((std::string("bh_posterior_sets_scan: ") + bh::scan_fault(cnt[2 * z], cnt[2 * z + 1])).c_str());
@@ -349,8 +346,8 @@ int bh_posterior_sets_scan(bh_posterior_sets *p, long long *total, double *vmin,
             argmin[z] = best;
         }
     }
-    STATS_HIP(hipMemcpyAsync(p->dmean, mu.data(), sizeof(double) * cols, hipMemcpyHostToDevice, p->st));
-    STATS_HIP(hipStreamSynchronize(p->st));
+    BH_HIP(hipMemcpyAsync(p->dmean, mu.data(), sizeof(double) * cols, hipMemcpyHostToDevice, p->st));
+    BH_HIP(hipStreamSynchronize(p->st));
     p->scanned = 1;
     return BH_OK;
 }
@@ -390,22 +387,22 @@ int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const i
     s.start = p->dstart;
     s.Gmax = p->Gmax;
     s.sflags = p->sflags;
-    STATS_HIP(hipMemcpyAsync(p->sflags, sflags.data(), sizeof(int) * S, hipMemcpyHostToDevice, p->st));
+    BH_HIP(hipMemcpyAsync(p->sflags, sflags.data(), sizeof(int) * S, hipMemcpyHostToDevice, p->st));
     if (want_hist) {
         double *dve = nullptr;
         int *ddb = nullptr, *dvo = nullptr;
         u64 *dho = nullptr;
         const size_t nve_all = (size_t)vedge_off[S], nhist = (size_t)hoff[S];
-        STATS_HIP(tmp.alloc(dve, nve_all ? nve_all : 1));
-        STATS_HIP(tmp.alloc(ddb, D));
-        STATS_HIP(tmp.alloc(dvo, (size_t)S + 1));
-        STATS_HIP(tmp.alloc(dho, (size_t)S + 1));
-        STATS_HIP(tmp.alloc(a.hist, nhist ? nhist : 1));
-        if (nve_all) STATS_HIP(hipMemcpyAsync(dve, vedges, sizeof(double) * nve_all, hipMemcpyHostToDevice, p->st));
-        STATS_HIP(hipMemcpyAsync(ddb, dbin, sizeof(int) * D, hipMemcpyHostToDevice, p->st));
-        STATS_HIP(hipMemcpyAsync(dvo, vedge_off, sizeof(int) * ((size_t)S + 1), hipMemcpyHostToDevice, p->st));
-        STATS_HIP(hipMemcpyAsync(dho, hoff.data(), sizeof(u64) * ((size_t)S + 1), hipMemcpyHostToDevice, p->st));
-        if (nhist) STATS_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * nhist, p->st));
+        BH_HIP(tmp.alloc(dve, nve_all ? nve_all : 1));
+        BH_HIP(tmp.alloc(ddb, D));
+        BH_HIP(tmp.alloc(dvo, (size_t)S + 1));
+        BH_HIP(tmp.alloc(dho, (size_t)S + 1));
+        BH_HIP(tmp.alloc(a.hist, nhist ? nhist : 1));
+        if (nve_all) BH_HIP(hipMemcpyAsync(dve, vedges, sizeof(double) * nve_all, hipMemcpyHostToDevice, p->st));
+        BH_HIP(hipMemcpyAsync(ddb, dbin, sizeof(int) * D, hipMemcpyHostToDevice, p->st));
+        BH_HIP(hipMemcpyAsync(dvo, vedge_off, sizeof(int) * ((size_t)S + 1), hipMemcpyHostToDevice, p->st));
+        BH_HIP(hipMemcpyAsync(dho, hoff.data(), sizeof(u64) * ((size_t)S + 1), hipMemcpyHostToDevice, p->st));
+        if (nhist) BH_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * nhist, p->st));
         a.flags |= F_HIST;
         a.vedges = dve;
         a.dbin = ddb;
@@ -475,7 +472,7 @@ int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const i
         std::vector<double> sq;
         int rc = fetch(sq, p->red, (size_t)S * D, p->st);
         if (rc) return rc;
-        STATS_HIP(hipStreamSynchronize(p->st));
+        BH_HIP(hipStreamSynchronize(p->st));
         for (int z = 0; z < S; z++)
             for (int c = 0; c < D; c++) {
                 const size_t i = (size_t)z * D + c;

@@ -2,7 +2,7 @@
 //
 // A translation unit of its own, so that no other kernel's registers or listing depend on it.  The workgroup is
 // rf_kernel's: RF_T threads, M buffers in LDS at the pitch rf_layout(Lmax, nsamp).per_model (+ the 4 nfreq doubles of
-// the trace form's two spectra behind each block when paired), the twiddle table of get_twiddles (capi.hip), and from
+// the trace form's two spectra behind each block when paired), the twiddle table of get_twiddles (rf_capi.hip), and from
 // "P4" on the statements of rf_kernel with the same functions: rf_xst, rf_fft_hermitian, rf_block_fft (rf_fft.h),
 // rf_fft_pair_entry.
 #include <hip/hip_runtime.h>

@@ -4,23 +4,15 @@
 // scan pass and a finish pass: min / max over order-preserving keys, Σ through a per-block slab that one thread
 // per column adds in block order, histograms over host-made edges, order statistics by radix select
 // (stats_core.h).  Only the way a block reads a value differs, and that stays in the two files; what surrounds
-// it is here: the error macro, the owner of device buffers, the fill and slab kernels, the select's device
-// side, and the part of a handle that carries a scan over to its finish.
+// it is here: the owner of device buffers, the fill and slab kernels, the select's device side, and the part of
+// a handle that carries a scan over to its finish.  (Errors and the device check: host_common.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <string>
 #include <vector>
-#include "../../include/bayhunter_amd.h"
+#include "host_common.h"
 #include "stats_core.h"
-
-namespace bh { int fail_arg_(const char *what); int fail_hip_(int e, const char *what); }
-
-#define STATS_HIP(call)                                                      \
-    do {                                                                     \
-        hipError_t e_ = (call);                                              \
-        if (e_ != hipSuccess) return bh::fail_hip_((int)e_, #call);          \
-    } while (0)
 
 namespace bh {
 
@@ -78,8 +70,8 @@ inline bool ascending(const double *v, int n)
 inline int read_hist(const u64 *dhist, size_t count, long long *hist, hipStream_t st)
 {
     std::vector<u64> h(count);
-    STATS_HIP(hipMemcpyAsync(h.data(), dhist, sizeof(u64) * count, hipMemcpyDeviceToHost, st));
-    STATS_HIP(hipStreamSynchronize(st));
+    BH_HIP(hipMemcpyAsync(h.data(), dhist, sizeof(u64) * count, hipMemcpyDeviceToHost, st));
+    BH_HIP(hipStreamSynchronize(st));
     for (size_t i = 0; i < count; i++) hist[i] = (long long)h[i];
     return BH_OK;
 }
@@ -94,26 +86,26 @@ struct DeviceSelect : RadixSelect {
 
     int alloc(DevBufs &bufs)
     {
-        STATS_HIP(bufs.alloc(dgbase, ncols));
-        STATS_HIP(bufs.alloc(dngroups, ncols));
-        STATS_HIP(bufs.alloc(dgpfx, pfx.size()));
-        STATS_HIP(bufs.alloc(ddigits, 256 * pfx.size()));
+        BH_HIP(bufs.alloc(dgbase, ncols));
+        BH_HIP(bufs.alloc(dngroups, ncols));
+        BH_HIP(bufs.alloc(dgpfx, pfx.size()));
+        BH_HIP(bufs.alloc(ddigits, 256 * pfx.size()));
         return BH_OK;
     }
     int begin_pass(hipStream_t st)
     {
         plan();
-        STATS_HIP(hipMemcpyAsync(dgbase, gbase.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
-        STATS_HIP(hipMemcpyAsync(dngroups, ngroups.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
-        STATS_HIP(hipMemcpyAsync(dgpfx, gpfx.data(), sizeof(u64) * slots, hipMemcpyHostToDevice, st));
-        STATS_HIP(hipMemsetAsync(ddigits, 0, sizeof(u64) * 256 * (size_t)slots, st));
+        BH_HIP(hipMemcpyAsync(dgbase, gbase.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
+        BH_HIP(hipMemcpyAsync(dngroups, ngroups.data(), sizeof(int) * ncols, hipMemcpyHostToDevice, st));
+        BH_HIP(hipMemcpyAsync(dgpfx, gpfx.data(), sizeof(u64) * slots, hipMemcpyHostToDevice, st));
+        BH_HIP(hipMemsetAsync(ddigits, 0, sizeof(u64) * 256 * (size_t)slots, st));
         return BH_OK;
     }
     int end_pass(hipStream_t st)             // synchronises
     {
         dig.resize((size_t)slots * 256);
-        STATS_HIP(hipMemcpyAsync(dig.data(), ddigits, sizeof(u64) * dig.size(), hipMemcpyDeviceToHost, st));
-        STATS_HIP(hipStreamSynchronize(st));
+        BH_HIP(hipMemcpyAsync(dig.data(), ddigits, sizeof(u64) * dig.size(), hipMemcpyDeviceToHost, st));
+        BH_HIP(hipStreamSynchronize(st));
         advance(dig.data());
         return BH_OK;
     }
@@ -140,11 +132,11 @@ struct ColumnStats {
 
     int alloc_columns()
     {
-        STATS_HIP(bufs.alloc(slab, (size_t)G * n));
-        STATS_HIP(bufs.alloc(red, n));
-        STATS_HIP(bufs.alloc(dmean, n));
-        STATS_HIP(bufs.alloc(kmin, n));
-        STATS_HIP(bufs.alloc(kmax, n));
+        BH_HIP(bufs.alloc(slab, (size_t)G * n));
+        BH_HIP(bufs.alloc(red, n));
+        BH_HIP(bufs.alloc(dmean, n));
+        BH_HIP(bufs.alloc(kmin, n));
+        BH_HIP(bufs.alloc(kmax, n));
         return BH_OK;
     }
     // a scan starts: whatever an earlier one left is void until this one has succeeded
@@ -153,7 +145,7 @@ struct ColumnStats {
         scanned = 0;
         hipLaunchKernelGGL(stats_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kmin, n, ~0ull);
         hipLaunchKernelGGL(stats_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kmax, n, 0ull);
-        STATS_HIP(hipGetLastError());
+        BH_HIP(hipGetLastError());
         return BH_OK;
     }
     // the slab of the pass just launched, added up: synchronises
@@ -161,10 +153,10 @@ struct ColumnStats {
     {
         hipLaunchKernelGGL(stats_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                            (const double *)slab, G, n, red);
-        STATS_HIP(hipGetLastError());
+        BH_HIP(hipGetLastError());
         out.assign(n, 0.0);
-        STATS_HIP(hipMemcpyAsync(out.data(), red, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-        STATS_HIP(hipStreamSynchronize(st));
+        BH_HIP(hipMemcpyAsync(out.data(), red, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+        BH_HIP(hipStreamSynchronize(st));
         return BH_OK;
     }
     // a scan ends, with its counts and reduce_slab's Σ w·v on the host: the total or an error (`who` names the
@@ -178,10 +170,10 @@ struct ColumnStats {
         std::vector<double> mu(n);
         std::vector<u64> kmn(n), kmx(n);
         for (int c = 0; c < n; c++) mu[c] = sum[c] / (double)included;
-        STATS_HIP(hipMemcpyAsync(dmean, mu.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
-        STATS_HIP(hipMemcpyAsync(kmn.data(), kmin, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
-        STATS_HIP(hipMemcpyAsync(kmx.data(), kmax, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
-        STATS_HIP(hipStreamSynchronize(st));
+        BH_HIP(hipMemcpyAsync(dmean, mu.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+        BH_HIP(hipMemcpyAsync(kmn.data(), kmin, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
+        BH_HIP(hipMemcpyAsync(kmx.data(), kmax, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
+        BH_HIP(hipStreamSynchronize(st));
         scanned = 1;
         for (int c = 0; c < n; c++) {
             if (vmin) vmin[c] = bh::post_unkey64(kmn[c]);

@@ -53,7 +53,7 @@ U = 2.0 ** -53
 LENGTHS = [8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096]
 MU_BOUND = 10.3          # twiddle error in units of u (the derivation above)
 DIRECT_MAX = 512         # the direct O(n^2) sum up to here
-LDS_LIMIT = 160 * 1024   # what the library's own launches allow a workgroup (capi.hip)
+LDS_LIMIT = 160 * 1024   # what the library's own launches allow a workgroup (host_common.h: kLdsLimit)
 _SIM = {}
 
 
@@ -120,7 +120,7 @@ def as_doubles(x):
 
 # ---- the two builds -----------------------------------------------------------------------------------------------------
 def library_table(n):
-    """The twiddle table as the library's own host code builds it (bh_rf_twiddles: what get_twiddles uploads), [2n].  The
+    """The twiddle table as the library's own host code builds it (bh_rf_twiddles: what get_twiddles of rf_capi.hip uploads), [2n].  The
     twin takes this table: rf_fill_twiddles compiled by g++ into the twin differs from the library's build of it in the
     last bit of one entry (n = 4096: the sine of pi 1955 / 2048) -- glibc's values both, through different calls."""
     if ('T', n) not in _SIM:

@@ -243,6 +243,23 @@ def test_form_plans_are_the_recorded_ones():
             assert got[section][key] == want[section][key], (section, key)
 
 
+def test_internal_prototypes_live_in_host_common_only():
+    """What one translation unit of the library defines and another calls is declared once, in csrc/host_common.h: a
+    prototype (return type, name, parameters, ';' and no body) of the shared internals occurs in no other file, and the
+    error macros and the device check that the header replaced are gone."""
+    csrc = os.path.join(ROOT, 'bayhunter_amd', 'csrc')
+    srcs = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.h', '.hip', '.cpp'))}
+    assert 'host_common.h' in srcs and len(srcs) > 25
+    for name in ('fail_arg_', 'fail_hip_', 'check_rf_params', 'like_gaps_derive', 'likelihood_sets_'):
+        proto = re.compile(r'\b(?:int|void|bool|auto)\s+(?:bh\s*::\s*)?%s\s*\([^;{}]*\)\s*;' % name)
+        where = [f for f, src in srcs.items() if proto.search(src)]
+        assert where == ['host_common.h'], (name, where)
+        assert len(proto.findall(srcs['host_common.h'])) == 1, name
+    for f, src in srcs.items():
+        for gone in ('EP_HIP', 'STATS_HIP', 'ensure_device'):
+            assert gone not in src, (gone, f)
+
+
 def test_no_switches_beyond_the_kept_ones():
     """The library's sources switch on these names and no others: every identifier of an #if / #ifdef / #ifndef / #elif
     line and every getenv name under bayhunter_amd/csrc (names the compiler predefines aside).  A measured-and-dropped
