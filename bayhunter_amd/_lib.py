@@ -12,9 +12,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "rf_capi.hip", "like_capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
-           "posterior_sets.hip", "datafits.hip", "moho.hip", "math_probe.hip", "rf_probe.hip"]
+           "posterior_sets.hip", "datafits.hip", "datafits_sets.hip", "moho.hip", "math_probe.hip", "rf_probe.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
-           "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "stats_core.h",
+           "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
            "stats_host.h", "moho_core.h", "math_probe.h", "rf_fft.h", "host_common.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
@@ -178,6 +178,9 @@ _SIGS = {
     "bh_forward_batch": (C.c_int, [C.c_int] * 3 + [_vp] * 5 + [C.c_int, C.POINTER(SwdTarget), _vp, C.c_int,
                                    C.POINTER(EvalInterp), C.c_int, C.POINTER(RfParams), _vp, C.c_double, C.c_int, _vp,
                                    C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "bh_forward_batch_sets": (C.c_int, [C.c_int] * 3 + [_vp] * 5 + [C.c_int, C.POINTER(SwdTarget), _vp, C.c_int,
+                                        C.POINTER(EvalInterp), C.c_int, C.POINTER(RfParams), _vp, C.c_double, C.c_int,
+                                        _vp, C.c_int, _vp, _vp, C.c_size_t, _vp, _vp, C.c_int, _vp, _vp]),
     "bh_swd_hint": (C.c_int, [C.c_double, C.c_int]),
     "bh_version": (C.c_char_p, []),
     "bh_last_error": (C.c_char_p, []),
@@ -250,6 +253,13 @@ _SIGS = {
     "bh_datafits_scan": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _vp, _vp, _vp]),
     "bh_datafits_finish": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "bh_datafits_destroy": (None, [_vp]),
+    "bh_datafits_sets_create": (C.c_int, [_vp, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp,
+                                          C.POINTER(_vp)]),
+    "bh_datafits_sets_scan": (C.c_int, [_vp] * 7),
+    "bh_datafits_sets_finish": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "bh_datafits_sets_destroy": (None, [_vp]),
+    "bh_datafits_sets_status_text": (C.c_char_p, [C.c_int]),
+    "bh_datafits_sets_set_chunk_bytes": (C.c_int, [_vp, C.c_longlong]),
     "bh_moho_rows": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_double, C.c_double, C.c_double,
                                _vp, _vp]),
     "bh_moho_hist2d": (C.c_int, [_vp, C.c_longlong, _vp, _vp, _vp, C.c_int, _vp, _vp]),

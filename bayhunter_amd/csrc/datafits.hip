@@ -3,11 +3,10 @@
 // The reference looks at the data fit through PlotFromStorage.plot_bestdatafits / plot_rfcorr
 // (src/Plotting.py:1054-1150): one plugin call per chain.  Here the forward output of the whole posterior,
 // Y[nrows, stride] (ForwardEngine's `out`, first ncols columns), is reduced per column over rows that each
-// carry an integer weight, without expanding them.
-//
 // carry an integer weight, without expanding them.  The shared parts of that weighted column reduction are in
-// stats_core.h / stats_host.h (keys, slabs, the scan / finish hand-over, the radix select); this file has what
-// is its own:
+// stats_core.h / stats_host.h (keys, slabs, the scan / finish hand-over, the radix select); what a block does with
+// its rows is df_block in datafits_kernel.h, which datafits_sets.hip runs too (one set per block); this file has
+// the handle of one set:
 //
 //   mask    before the scan, one wave per row: the row's weight, or 0 when any of its err flags is non-zero
 //           or any of its ncols values is NaN (excluded); weighted totals of included / excluded rows,
@@ -22,53 +21,13 @@
 #include <memory>
 #include <new>
 #include "host_common.h"
-#include "stats_host.h"
+#include "datafits_kernel.h"
 
 namespace {
 
 using bh::u64;
-constexpr int kThreads = 256;
-constexpr int kCols = 8;                        // columns per blockIdx.y
-constexpr int kRowLanes = kThreads / kCols;     // rows a block reads at once
-constexpr int kGroups = 4;                      // digit histograms per column and block (LDS 8 * 4 * 256 * 8 B = 64 KiB)
-constexpr int kMaxBlocksX = 1024;               // fixed, so that the slab order depends on nrows only
-constexpr int kHistLdsBytes = 64 * 1024;
+using namespace bh::fit;
 constexpr int kMaxRanks = BH_DATAFITS_MAX_RANKS;
-
-enum { MODE_SCAN = 1, MODE_FINISH = 2, MODE_RADIX = 3 };
-
-struct FitArgs {
-    const double *Y;
-    long long nrows, stride;
-    int ncols;
-    const int *wk;                     // [nrows] effective weight (0: skip)
-    double *slab;                      // [gridDim.x][ncols]
-    // scan
-    u64 *kmin, *kmax;                  // [ncols]
-    // finish
-    const double *mean;                // [ncols]
-    const double *edges; int nedges;   // [nsets][nedges]
-    const int *eset;                   // [ncols]
-    u64 *hist;                         // [ncols][nedges - 1]
-    int do_hist, hist_lds;
-    // radix
-    int shift;                         // digit (key >> shift) & 255
-    const int *gbase, *ngroups;        // [ncols]: first slot of the column's groups, their number
-    const u64 *gpfx;                   // [slots] prefix (key >> (shift + 8)) of each group
-    u64 *digits;                       // [slots][256]
-};
-
-// Σ over the 32 row lanes of each column, in lane order: thread (rl, cl) -> column cl
-__device__ __forceinline__ double lanes_sum(double v, double *red, int tid)
-{
-    red[tid] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (tid < kCols)
-        for (int l = 0; l < kRowLanes; l++) s = s + red[l * kCols + tid];
-    __syncthreads();
-    return s;
-}
 
 // one wave per row: effective weights and the totals of included / excluded weight
 __global__ __launch_bounds__(kThreads) void df_mask_kernel(const double *Y, long long nrows, long long stride,
@@ -82,13 +41,8 @@ __global__ __launch_bounds__(kThreads) void df_mask_kernel(const double *Y, long
     u64 in = 0, ex = 0, neg = 0;
     const long long waves = (long long)gridDim.x * (kThreads / 64);
     for (long long r = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); r < nrows; r += waves) {
-        const long long wt = w ? (long long)w[r] : 1;
-        bool bad = false;
-        const double *row = Y + r * stride;
-        for (int c = lane; c < ncols; c += 64) bad |= !(row[c] == row[c]);
-        if (err)
-            for (int f = lane; f < nerr; f += 64) bad |= err[r * nerr + f] != 0;
-        bad = __any(bad);
+        long long wt;
+        const bool bad = mask_row(Y, stride, ncols, w, err, nerr, r, lane, wt);
         if (lane == 0) {
             if (wt < 0) neg++;
             else if (bad) ex += (u64)wt;
@@ -109,113 +63,12 @@ __global__ __launch_bounds__(kThreads) void df_mask_kernel(const double *Y, long
     }
 }
 
+// all rows are one set: block blockIdx.x of gridDim.x, group slice blockIdx.z (datafits_kernel.h)
 template <int MODE>
 __global__ __launch_bounds__(kThreads) void df_kernel(FitArgs a)
 {
-    extern __shared__ u64 lds[];
-    __shared__ double red[kThreads];
-    __shared__ u64 smin[kCols], smax[kCols];
-    const int tid = threadIdx.x;
-    const int cl = tid % kCols, rl = tid / kCols;
-    const int c = blockIdx.y * kCols + cl;
-    const bool valid = c < a.ncols;
-    const int cc = valid ? c : a.ncols - 1;
-
-    // radix: the groups [g0, g0 + kGroups) of this column that this block counts
-    const int g0 = blockIdx.z * kGroups;
-    int ng = 0, slot0 = 0;
-    u64 pf[kGroups];
-#pragma unroll
-    for (int j = 0; j < kGroups; j++) pf[j] = 0;
-    if (MODE == MODE_RADIX) {
-        if (valid) {
-            ng = a.ngroups[c] - g0;
-            ng = ng < 0 ? 0 : (ng > kGroups ? kGroups : ng);
-            slot0 = a.gbase[c] + g0;
-#pragma unroll
-            for (int j = 0; j < kGroups; j++) pf[j] = j < ng ? a.gpfx[slot0 + j] : 0;
-        }
-        // nothing to count in this slice for any column of the tile: the whole block leaves
-        int any = 0;
-        for (int j = 0; j < kCols; j++) {
-            const int cj = blockIdx.y * kCols + j;
-            any |= cj < a.ncols && a.ngroups[cj] > g0;
-        }
-        if (!any) return;
-    }
-    const bool whole = MODE == MODE_RADIX && a.shift + 8 >= 64;
-    const int nb = a.nedges - 1;
-    const double *ed = MODE == MODE_FINISH && a.do_hist ? a.edges + (size_t)a.eset[cc] * a.nedges : nullptr;
-    const double mu = MODE == MODE_FINISH ? a.mean[cc] : 0.0;
-
-    int nlds = 0;
-    if (MODE == MODE_RADIX) nlds = kCols * kGroups * 256;
-    if (MODE == MODE_FINISH && a.do_hist && a.hist_lds) nlds = kCols * nb;
-    for (int i = tid; i < nlds; i += kThreads) lds[i] = 0;
-    if (tid < kCols) { smin[tid] = ~0ull; smax[tid] = 0ull; }
-    __syncthreads();
-
-    double acc = 0.0;
-    u64 mn = ~0ull, mx = 0ull;
-    const long long step = (long long)gridDim.x * kRowLanes;
-    for (long long r = (long long)blockIdx.x * kRowLanes + rl; r < a.nrows; r += step) {
-        const int w = a.wk[r];
-        if (w == 0 || !valid) continue;
-        const double y = a.Y[r * a.stride + c];
-        if (MODE == MODE_SCAN) {
-            acc = acc + (double)w * y;
-            const u64 k = bh::post_key64(y);
-            mn = k < mn ? k : mn;
-            mx = k > mx ? k : mx;
-        } else if (MODE == MODE_FINISH) {
-            const double e = y - mu;
-            acc = acc + (double)w * (e * e);
-            const int b = a.do_hist ? bh::post_bin(ed, a.nedges, y) : -1;
-            if (b >= 0) {
-                if (a.hist_lds) atomicAdd(&lds[cl * nb + b], (u64)w);
-                else atomicAdd(&a.hist[(size_t)c * nb + b], (u64)w);
-            }
-        } else {
-            const u64 k = bh::post_key64(y);
-            const u64 hi = whole ? 0ull : (k >> (a.shift + 8));
-            const int dig = (int)((k >> a.shift) & 255u);
-#pragma unroll
-            for (int j = 0; j < kGroups; j++)
-                if (j < ng && hi == pf[j]) atomicAdd(&lds[(cl * kGroups + j) * 256 + dig], (u64)w);
-        }
-    }
-
-    if (MODE != MODE_RADIX) {
-        const double s = lanes_sum(acc, red, tid);
-        if (tid < kCols && blockIdx.y * kCols + tid < a.ncols)
-            a.slab[(size_t)blockIdx.x * a.ncols + blockIdx.y * kCols + tid] = s;
-    }
-    if (MODE == MODE_SCAN) {
-        if (mn != ~0ull) atomicMin(&smin[cl], mn);
-        if (mx != 0ull) atomicMax(&smax[cl], mx);
-        __syncthreads();
-        if (tid < kCols && blockIdx.y * kCols + tid < a.ncols) {
-            if (smin[tid] != ~0ull) atomicMin(&a.kmin[blockIdx.y * kCols + tid], smin[tid]);
-            if (smax[tid] != 0ull) atomicMax(&a.kmax[blockIdx.y * kCols + tid], smax[tid]);
-        }
-    }
-    if (MODE == MODE_FINISH && a.do_hist && a.hist_lds) {
-        __syncthreads();
-        for (int i = tid; i < kCols * nb; i += kThreads) {
-            const int cj = blockIdx.y * kCols + i / nb;
-            if (cj < a.ncols && lds[i]) atomicAdd(&a.hist[(size_t)cj * nb + i % nb], lds[i]);
-        }
-    }
-    if (MODE == MODE_RADIX) {
-        __syncthreads();
-        for (int i = tid; i < kCols * kGroups * 256; i += kThreads) {
-            const int cj = blockIdx.y * kCols + i / (kGroups * 256);
-            const int j = (i / 256) % kGroups;
-            if (cj >= a.ncols || !lds[i]) continue;
-            const int n = a.ngroups[cj] - g0;
-            if (j < n) atomicAdd(&a.digits[(size_t)(a.gbase[cj] + g0 + j) * 256 + (i % 256)], lds[i]);
-        }
-    }
+    a.g0 = blockIdx.z * kGroups;
+    df_block<MODE>(a, 0, a.nrows, blockIdx.x, gridDim.x);
 }
 
 }  // namespace
@@ -279,8 +132,7 @@ int bh_datafits_create(const double *Y, long long nrows, long long stride, int n
     p->err = err;
     p->nerr = err ? nerr : 0;
     p->st = (hipStream_t)stream;
-    long long g = (nrows + kRowLanes - 1) / kRowLanes;
-    p->G = (int)(g < kMaxBlocksX ? g : kMaxBlocksX);
+    p->G = blocks_of(nrows);
     int rc = p->alloc_columns();
     if (rc) return rc;
     BH_HIP(p->bufs.alloc(p->wk, (size_t)nrows));

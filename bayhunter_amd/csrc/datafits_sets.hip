@@ -1,0 +1,456 @@
+// datafits_sets.hip -- the data-fit statistics of many sets of rows at once (bh_datafits_sets_*).
+//
+// A network inverted in one pool (StationPool) is read station by station: the statistics of datafits.hip over each
+// station's rows of the modelled data.  One bh_datafits handle per station is a few thousand rows per launch, i.e.
+// the latency of its launches, copies and synchronisations times the number of stations.  Here the rows come in
+// contiguous segments, one per set, and a block belongs to one set: it runs the very body df_kernel runs
+// (datafits_kernel.h) over the set's rows, as block x of the G blocks a handle of that many rows would have launched,
+// with the set's own outputs.  The slab of a set is added in block order like there, the mean and the standard
+// deviation leave the host through the same expressions: every number of a set is bit for bit the number of a
+// bh_datafits handle over its rows.
+//
+//   mask     one launch for all rows; a wave keeps the totals of the set its rows are in and hands them over when
+//            its rows move on to another set
+//   grid     x: blocks of the largest set (a block beyond its set's G leaves at once), y: column tiles,
+//            z: set (scan, finish) or set * slices + group slice (radix passes)
+//   slab     the sets' partials one after the other, set z owning G(z) rows from goff[z]: about 1/32 of the
+//            matrix in all, so the scan and the finish take every set in one launch
+//   chunks   the select's digit table is 256 * 8 B per (rank, column), so the radix passes take the sets in chunks
+//            whose table stays under a budget; a set is never split, and nothing a set's blocks compute depends on
+//            the chunk
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <new>
+#include "host_common.h"
+#include "datafits_kernel.h"
+
+namespace {
+
+using bh::u64;
+using namespace bh::fit;
+constexpr int kMaxRanks = BH_DATAFITS_MAX_RANKS;
+
+struct SetArgs {
+    const long long *start;            // [nsets + 1] rows of set z: start[z] .. start[z + 1]
+    const long long *goff;             // [nsets + 1] slab rows before set z: Σ blocks_of over the sets before it
+    int first, gz;                     // the launch's first set; group slices per set (1 outside the radix passes)
+    const int *skip;                   // [nsets] finish and radix: the set is left out
+    int nesets;                        // edge sets per set
+};
+
+template <int MODE>
+__global__ __launch_bounds__(kThreads) void df_sets_kernel(FitArgs a, SetArgs s)
+{
+    const int zl = blockIdx.z / s.gz, z = s.first + zl;
+    const long long r0 = s.start[z], r1 = s.start[z + 1];
+    const int G = blocks_of(r1 - r0), bx = blockIdx.x;
+    if (bx >= G) return;
+    if (MODE != MODE_SCAN && s.skip[z]) return;
+    const size_t col = (size_t)z * a.ncols;
+    a.slab += (size_t)s.goff[z] * a.ncols;
+    if (MODE == MODE_SCAN) {
+        a.kmin += col;
+        a.kmax += col;
+    }
+    if (MODE == MODE_FINISH) {
+        a.mean += col;
+        if (a.do_hist) {
+            a.edges += (size_t)z * s.nesets * a.nedges;
+            a.hist += col * (a.nedges - 1);
+        }
+    }
+    if (MODE == MODE_RADIX) {
+        a.g0 = (blockIdx.z % s.gz) * kGroups;
+        a.gbase += (size_t)zl * a.ncols;
+        a.ngroups += (size_t)zl * a.ncols;
+    }
+    df_block<MODE>(a, r0, r1, bx, G);
+}
+
+// one wave per row, as df_mask_kernel; cnt[set][3]: included, excluded weight, rows with a negative weight.  The rows
+// of a wave ascend, so its sets do: lane 0 adds up the set it is in and hands the totals over when it leaves it.
+__global__ __launch_bounds__(kThreads) void df_sets_mask_kernel(const double *Y, long long nrows, long long stride,
+                                                               int ncols, const int *w, const int *err, int nerr,
+                                                               const long long *start, int nsets, int *wk, u64 *cnt)
+{
+    const int lane = threadIdx.x & 63;
+    int z = -1;
+    u64 in = 0, ex = 0, neg = 0;
+    const long long waves = (long long)gridDim.x * (kThreads / 64);
+    for (long long r = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); r < nrows; r += waves) {
+        long long wt;
+        const bool bad = mask_row(Y, stride, ncols, w, err, nerr, r, lane, wt);
+        if (lane == 0) {
+            if (z < 0 || r >= start[z + 1]) {
+                if (in) atomicAdd(&cnt[3 * (size_t)z], in);
+                if (ex) atomicAdd(&cnt[3 * (size_t)z + 1], ex);
+                if (neg) atomicAdd(&cnt[3 * (size_t)z + 2], neg);
+                in = ex = neg = 0;
+                int lo = z < 0 ? 0 : z + 1, hi = nsets;      // the last set with start <= r (empty sets lie before it)
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (start[mid] <= r) lo = mid;
+                    else hi = mid;
+                }
+                z = lo;
+            }
+            if (wt < 0) neg++;
+            else if (bad) ex += (u64)wt;
+            else in += (u64)wt;
+            wk[r] = (wt > 0 && !bad) ? (int)wt : 0;
+        }
+    }
+    if (lane == 0 && z >= 0) {
+        if (in) atomicAdd(&cnt[3 * (size_t)z], in);
+        if (ex) atomicAdd(&cnt[3 * (size_t)z + 1], ex);
+        if (neg) atomicAdd(&cnt[3 * (size_t)z + 2], neg);
+    }
+}
+
+// Σ over a set's blocks in block order: one thread per (set, column)
+__global__ void df_sets_reduce_kernel(const double *slab, const long long *start, const long long *goff, int nsets,
+                                      int n, double *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)nsets * n) return;
+    const int z = (int)(i / n), c = (int)(i % n);
+    const int G = blocks_of(start[z + 1] - start[z]);
+    const double *sl = slab + (size_t)goff[z] * n;
+    double s = 0.0;
+    for (int g = 0; g < G; g++) s = s + sl[(size_t)g * n + c];
+    out[i] = s;
+}
+
+}  // namespace
+
+struct bh_datafits_sets {
+    int n = 0, nerr = 0, nsets = 0, Gmax = 1, scanned = 0;
+    long long chunk_bytes = 0;
+    const double *Y = nullptr;
+    const int *w = nullptr, *err = nullptr;
+    long long nrows = 0, stride = 0;
+    hipStream_t st = nullptr;
+    std::vector<long long> start, goff;          // [nsets + 1]
+    std::vector<u64> total;                      // [nsets] of the scan
+    std::vector<int> status;                     // [nsets] of the scan
+    bh::DevBufs bufs;
+    // device
+    long long *dstart = nullptr, *dgoff = nullptr;
+    int *wk = nullptr, *dskip = nullptr;
+    u64 *cnt = nullptr, *kmin = nullptr, *kmax = nullptr;        // [nsets][3], [nsets][n], [nsets][n]
+    double *slab = nullptr, *red = nullptr, *dmean = nullptr;    // [goff[nsets]][n], [nsets][n], [nsets][n]
+
+    int chunk_blocks(int first, int nc) const
+    {
+        int g = 1;
+        for (int z = first; z < first + nc; z++) {
+            const int gs = blocks_of(start[z + 1] - start[z]);
+            g = gs > g ? gs : g;
+        }
+        return g;
+    }
+};
+
+namespace {
+
+FitArgs base_args(const bh_datafits_sets *p)
+{
+    FitArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.Y = p->Y;
+    a.nrows = p->nrows;
+    a.stride = p->stride;
+    a.ncols = p->n;
+    a.wk = p->wk;
+    a.slab = p->slab;
+    return a;
+}
+
+SetArgs set_args(const bh_datafits_sets *p)
+{
+    SetArgs s;
+    std::memset(&s, 0, sizeof(s));
+    s.start = p->dstart;
+    s.goff = p->dgoff;
+    s.gz = 1;
+    s.skip = p->dskip;
+    return s;
+}
+
+// sets [s.first, s.first + nc), s.gz group slices each
+template <int MODE>
+int launch(bh_datafits_sets *p, const FitArgs &a, const SetArgs &s, int nc, size_t lds)
+{
+    dim3 grid((unsigned)p->chunk_blocks(s.first, nc), (unsigned)((p->n + kCols - 1) / kCols), (unsigned)(nc * s.gz));
+    hipLaunchKernelGGL((df_sets_kernel<MODE>), grid, dim3(kThreads), lds, p->st, a, s);
+    BH_HIP(hipGetLastError());
+    return BH_OK;
+}
+
+// the slab of the pass just launched, added up per set: synchronises
+int reduce_slab(bh_datafits_sets *p, std::vector<double> &out)
+{
+    const size_t cols = (size_t)p->nsets * p->n;
+    hipLaunchKernelGGL(df_sets_reduce_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st,
+                       (const double *)p->slab, (const long long *)p->dstart, (const long long *)p->dgoff, p->nsets,
+                       p->n, p->red);
+    BH_HIP(hipGetLastError());
+    out.assign(cols, 0.0);
+    BH_HIP(hipMemcpyAsync(out.data(), p->red, sizeof(double) * cols, hipMemcpyDeviceToHost, p->st));
+    BH_HIP(hipStreamSynchronize(p->st));
+    return BH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *bh_datafits_sets_status_text(int status)
+{
+    return status == BH_DATAFITS_SET_EMPTY ? bh::scan_fault(0, 0)
+           : status == BH_DATAFITS_SET_OVERFLOW ? bh::scan_fault(~0ull, 0) : "";
+}
+
+int bh_datafits_sets_set_chunk_bytes(bh_datafits_sets *p, long long bytes)
+{
+    if (!p) return bh::fail_arg_("fits is NULL");
+    p->chunk_bytes = bytes > 0 ? bytes : 0;
+    return BH_OK;
+}
+
+int bh_datafits_sets_create(const double *Y, long long nrows, long long stride, int ncols, const int *weights,
+                            const int *err, int nerr, const long long *set_start, int nsets, void *stream,
+                            bh_datafits_sets **fits)
+{
+    if (!fits) return bh::fail_arg_("fits is NULL");
+    *fits = nullptr;
+    if (!Y || nrows < 1) return bh::fail_arg_("bh_datafits_sets_create: no rows (empty selection)");
+    if (nrows > (1ll << 32)) return bh::fail_arg_("bh_datafits_sets_create: more than 2^32 rows (the weight total could overflow)");
+    if (ncols < 1) return bh::fail_arg_("bh_datafits_sets_create: ncols < 1");
+    if (stride < ncols) return bh::fail_arg_("bh_datafits_sets_create: stride < ncols");
+    if (err && nerr < 1) return bh::fail_arg_("bh_datafits_sets_create: err flags given with nerr < 1");
+    if (nsets < 1 || nsets > kMaxGridZ) return bh::fail_arg_("bh_datafits_sets_create: 1 to 65535 sets");
+    if (!set_start || set_start[0] != 0 || set_start[nsets] != nrows)
+        return bh::fail_arg_("bh_datafits_sets_create: set_start must begin at 0 and end at nrows");
+    for (int z = 0; z < nsets; z++)
+        if (set_start[z] > set_start[z + 1]) return bh::fail_arg_("bh_datafits_sets_create: set_start must be ascending");
+    if ((long long)nsets * ncols > 0x3fffffff) return bh::fail_arg_("bh_datafits_sets_create: more than 2^30 (set, column) pairs");
+    if (int rc = bh::require_device()) return rc;
+    std::unique_ptr<bh_datafits_sets> p(new (std::nothrow) bh_datafits_sets);
+    if (!p) return bh::fail_arg_("out of memory");
+    p->Y = Y;
+    p->nrows = nrows;
+    p->stride = stride;
+    p->n = ncols;
+    p->w = weights;
+    p->err = err;
+    p->nerr = err ? nerr : 0;
+    p->nsets = nsets;
+    p->st = (hipStream_t)stream;
+    p->start.assign(set_start, set_start + nsets + 1);
+    p->goff.assign((size_t)nsets + 1, 0);
+    for (int z = 0; z < nsets; z++) p->goff[z + 1] = p->goff[z] + blocks_of(set_start[z + 1] - set_start[z]);
+    p->Gmax = p->chunk_blocks(0, nsets);
+    p->total.assign(nsets, 0);
+    p->status.assign(nsets, BH_DATAFITS_SET_EMPTY);
+    const size_t cols = (size_t)nsets * ncols;
+    BH_HIP(p->bufs.alloc(p->dstart, (size_t)nsets + 1));
+    BH_HIP(p->bufs.alloc(p->dgoff, (size_t)nsets + 1));
+    BH_HIP(p->bufs.alloc(p->wk, (size_t)nrows));
+    BH_HIP(p->bufs.alloc(p->dskip, nsets));
+    BH_HIP(p->bufs.alloc(p->cnt, 3 * (size_t)nsets));
+    BH_HIP(p->bufs.alloc(p->kmin, cols));
+    BH_HIP(p->bufs.alloc(p->kmax, cols));
+    BH_HIP(p->bufs.alloc(p->slab, (size_t)p->goff[nsets] * ncols));
+    BH_HIP(p->bufs.alloc(p->red, cols));
+    BH_HIP(p->bufs.alloc(p->dmean, cols));
+    BH_HIP(hipMemcpyAsync(p->dstart, p->start.data(), sizeof(long long) * ((size_t)nsets + 1), hipMemcpyHostToDevice, p->st));
+    BH_HIP(hipMemcpyAsync(p->dgoff, p->goff.data(), sizeof(long long) * ((size_t)nsets + 1), hipMemcpyHostToDevice, p->st));
+    BH_HIP(hipStreamSynchronize(p->st));
+    *fits = p.release();
+    return BH_OK;
+}
+
+void bh_datafits_sets_destroy(bh_datafits_sets *fits)
+{
+    if (fits) {
+        (void)hipStreamSynchronize(fits->st);
+        delete fits;
+    }
+}
+
+int bh_datafits_sets_scan(bh_datafits_sets *p, long long *total, long long *excluded, double *vmin, double *vmax,
+                          double *mean, int *status)
+{
+    if (!p) return bh::fail_arg_("fits is NULL");
+    if (!status) return bh::fail_arg_("bh_datafits_sets_scan: status is NULL");
+    p->scanned = 0;
+    const int N = p->n, S = p->nsets;
+    const int cols = S * N;
+    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmin, cols, ~0ull);
+    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmax, cols, 0ull);
+    BH_HIP(hipGetLastError());
+    BH_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 3 * (size_t)S, p->st));
+    {
+        const long long blocks = (p->nrows + kThreads / 64 - 1) / (kThreads / 64);
+        hipLaunchKernelGGL(df_sets_mask_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kThreads), 0, p->st,
+                           p->Y, p->nrows, p->stride, N, p->w, p->err, p->nerr, (const long long *)p->dstart, S, p->wk,
+                           p->cnt);
+        BH_HIP(hipGetLastError());
+    }
+    FitArgs a = base_args(p);
+    a.kmin = p->kmin;
+    a.kmax = p->kmax;
+    SetArgs s = set_args(p);
+    int rc = launch<MODE_SCAN>(p, a, s, S, 0);
+    if (rc) return rc;
+    std::vector<u64> cnt(3 * (size_t)S), kmn((size_t)cols), kmx((size_t)cols);
+    BH_HIP(hipMemcpyAsync(cnt.data(), p->cnt, sizeof(u64) * cnt.size(), hipMemcpyDeviceToHost, p->st));
+    BH_HIP(hipMemcpyAsync(kmn.data(), p->kmin, sizeof(u64) * kmn.size(), hipMemcpyDeviceToHost, p->st));
+    BH_HIP(hipMemcpyAsync(kmx.data(), p->kmax, sizeof(u64) * kmx.size(), hipMemcpyDeviceToHost, p->st));
+    std::vector<double> sum;
+    rc = reduce_slab(p, sum);                      // synchronises the stream
+    if (rc) return rc;
+    for (int z = 0; z < S; z++)
+        if (cnt[3 * (size_t)z + 2])
+            return bh::fail_arg_((std::string("bh_datafits_sets_scan: ") + bh::scan_fault(cnt[3 * (size_t)z], 1)).c_str());
+    std::vector<double> mu((size_t)cols);
+    const double nan = std::nan("");
+    for (int z = 0; z < S; z++) {
+        const u64 included = cnt[3 * (size_t)z];
+        p->total[z] = included;
+        p->status[z] = included == 0 ? BH_DATAFITS_SET_EMPTY
+                       : included > (1ull << 53) ? BH_DATAFITS_SET_OVERFLOW : BH_DATAFITS_SET_OK;
+        status[z] = p->status[z];
+        const bool live = p->status[z] == BH_DATAFITS_SET_OK;
+        if (total) total[z] = (long long)included;
+        if (excluded) excluded[z] = (long long)cnt[3 * (size_t)z + 1];
+        for (int c = 0; c < N; c++) {
+            const size_t i = (size_t)z * N + c;
+            mu[i] = live ? sum[i] / (double)included : nan;
+            if (vmin) vmin[i] = live ? bh::post_unkey64(kmn[i]) : nan;
+            if (vmax) vmax[i] = live ? bh::post_unkey64(kmx[i]) : nan;
+            if (mean) mean[i] = mu[i];
+        }
+    }
+    BH_HIP(hipMemcpyAsync(p->dmean, mu.data(), sizeof(double) * cols, hipMemcpyHostToDevice, p->st));
+    BH_HIP(hipStreamSynchronize(p->st));
+    p->scanned = 1;
+    return BH_OK;
+}
+
+int bh_datafits_sets_finish(bh_datafits_sets *p, const long long *ranks, int nranks, double *order_stats,
+                            const double *edges, int nedges, int nesets, const int *eset, long long *hist,
+                            double *stdev)
+{
+    // the arguments first: what needs no handle, then what the scan decides; nothing is launched before
+    if (nranks < 0 || nranks > kMaxRanks) return bh::fail_arg_("bh_datafits_sets_finish: 0 to 16 ranks");
+    if (nranks && (!ranks || !order_stats)) return bh::fail_arg_("bh_datafits_sets_finish: ranks and order_stats");
+    const bool want_hist = edges != nullptr;
+    if (want_hist && (nedges < 2 || nesets < 1 || !eset || !hist))
+        return bh::fail_arg_("bh_datafits_sets_finish: edges need nedges >= 2, nsets >= 1, eset and hist");
+    if (!p) return bh::fail_arg_("fits is NULL");
+    if (!p->scanned) return bh::fail_arg_("bh_datafits_sets_finish before a successful bh_datafits_sets_scan");
+    const int N = p->n, S = p->nsets;
+    std::vector<int> skip(S);
+    for (int z = 0; z < S; z++) {
+        skip[z] = p->status[z] != BH_DATAFITS_SET_OK;
+        if (skip[z]) continue;
+        for (int i = 0; i < nranks; i++) {
+            const long long r = ranks[(size_t)z * nranks + i];
+            if (r < 0) return bh::fail_arg_("bh_datafits_sets_finish: negative rank");
+            if ((u64)r >= p->total[z]) return bh::fail_arg_("bh_datafits_sets_finish: rank >= the weight total");
+        }
+        for (int e = 0; want_hist && e < nesets; e++)
+            if (!bh::ascending(edges + ((size_t)z * nesets + e) * nedges, nedges))
+                return bh::fail_arg_("bh_datafits_sets_finish: edges must be ascending");
+    }
+    if (want_hist)
+        for (int c = 0; c < N; c++)
+            if (eset[c] < 0 || eset[c] >= nesets) return bh::fail_arg_("bh_datafits_sets_finish: edge set out of range");
+
+    bh::CallBufs tmp(p->st);
+    const int nb = nedges - 1;
+    const size_t cols = (size_t)S * N;
+    const double nan = std::nan("");
+    BH_HIP(hipMemcpyAsync(p->dskip, skip.data(), sizeof(int) * S, hipMemcpyHostToDevice, p->st));
+    if (stdev || want_hist) {
+        FitArgs a = base_args(p);
+        a.mean = p->dmean;
+        SetArgs s = set_args(p);
+        size_t lds = 0;
+        if (want_hist) {
+            double *ded = nullptr;
+            int *dset = nullptr;
+            const size_t ne = (size_t)S * nesets * nedges;
+            BH_HIP(tmp.alloc(ded, ne));
+            BH_HIP(tmp.alloc(dset, N));
+            BH_HIP(tmp.alloc(a.hist, cols * nb));
+            BH_HIP(hipMemcpyAsync(ded, edges, sizeof(double) * ne, hipMemcpyHostToDevice, p->st));
+            BH_HIP(hipMemcpyAsync(dset, eset, sizeof(int) * N, hipMemcpyHostToDevice, p->st));
+            BH_HIP(hipMemsetAsync(a.hist, 0, sizeof(u64) * cols * nb, p->st));
+            a.edges = ded;
+            a.nedges = nedges;
+            a.eset = dset;
+            a.do_hist = 1;
+            a.hist_lds = (size_t)kCols * nb * sizeof(u64) <= (size_t)kHistLdsBytes;
+            lds = a.hist_lds ? (size_t)kCols * nb * sizeof(u64) : 0;
+            s.nesets = nesets;
+        }
+        int rc = launch<MODE_FINISH>(p, a, s, S, lds);
+        if (!rc && stdev) {
+            std::vector<double> sq;
+            rc = reduce_slab(p, sq);                                 // synchronises the stream
+            for (int z = 0; !rc && z < S; z++)
+                for (int c = 0; c < N; c++) {
+                    const size_t i = (size_t)z * N + c;
+                    stdev[i] = skip[z] ? nan : std::sqrt(sq[i] / (double)p->total[z]);
+                }
+        }
+        if (!rc && want_hist) rc = bh::read_hist(a.hist, cols * nb, hist, p->st);
+        if (rc) return rc;
+    }
+    if (!nranks) return BH_OK;
+
+    const int gz_max = (nranks + kGroups - 1) / kGroups;
+    const int chunk = sets_per_chunk(S, N, nranks, gz_max, p->chunk_bytes);
+    FitArgs r = base_args(p);
+    SetArgs s = set_args(p);
+    std::vector<uint64_t> rk;
+    for (int first = 0; first < S; first += chunk) {
+        const int nc = S - first < chunk ? S - first : chunk;
+        // every set its own ranks, because the weight totals differ: [nranks][nc * N]
+        rk.assign((size_t)nranks * nc * N, 0);
+        for (int i = 0; i < nranks; i++)
+            for (int zl = 0; zl < nc; zl++) {
+                const uint64_t v = skip[first + zl] ? 0 : (uint64_t)ranks[(size_t)(first + zl) * nranks + i];
+                for (int c = 0; c < N; c++) rk[((size_t)i * nc + zl) * N + c] = v;
+            }
+        bh::CallBufs seltmp(p->st);
+        bh::DeviceSelect sel(nc * N, nranks, 64, rk.data(), bh::RadixSelect::PerColumn());
+        int rc = sel.alloc(seltmp);
+        if (rc) return rc;
+        r.gbase = sel.dgbase;
+        r.ngroups = sel.dngroups;
+        r.gpfx = sel.dgpfx;
+        r.digits = sel.ddigits;
+        s.first = first;
+        while (!sel.done()) {
+            rc = sel.begin_pass(p->st);
+            r.shift = sel.shift;
+            s.gz = (sel.maxgroups + kGroups - 1) / kGroups;
+            if (!rc) rc = launch<MODE_RADIX>(p, r, s, nc, sizeof(u64) * kCols * kGroups * 256);
+            if (!rc) rc = sel.end_pass(p->st);
+            if (rc) return rc;
+        }
+        for (int zl = 0; zl < nc; zl++)
+            for (int i = 0; i < nranks; i++)
+                for (int c = 0; c < N; c++)
+                    order_stats[((size_t)(first + zl) * nranks + i) * N + c] =
+                        skip[first + zl] ? nan : bh::post_unkey64(sel.key(i, zl * N + c));
+    }
+    return BH_OK;
+}
+
+}  // extern "C"

@@ -314,6 +314,23 @@ int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const d
                          0, nullptr, nullptr);
 }
 
+int bh_forward_batch_sets(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                          const double *vs, const double *rho, int nswd, const bh_swd_target *swd, const double *periods,
+                          int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
+                          double mean_layers, int concurrent_calls, double *out, int out_stride, int *err, void *workspace,
+                          size_t workspace_bytes, void *stream, void *rf_stream, int nsets, const double *rf_set_p,
+                          const int *set_id)
+{
+    if (rf_set_p) {                        // (what bh_rf_batch_sets would refuse only after the dispersion launch)
+        if (nrf < 1) return bh::fail_arg_("bh_forward_batch_sets: ray parameters without a receiver-function target");
+        if (nsets < 1) return bh::fail_arg_("bh_forward_batch_sets: nsets < 1");
+        if (!set_id && nsets > 1) return bh::fail_arg_("bh_forward_batch_sets: set_id is NULL with more than one set");
+    }
+    return forward_batch(B, Lmax, model_stride, nlay, h, vp, vs, rho, nswd, swd, periods, ninterp, interp, nrf, rf, order,
+                         mean_layers, concurrent_calls, out, out_stride, err, workspace, workspace_bytes, stream, rf_stream,
+                         rf_set_p ? nsets : 0, rf_set_p, rf_set_p ? set_id : nullptr);
+}
+
 }  // extern "C"
 
 // the launches of one submission; `forked` tells the caller whether the side stream was made to wait

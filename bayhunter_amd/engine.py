@@ -118,10 +118,14 @@ class ForwardEngine(object):
         err = torch.empty((B, max(1, len(self.swd))), dtype=torch.int32, device=self.device)
         return out, err
 
-    def run(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, stream=None):
+    def run(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, stream=None, rf_sets=None):
         """Launch all targets for the batch (asynchronous).  Either `run(models)` with resident
         DeviceModels (from `upload` / models.layers_from_voronoi) or `run(H, VP, VS, RHO, nlay)`
-        with host or device arrays, which are packed first.  Returns (out[B,row], err[B,nswd])."""
+        with host or device arrays, which are packed first.  Returns (out[B,row], err[B,nswd]).
+
+        rf_sets = (set_p, set_id): every row's receiver functions at the ray parameter of the row's set (station)
+        instead of the engine's -- set_p [nrf][nsets] fp64 and set_id [B] int32, device tensors
+        (bh_forward_batch_sets; a row is bit for bit what an engine with that p computes)."""
         models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
         if models.packed.device != self.device:
             raise ValueError("models live on %s, engine on %s" % (models.packed.device, self.device))
@@ -161,14 +165,24 @@ class ForwardEngine(object):
                                                                     device=self.device)
                 ws_ptr = ws.data_ptr()
             # row, descriptors and overlap are read at every call: a caller may move a target's columns (bench.py)
-            _lib.check(self.lib.bh_forward_batch(
-                B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(), RHO.data_ptr(),
-                len(self.swd), self._tg, self.periods.data_ptr(), len(self._obsx), self._interp, len(self.rf),
-                self._rfp, models.order.data_ptr() if models.order is not None else None, models.mean_depth or 0.0, 1,
-                out.data_ptr(), self.row, err.data_ptr(), ws_ptr, need, sp,
-                sp if side is None else C.c_void_p(side.cuda_stream)))
+            args = (B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(), RHO.data_ptr(),
+                    len(self.swd), self._tg, self.periods.data_ptr(), len(self._obsx), self._interp, len(self.rf),
+                    self._rfp, models.order.data_ptr() if models.order is not None else None, models.mean_depth or 0.0, 1,
+                    out.data_ptr(), self.row, err.data_ptr(), ws_ptr, need, sp,
+                    sp if side is None else C.c_void_p(side.cuda_stream))
+            if rf_sets is None:
+                _lib.check(self.lib.bh_forward_batch(*args))
+            else:
+                set_p, set_id = rf_sets
+                if not self.rf or set_p.dim() != 2 or set_p.shape[0] != len(self.rf) or set_p.dtype != torch.float64 \
+                        or not set_p.is_contiguous() or set_p.device != self.device:
+                    raise ValueError("rf_sets: set_p [nrf][nsets] float64, contiguous, on the engine's device")
+                if set_id.shape != (B,) or set_id.dtype != torch.int32 or not set_id.is_contiguous() \
+                        or set_id.device != self.device:
+                    raise ValueError("rf_sets: set_id [B] int32, contiguous, on the engine's device")
+                _lib.check(self.lib.bh_forward_batch_sets(*(args + (set_p.shape[1], set_p.data_ptr(), set_id.data_ptr()))))
             if side is not None:
                 st.wait_stream(side)
-                for t in (H, VP, VS, RHO, nlay, out):
+                for t in (H, VP, VS, RHO, nlay, out) + (() if rf_sets is None else tuple(rf_sets)):
                     t.record_stream(side)
         return out, err

@@ -12,6 +12,7 @@ it is in, so a station's chains are bit for bit the chains of a `ChainPool` of t
                        random_seeds=[11, 12, ...]).run()
     pool.station('ST2').posterior()          # the interface of a ChainPool, restricted to the station's chains
     pool.posterior().mean                    # every station's posterior in one pass: [nstations, depths]
+    pool.datafits().mean[0]                  # ... and its modelled data, per target: [nstations, samples]
     pool.save()                              # one directory per station, each what a single-station pool writes
 
 One plugin parameter may differ between stations when the pool is told so: the ray parameter `p` of a receiver
@@ -422,6 +423,21 @@ class StationPool(object):
         failed station is a ValueError naming the first one."""
         from .posterior import stations_posterior
         return stations_posterior(self, dep_int, depint, dev, exclude_outliers, selection, device, strict)
+
+    def datafits(self, selection='weighted', dev=0.05, exclude_outliers=True, q=(2.5, 16, 50, 84, 97.5), nbins=100,
+                 device=None, strict=True, max_rows=None):
+        """The statistics of the modelled data of every station in one pass (datafits.summarize_sets): one forward
+        pass over the rows posterior() takes -- every row at its own station's ray parameter with per_station=('p',)
+        -- and one segmented reduction (bh_datafits_sets_*), instead of a forward pass and a handle per station.  Per
+        station the very dict station(s).datafits(...) returns, bit for bit ('chains' and 'bestfits' numbered within
+        the station; the observed value and the residual of a gap NaN).  -> datafits.StationDatafits: `stations[name]`
+        those dicts, `failed` {name: message}, and per target the stacked `mean / std / median / min / max / best /
+        residual [nstations, S]`, `quantiles [nstations, len(q), S]`, and `nmodels`, `nexcluded [nstations]`, with NaN
+        rows for failed stations.  strict=True: a failed station is a ValueError naming the first one.  max_rows: the
+        stations are taken in runs of whole stations of at most that many rows (default: what half of the free device
+        memory holds); no result depends on it."""
+        from .datafits import stations_datafits
+        return stations_datafits(self, selection, dev, exclude_outliers, q, nbins, device, strict, max_rows)
 
     def moho(self, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50, device=None):
         """Moho depth +- std, crustal Vs and the share of models with a Moho of every station in one pass over the

@@ -517,6 +517,16 @@ int bh_forward_batch(int B, int Lmax, int model_stride, const int *nlay, const d
                      int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
                      double mean_layers, int concurrent_calls, double *out, int out_stride, int *err,
                      void *workspace, size_t workspace_bytes, void *stream, void *rf_stream);
+/* The same with every row's receiver functions at the ray parameter of the row's set (the stations of a network):
+ * rf_set_p DEVICE [nrf][nsets] (target i at set s: rf_set_p[i * nsets + s]; rf[i].p is ignored) and set_id DEVICE
+ * int32 [B] (may be NULL with one set) send every receiver-function target through bh_rf_batch_sets, whose rows are
+ * bit for bit bh_rf_batch's at that p.  rf_set_p NULL: bh_forward_batch (nsets and set_id are ignored). */
+int bh_forward_batch_sets(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                          const double *vs, const double *rho, int nswd, const bh_swd_target *swd, const double *periods,
+                          int ninterp, const bh_eval_interp *interp, int nrf, const bh_rf_params *rf, const int *order,
+                          double mean_layers, int concurrent_calls, double *out, int out_stride, int *err,
+                          void *workspace, size_t workspace_bytes, void *stream, void *rf_stream, int nsets,
+                          const double *rf_set_p, const int *set_id);
 int  bh_eval_create(int max_models, int Lmax, int row, int nswd, const bh_swd_target *swd,
                     const double *periods, int nperiods, int nrf, const bh_rf_params *rf, int ntargets,
                     const bh_like_target *like, int nflags, const double *yobs, const double *aux,
@@ -667,6 +677,53 @@ int  bh_datafits_finish(bh_datafits *fits, const long long *ranks, int nranks, d
                         const double *edges, int nedges, int nsets, const int *eset, long long *hist,
                         double *stdev);
 void bh_datafits_destroy(bh_datafits *fits);
+
+/* ---- the same statistics for many sets of rows in one pass (the stations of a network) ----- */
+/* The rows of Y come in contiguous segments, one per set: set s is rows set_start[s] .. set_start[s + 1].  Every
+ * number reported for a set is bit for bit what a bh_datafits handle over that set's rows alone reports (a block of
+ * the kernel belongs to one set and runs as the block it would be there; the per-block partials of a set are reduced
+ * in the same order), from one mask launch, one scan launch, one finish launch and one launch per radix pass and
+ * chunk of sets.
+ *
+ * Y, weights, err, nerr, stream    as for bh_datafits_create
+ * set_start  HOST [nsets + 1], ascending, set_start[0] = 0, set_start[nsets] = nrows; 1 <= nsets <= 65535.  A set may
+ *            be empty
+ *
+ *   bh_datafits_sets_create   BH_ERR_ARG for what bh_datafits_create refuses and for a bad set_start / nsets
+ *   bh_datafits_sets_scan     per set: included weight total and excluded weight [nsets], min / max / mean
+ *                             [nsets][ncols], and status [nsets] (required): BH_DATAFITS_SET_OK, or why the set has
+ *                             no statistics (bh_datafits_sets_status_text: the words bh_datafits_scan fails with) --
+ *                             no included row of positive weight, an empty segment among them.  Such a set has total
+ *                             0, NaN min / max / mean and is left out by the finish; the call succeeds.  A negative
+ *                             weight anywhere fails the call
+ *   bh_datafits_sets_finish   after a scan, each part optional as for bh_datafits_finish: ranks [nsets][nranks]
+ *                             (every set its own, 0 <= rank < the set's total, at most BH_DATAFITS_MAX_RANKS a set)
+ *                             -> order_stats [nsets][nranks][ncols]; edges [nsets][nesets][nedges] (every set its
+ *                             own edge sets, each ascending) and eset [ncols] (the edge set of column c, the same
+ *                             for all sets) -> hist [nsets][ncols][nedges - 1]; stdev [nsets][ncols].  A set of
+ *                             non-zero status is skipped: its ranks and edges are not looked at, its order
+ *                             statistics and std are NaN, its histogram 0.  All arguments are checked before the
+ *                             first launch
+ *   bh_datafits_sets_set_chunk_bytes   the radix passes take the sets in chunks (one after the other on the handle's
+ *                             stream, a set never split) so that the select's digit table of a chunk, 256 * 8 B per
+ *                             (set, rank, column), stays under 64 MiB.  This sets the handle's own bound (<= 0: the
+ *                             default).  No result depends on it
+ * Every output is a HOST buffer; each call returns when its results are there.  Two runs are bit-identical. */
+#define BH_DATAFITS_SET_OK       0
+#define BH_DATAFITS_SET_EMPTY    1   /* no included row with a positive weight */
+#define BH_DATAFITS_SET_OVERFLOW 2   /* weight total above 2^53 */
+typedef struct bh_datafits_sets bh_datafits_sets;
+int  bh_datafits_sets_create(const double *Y, long long nrows, long long stride, int ncols, const int *weights,
+                             const int *err, int nerr, const long long *set_start, int nsets, void *stream,
+                             bh_datafits_sets **fits);
+int  bh_datafits_sets_scan(bh_datafits_sets *fits, long long *total, long long *excluded, double *vmin, double *vmax,
+                           double *mean, int *status);
+int  bh_datafits_sets_finish(bh_datafits_sets *fits, const long long *ranks, int nranks, double *order_stats,
+                             const double *edges, int nedges, int nesets, const int *eset, long long *hist,
+                             double *stdev);
+void bh_datafits_sets_destroy(bh_datafits_sets *fits);
+const char *bh_datafits_sets_status_text(int status);
+int  bh_datafits_sets_set_chunk_bytes(bh_datafits_sets *fits, long long bytes);
 
 /* ---- Moho depth and crustal velocity ------------------------------------------------------ */
 /* What PlotFromStorage.plot_moho_crustvel_tradeoff (src/Plotting.py:753-902) derives from every posterior model

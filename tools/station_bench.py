@@ -9,7 +9,7 @@ vp/vs and noise, like tools/chain_bench.py).  For S stations of c chains each, t
                the output: "scaled": true)
 
     python tools/station_bench.py [--modes stations,onepool,singles] [--repeats 5] [--sample 16] [--root DIR]
-                                  [--vary-p LO HI] [--gaps FRACTION] [--out FILE.jsonl] [SxC ...]
+                                  [--vary-p LO HI] [--gaps FRACTION] [--posterior | --datafits] [--out FILE.jsonl] [SxC ...]
                                   (default 64x16 256x16 1024x16 1024x4)
 
 --vary-p LO HI: every station its own receiver-function ray parameter, spread evenly over [LO, HI] s/deg; the station
@@ -27,6 +27,10 @@ is summarised twice: by the loop over its station views (pool.station(s).posteri
 and by StationPool.posterior() (one pass over all stations).  Each is warmed once, then timed --repeats times
 wall-clock around a device synchronisation; the two results are asserted equal, field by field and bit for bit,
 before a time is reported.  One JSON line per S x c.
+
+--datafits: the same for the statistics of the modelled data: the loop over pool.station(s).datafits() (one forward
+pass and one bh_datafits handle per station) against StationPool.datafits() (one forward pass and one bh_datafits_sets
+handle for all stations); with --vary-p the pool has per_station=('p',).
 
 A warm-up pool of every mode runs first; then `--repeats` rounds, each round running every mode once (alternating,
 so that a drift of the box hits all modes alike).  One JSON line per (S, c, mode) with every repeat's seconds,
@@ -55,11 +59,13 @@ def main():
                     help="fraction of the dispersion periods missing at every station but the first; pooled with missing='mask'")
     ap.add_argument('--posterior', action='store_true',
                     help='time StationPool.posterior() against the loop over station views on one finished pool')
+    ap.add_argument('--datafits', action='store_true',
+                    help='time StationPool.datafits() against the loop over station views on one finished pool')
     ap.add_argument('--tag', default=None)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if not args.configs:
-        args.configs = ['64x16', '256x16', '1024x16'] + ([] if args.posterior else ['1024x4'])
+        args.configs = ['64x16', '256x16', '1024x16'] + ([] if args.posterior or args.datafits else ['1024x4'])
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     root = os.path.abspath(args.root) if args.root else here
     sys.path.insert(0, os.path.join(here, 'tests', 'scenarios'))
@@ -128,18 +134,21 @@ def main():
             x, y = np.asarray(a), np.asarray(b)
             assert np.array_equal(x, y, equal_nan=x.dtype.kind in 'fc'), path
 
-    def posterior_leg(S, c, iters, stations):
+    def readout_leg(what, S, c, iters, stations):
+        """what: 'posterior' or 'datafits' -- the method of the station views and of the pool"""
         import torch
         from bayhunter_amd.stations import StationPool
-        with StationPool(stations, params(iters), case['priors'], seeds=seeds_of(S, c), nmodels=iters + iters // 2 + 1) as pool:
+        per = dict(per_station=('p',)) if args.vary_p else {}
+        with StationPool(stations, params(iters), case['priors'], seeds=seeds_of(S, c), nmodels=iters + iters // 2 + 1,
+                         **per) as pool:
             pool.run()
 
         def loop():
             out, failed = {}, {}
             for name in pool.names:
                 try:
-                    out[name] = pool.station(name).posterior()
-                except ValueError as e:
+                    out[name] = getattr(pool.station(name), what)()
+                except (ValueError, bayhunter_amd._lib.BayHunterAmdError) as e:
                     failed[name] = str(e)
             return out, failed
 
@@ -150,7 +159,7 @@ def main():
             torch.cuda.synchronize()
             return time.perf_counter() - t0, r
 
-        one = lambda: pool.posterior(strict=False)
+        one = lambda: getattr(pool, what)(strict=False)
         (_, (want, wfailed)), (_, got) = timed(loop), timed(one)       # warm
         assert sorted(got.failed) == sorted(wfailed) and list(got.stations) == list(want), (got.failed, wfailed)
         same(got.stations, want)
@@ -159,7 +168,7 @@ def main():
             secs['loop'].append(timed(loop)[0])
             secs['one_call'].append(timed(one)[0])
         med = {k: float(np.median(v)) for k, v in secs.items()}
-        return dict(bench='station_posterior', tag=args.tag, stations=S, chains_per_station=c, chains=S * c,
+        return dict(bench='station_' + what, tag=args.tag, src=bayhunter_amd._lib.built_hash(), vary_p=args.vary_p, stations=S, chains_per_station=c, chains=S * c,
                     iterations=iters + iters // 2, models=int(sum(r['nmodels'] for r in want.values())),
                     stations_failed=len(wfailed), equal=True, repeats=args.repeats,
                     loop_s=[round(x, 4) for x in secs['loop']], one_call_s=[round(x, 4) for x in secs['one_call']],
@@ -170,16 +179,16 @@ def main():
         S, c = (int(v) for v in cfg.lower().split('x'))
         iters = args.iters or (120 if S * c <= 4096 else 60)
         stations = make_stations(data, S, yerr=True)
-        if args.posterior:
-            line = json.dumps(posterior_leg(S, c, iters, stations))
+        if args.vary_p:
+            for joint, p in zip(stations, np.linspace(args.vary_p[0], args.vary_p[1], S)):
+                joint.targets[1].moddata.plugin.set_modelparams(p=float(p))
+        if args.posterior or args.datafits:
+            line = json.dumps(readout_leg('posterior' if args.posterior else 'datafits', S, c, iters, stations))
             print(line, flush=True)
             if args.out:
                 with open(args.out, 'a') as fh:
                     fh.write(line + '\n')
             continue
-        if args.vary_p:
-            for joint, p in zip(stations, np.linspace(args.vary_p[0], args.vary_p[1], S)):
-                joint.targets[1].moddata.plugin.set_modelparams(p=float(p))
         if args.gaps:
             for s, joint in enumerate(stations[1:], 1):
                 y = joint.targets[0].obsdata.y.copy()
