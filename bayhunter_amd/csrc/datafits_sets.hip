@@ -13,8 +13,8 @@
 //            its rows move on to another set
 //   grid     x: blocks of the largest set (a block beyond its set's G leaves at once), y: column tiles,
 //            z: set (scan, finish) or set * slices + group slice (radix passes)
-//   slab     the sets' partials one after the other, set z owning G(z) rows from goff[z]: about 1/32 of the
-//            matrix in all, so the scan and the finish take every set in one launch
+//   slab     the sets' partials one after the other, set z owning G(z) rows from goff[z] (stats_host.h: SetStats):
+//            about 1/32 of the matrix in all, so the scan and the finish take every set in one launch
 //   chunks   the select's digit table is 256 * 8 B per (rank, column), so the radix passes take the sets in chunks
 //            whose table stays under a budget; a set is never split, and nothing a set's blocks compute depends on
 //            the chunk
@@ -108,48 +108,17 @@ __global__ __launch_bounds__(kThreads) void df_sets_mask_kernel(const double *Y,
     }
 }
 
-// Σ over a set's blocks in block order: one thread per (set, column)
-__global__ void df_sets_reduce_kernel(const double *slab, const long long *start, const long long *goff, int nsets,
-                                      int n, double *out)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)nsets * n) return;
-    const int z = (int)(i / n), c = (int)(i % n);
-    const int G = blocks_of(start[z + 1] - start[z]);
-    const double *sl = slab + (size_t)goff[z] * n;
-    double s = 0.0;
-    for (int g = 0; g < G; g++) s = s + sl[(size_t)g * n + c];
-    out[i] = s;
-}
-
 }  // namespace
 
-struct bh_datafits_sets {
-    int n = 0, nerr = 0, nsets = 0, Gmax = 1, scanned = 0;
+struct bh_datafits_sets : bh::SetStats<blocks_of> {
+    int nerr = 0;
     long long chunk_bytes = 0;
     const double *Y = nullptr;
     const int *w = nullptr, *err = nullptr;
     long long nrows = 0, stride = 0;
-    hipStream_t st = nullptr;
-    std::vector<long long> start, goff;          // [nsets + 1]
-    std::vector<u64> total;                      // [nsets] of the scan
-    std::vector<int> status;                     // [nsets] of the scan
-    bh::DevBufs bufs;
     // device
-    long long *dstart = nullptr, *dgoff = nullptr;
-    int *wk = nullptr, *dskip = nullptr;
-    u64 *cnt = nullptr, *kmin = nullptr, *kmax = nullptr;        // [nsets][3], [nsets][n], [nsets][n]
-    double *slab = nullptr, *red = nullptr, *dmean = nullptr;    // [goff[nsets]][n], [nsets][n], [nsets][n]
-
-    int chunk_blocks(int first, int nc) const
-    {
-        int g = 1;
-        for (int z = first; z < first + nc; z++) {
-            const int gs = blocks_of(start[z + 1] - start[z]);
-            g = gs > g ? gs : g;
-        }
-        return g;
-    }
+    int *wk = nullptr;                 // [nrows]
+    u64 *cnt = nullptr;                // [nsets][3]
 };
 
 namespace {
@@ -188,28 +157,13 @@ int launch(bh_datafits_sets *p, const FitArgs &a, const SetArgs &s, int nc, size
     return BH_OK;
 }
 
-// the slab of the pass just launched, added up per set: synchronises
-int reduce_slab(bh_datafits_sets *p, std::vector<double> &out)
-{
-    const size_t cols = (size_t)p->nsets * p->n;
-    hipLaunchKernelGGL(df_sets_reduce_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st,
-                       (const double *)p->slab, (const long long *)p->dstart, (const long long *)p->dgoff, p->nsets,
-                       p->n, p->red);
-    BH_HIP(hipGetLastError());
-    out.assign(cols, 0.0);
-    BH_HIP(hipMemcpyAsync(out.data(), p->red, sizeof(double) * cols, hipMemcpyDeviceToHost, p->st));
-    BH_HIP(hipStreamSynchronize(p->st));
-    return BH_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 const char *bh_datafits_sets_status_text(int status)
 {
-    return status == BH_DATAFITS_SET_EMPTY ? bh::scan_fault(0, 0)
-           : status == BH_DATAFITS_SET_OVERFLOW ? bh::scan_fault(~0ull, 0) : "";
+    return bh::set_status_text(status);
 }
 
 int bh_datafits_sets_set_chunk_bytes(bh_datafits_sets *p, long long bytes)
@@ -231,10 +185,7 @@ int bh_datafits_sets_create(const double *Y, long long nrows, long long stride, 
     if (stride < ncols) return bh::fail_arg_("bh_datafits_sets_create: stride < ncols");
     if (err && nerr < 1) return bh::fail_arg_("bh_datafits_sets_create: err flags given with nerr < 1");
     if (nsets < 1 || nsets > kMaxGridZ) return bh::fail_arg_("bh_datafits_sets_create: 1 to 65535 sets");
-    if (!set_start || set_start[0] != 0 || set_start[nsets] != nrows)
-        return bh::fail_arg_("bh_datafits_sets_create: set_start must begin at 0 and end at nrows");
-    for (int z = 0; z < nsets; z++)
-        if (set_start[z] > set_start[z + 1]) return bh::fail_arg_("bh_datafits_sets_create: set_start must be ascending");
+    if (int rc = bh::check_set_start("bh_datafits_sets_create", set_start, nsets, nrows)) return rc;
     if ((long long)nsets * ncols > 0x3fffffff) return bh::fail_arg_("bh_datafits_sets_create: more than 2^30 (set, column) pairs");
     if (int rc = bh::require_device()) return rc;
     std::unique_ptr<bh_datafits_sets> p(new (std::nothrow) bh_datafits_sets);
@@ -248,25 +199,9 @@ int bh_datafits_sets_create(const double *Y, long long nrows, long long stride, 
     p->nerr = err ? nerr : 0;
     p->nsets = nsets;
     p->st = (hipStream_t)stream;
-    p->start.assign(set_start, set_start + nsets + 1);
-    p->goff.assign((size_t)nsets + 1, 0);
-    for (int z = 0; z < nsets; z++) p->goff[z + 1] = p->goff[z] + blocks_of(set_start[z + 1] - set_start[z]);
-    p->Gmax = p->chunk_blocks(0, nsets);
-    p->total.assign(nsets, 0);
-    p->status.assign(nsets, BH_DATAFITS_SET_EMPTY);
-    const size_t cols = (size_t)nsets * ncols;
-    BH_HIP(p->bufs.alloc(p->dstart, (size_t)nsets + 1));
-    BH_HIP(p->bufs.alloc(p->dgoff, (size_t)nsets + 1));
+    if (int rc = p->alloc_sets(set_start)) return rc;
     BH_HIP(p->bufs.alloc(p->wk, (size_t)nrows));
-    BH_HIP(p->bufs.alloc(p->dskip, nsets));
     BH_HIP(p->bufs.alloc(p->cnt, 3 * (size_t)nsets));
-    BH_HIP(p->bufs.alloc(p->kmin, cols));
-    BH_HIP(p->bufs.alloc(p->kmax, cols));
-    BH_HIP(p->bufs.alloc(p->slab, (size_t)p->goff[nsets] * ncols));
-    BH_HIP(p->bufs.alloc(p->red, cols));
-    BH_HIP(p->bufs.alloc(p->dmean, cols));
-    BH_HIP(hipMemcpyAsync(p->dstart, p->start.data(), sizeof(long long) * ((size_t)nsets + 1), hipMemcpyHostToDevice, p->st));
-    BH_HIP(hipMemcpyAsync(p->dgoff, p->goff.data(), sizeof(long long) * ((size_t)nsets + 1), hipMemcpyHostToDevice, p->st));
     BH_HIP(hipStreamSynchronize(p->st));
     *fits = p.release();
     return BH_OK;
@@ -285,13 +220,9 @@ int bh_datafits_sets_scan(bh_datafits_sets *p, long long *total, long long *excl
 {
     if (!p) return bh::fail_arg_("fits is NULL");
     if (!status) return bh::fail_arg_("bh_datafits_sets_scan: status is NULL");
-    p->scanned = 0;
     const int N = p->n, S = p->nsets;
-    const int cols = S * N;
-    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmin, cols, ~0ull);
-    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmax, cols, 0ull);
-    BH_HIP(hipGetLastError());
-    BH_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 3 * (size_t)S, p->st));
+    int rc = p->begin_scan(p->cnt, 3 * (size_t)S);
+    if (rc) return rc;
     {
         const long long blocks = (p->nrows + kThreads / 64 - 1) / (kThreads / 64);
         hipLaunchKernelGGL(df_sets_mask_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kThreads), 0, p->st,
@@ -303,40 +234,21 @@ int bh_datafits_sets_scan(bh_datafits_sets *p, long long *total, long long *excl
     a.kmin = p->kmin;
     a.kmax = p->kmax;
     SetArgs s = set_args(p);
-    int rc = launch<MODE_SCAN>(p, a, s, S, 0);
+    rc = launch<MODE_SCAN>(p, a, s, S, 0);
     if (rc) return rc;
-    std::vector<u64> cnt(3 * (size_t)S), kmn((size_t)cols), kmx((size_t)cols);
+    std::vector<u64> cnt(3 * (size_t)S);
     BH_HIP(hipMemcpyAsync(cnt.data(), p->cnt, sizeof(u64) * cnt.size(), hipMemcpyDeviceToHost, p->st));
-    BH_HIP(hipMemcpyAsync(kmn.data(), p->kmin, sizeof(u64) * kmn.size(), hipMemcpyDeviceToHost, p->st));
-    BH_HIP(hipMemcpyAsync(kmx.data(), p->kmax, sizeof(u64) * kmx.size(), hipMemcpyDeviceToHost, p->st));
     std::vector<double> sum;
-    rc = reduce_slab(p, sum);                      // synchronises the stream
+    rc = p->reduce_slab(sum);                      // synchronises the stream
     if (rc) return rc;
-    for (int z = 0; z < S; z++)
-        if (cnt[3 * (size_t)z + 2])
-            return bh::fail_arg_((std::string("bh_datafits_sets_scan: ") + bh::scan_fault(cnt[3 * (size_t)z], 1)).c_str());
-    std::vector<double> mu((size_t)cols);
-    const double nan = std::nan("");
+    std::vector<u64> included(S), negative(S);
     for (int z = 0; z < S; z++) {
-        const u64 included = cnt[3 * (size_t)z];
-        p->total[z] = included;
-        p->status[z] = included == 0 ? BH_DATAFITS_SET_EMPTY
-                       : included > (1ull << 53) ? BH_DATAFITS_SET_OVERFLOW : BH_DATAFITS_SET_OK;
-        status[z] = p->status[z];
-        const bool live = p->status[z] == BH_DATAFITS_SET_OK;
-        if (total) total[z] = (long long)included;
-        if (excluded) excluded[z] = (long long)cnt[3 * (size_t)z + 1];
-        for (int c = 0; c < N; c++) {
-            const size_t i = (size_t)z * N + c;
-            mu[i] = live ? sum[i] / (double)included : nan;
-            if (vmin) vmin[i] = live ? bh::post_unkey64(kmn[i]) : nan;
-            if (vmax) vmax[i] = live ? bh::post_unkey64(kmx[i]) : nan;
-            if (mean) mean[i] = mu[i];
-        }
+        included[z] = cnt[3 * (size_t)z];
+        negative[z] = cnt[3 * (size_t)z + 2];
     }
-    BH_HIP(hipMemcpyAsync(p->dmean, mu.data(), sizeof(double) * cols, hipMemcpyHostToDevice, p->st));
-    BH_HIP(hipStreamSynchronize(p->st));
-    p->scanned = 1;
+    rc = p->end_scan("bh_datafits_sets_scan", included, negative, sum, total, status, vmin, vmax, mean);
+    if (rc) return rc;
+    for (int z = 0; excluded && z < S; z++) excluded[z] = (long long)cnt[3 * (size_t)z + 1];
     return BH_OK;
 }
 
@@ -353,9 +265,9 @@ int bh_datafits_sets_finish(bh_datafits_sets *p, const long long *ranks, int nra
     if (!p) return bh::fail_arg_("fits is NULL");
     if (!p->scanned) return bh::fail_arg_("bh_datafits_sets_finish before a successful bh_datafits_sets_scan");
     const int N = p->n, S = p->nsets;
-    std::vector<int> skip(S);
+    std::vector<int> &skip = p->skip;
     for (int z = 0; z < S; z++) {
-        skip[z] = p->status[z] != BH_DATAFITS_SET_OK;
+        skip[z] = p->status[z] != BH_DATAFITS_SET_OK ? bh::SET_SKIP : 0;
         if (skip[z]) continue;
         for (int i = 0; i < nranks; i++) {
             const long long r = ranks[(size_t)z * nranks + i];
@@ -374,7 +286,7 @@ int bh_datafits_sets_finish(bh_datafits_sets *p, const long long *ranks, int nra
     const int nb = nedges - 1;
     const size_t cols = (size_t)S * N;
     const double nan = std::nan("");
-    BH_HIP(hipMemcpyAsync(p->dskip, skip.data(), sizeof(int) * S, hipMemcpyHostToDevice, p->st));
+    if (int rc = p->upload_skip()) return rc;
     if (stdev || want_hist) {
         FitArgs a = base_args(p);
         a.mean = p->dmean;
@@ -399,15 +311,7 @@ int bh_datafits_sets_finish(bh_datafits_sets *p, const long long *ranks, int nra
             s.nesets = nesets;
         }
         int rc = launch<MODE_FINISH>(p, a, s, S, lds);
-        if (!rc && stdev) {
-            std::vector<double> sq;
-            rc = reduce_slab(p, sq);                                 // synchronises the stream
-            for (int z = 0; !rc && z < S; z++)
-                for (int c = 0; c < N; c++) {
-                    const size_t i = (size_t)z * N + c;
-                    stdev[i] = skip[z] ? nan : std::sqrt(sq[i] / (double)p->total[z]);
-                }
-        }
+        if (!rc && stdev) rc = p->read_stdev(stdev);                 // synchronises the stream
         if (!rc && want_hist) rc = bh::read_hist(a.hist, cols * nb, hist, p->st);
         if (rc) return rc;
     }

@@ -350,10 +350,7 @@ int bh_moho_sets(const double *D, long long nrows, const int *weights, const lon
     if (!D || nrows < 1) return bh::fail_arg_("bh_moho_sets: no rows (empty selection)");
     if (nrows > (1ll << 32)) return bh::fail_arg_("bh_moho_sets: more than 2^32 rows (the weight total could overflow)");
     if (nsets < 1 || nsets > (1 << 24)) return bh::fail_arg_("bh_moho_sets: 1 to 2^24 sets");
-    if (!set_start || set_start[0] != 0 || set_start[nsets] != nrows)
-        return bh::fail_arg_("bh_moho_sets: set_start must begin at 0 and end at nrows");
-    for (int z = 0; z < nsets; z++)
-        if (set_start[z] > set_start[z + 1]) return bh::fail_arg_("bh_moho_sets: set_start must be ascending");
+    if (int rc = bh::check_set_start("bh_moho_sets", set_start, nsets, nrows)) return rc;
     const bool want_hist = edges != nullptr;
     if (want_hist && (nedges < 2 || !hist || !bh::ascending(edges, nedges)))
         return bh::fail_arg_("bh_moho_sets: edges must be ascending, two at least, with hist");

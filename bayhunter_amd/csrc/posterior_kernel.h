@@ -3,10 +3,12 @@
 // range of the rows).  Both kernels hand it the rows [r0, r1), the block's place `bx` among the `G` blocks that
 // share them, and arguments whose output pointers are the set's own; what a set's block adds up, and in which order,
 // therefore does not depend on which of the two kernels runs it.
+//
+// The part above BH_HOSTSIM's #ifndef needs no device (the launch geometry): tests/hostsim/datafits_sets_sim.cpp
+// compiles it with g++ (test infrastructure only).
 #pragma once
 #include <cstdint>
 #include "posterior_core.h"
-#include "stats_host.h"
 
 namespace bh {
 namespace post {
@@ -20,11 +22,20 @@ enum { MODE_SCAN = 1, MODE_FINISH = 2 };
 enum { F_ROWS = 1, F_SQ = 2, F_HIST = 4, F_RADIX = 8, F_HIST_GLOBAL = 16 };
 
 // blocks along the rows of a set of nrows rows
-inline __host__ __device__ int blocks_of(long long nrows)
+BH_HD int blocks_of(long long nrows)
 {
     const long long g = (nrows + kThreads - 1) / kThreads;
     return (int)(g < kMaxBlocksX ? g : kMaxBlocksX);
 }
+
+}  // namespace post
+}  // namespace bh
+
+#ifndef BH_HOSTSIM
+#include "stats_host.h"
+
+namespace bh {
+namespace post {
 
 struct PostArgs {
     const void *rows;
@@ -299,3 +310,4 @@ inline double median_of(const RadixSelect &sel, int fp64, int c)
 
 }  // namespace post
 }  // namespace bh
+#endif  // BH_HOSTSIM

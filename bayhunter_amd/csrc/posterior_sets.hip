@@ -10,10 +10,11 @@
 // of a single-set handle over its rows.
 //
 //   scan     one launch (grid: blocks of the largest set, depth tiles, sets) and one slab reduction
+//   slab     the sets' partials one after the other, set z owning G(z) rows from goff[z] (stats_host.h: SetStats)
 //   finish   per set its own Vs edges (concatenated, with offsets) and histogram; the select runs over
 //            nsets * D columns with each set's two middle ranks; one launch per radix pass for all sets
-//   chunks   the select's digit table is 2 * 256 * 8 B per column, so the sets are taken in chunks whose table
-//            stays under a budget; a set is never split, and nothing a set's blocks compute depends on the chunk
+//   chunks   the select's digit table is 2 * 256 * 8 B per column, so the finish takes the sets in chunks whose
+//            table stays under a budget; a set is never split, and nothing a set's blocks compute depends on the chunk
 #include <cstring>
 #include <memory>
 #include <new>
@@ -27,11 +28,12 @@ using namespace bh::post;
 
 constexpr long long kDigitBudget = 64ll << 20;       // bytes of digit table per chunk (bh_posterior_sets_set_chunk_bytes)
 
-enum { S_SKIP = 1, S_HIST_GLOBAL = 2 };              // per set, for the finish
+enum { S_SKIP = bh::SET_SKIP, S_HIST_GLOBAL = 2 };   // per set, for the finish
 
 struct SetArgs {
     const long long *start;            // [nsets + 1] rows of set z: start[z] .. start[z + 1]
-    int first, Gmax;                   // the chunk's first set; blocks per set in the slab and the argmin partials
+    const long long *goff;             // [nsets + 1] slab rows (and argmin partials) before set z
+    int first;                         // the launch's first set
     const int *sflags;                 // [nsets] finish: S_SKIP, S_HIST_GLOBAL
     const int *vedge_off;              // [nsets + 1] into vedges
     const u64 *hist_off;               // [nsets + 1] into hist
@@ -45,15 +47,15 @@ __global__ __launch_bounds__(kThreads) void post_sets_kernel(PostArgs a, SetArgs
     const int G = blocks_of(r1 - r0), bx = blockIdx.x;
     if (bx >= G) return;
     const size_t col = (size_t)z * a.D;
-    a.slab += (size_t)zl * s.Gmax * a.D;
+    a.slab += (size_t)s.goff[z] * a.D;
     if (MODE == MODE_SCAN) {
         a.kmin += col;
         a.kmax += col;
         a.cnt += 2 * (size_t)z;
         a.nlay += (size_t)z * (a.maxn + 1);
         if (a.nif > 1) a.ifhist += (size_t)z * (a.nif - 1);
-        a.mfkey += (size_t)z * s.Gmax;
-        a.mfrow += (size_t)z * s.Gmax;
+        a.mfkey += s.goff[z];
+        a.mfrow += s.goff[z];
     } else {
         const int f = s.sflags[z];
         if (f & S_SKIP) return;
@@ -72,48 +74,19 @@ __global__ __launch_bounds__(kThreads) void post_sets_kernel(PostArgs a, SetArgs
     post_block<T, MODE>(a, r0, r1, bx, G);
 }
 
-// Σ over a set's blocks in block order: one thread per (set of the chunk, column)
-__global__ void sets_reduce_kernel(const double *slab, const long long *start, int first, int nc, int Gmax, int D,
-                                   double *out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nc * D) return;
-    const int zl = i / D, c = i % D, z = first + zl;
-    const int G = blocks_of(start[z + 1] - start[z]);
-    double s = 0.0;
-    for (int g = 0; g < G; g++) s = s + slab[((size_t)zl * Gmax + g) * D + c];
-    out[(size_t)z * D + c] = s;
-}
-
 }  // namespace
 
-struct bh_posterior_sets {
-    int fp64 = 0, width = 0, nif = 0, maxn = 0, D = 0, nsets = 0, Gmax = 1, chunk = 1, scanned = 0;
+struct bh_posterior_sets : bh::SetStats<blocks_of> {
+    int fp64 = 0, width = 0, nif = 0, maxn = 0;          // n of SetStats: the depths
+    long long chunk_bytes = 0;
     const void *rows = nullptr;
     long long nrows = 0, stride = 0;
     const int *w = nullptr;
     const double *misfit = nullptr;
-    hipStream_t st = nullptr;
-    std::vector<long long> start;      // [nsets + 1]
-    std::vector<u64> total;            // [nsets] of the scan
-    std::vector<int> status;           // [nsets] of the scan
-    bh::DevBufs bufs;
     // device
-    long long *dstart = nullptr;
     double *dep = nullptr, *ifedges = nullptr;
-    double *slab = nullptr, *red = nullptr, *dmean = nullptr;    // [chunk][Gmax][D], [nsets][D], [nsets][D]
-    u64 *kmin = nullptr, *kmax = nullptr;                        // [nsets][D]
-    u64 *cnt = nullptr, *nlay = nullptr, *ifhist = nullptr, *mfkey = nullptr;
+    u64 *cnt = nullptr, *nlay = nullptr, *ifhist = nullptr, *mfkey = nullptr;    // [nsets][2], ..., [goff[nsets]]
     long long *mfrow = nullptr;
-    int *sflags = nullptr;
-
-    int G(int z) const { return blocks_of(start[z + 1] - start[z]); }
-    int chunk_blocks(int first, int nc) const
-    {
-        int g = 1;
-        for (int z = first; z < first + nc; z++) g = G(z) > g ? G(z) : g;
-        return g;
-    }
 };
 
 namespace {
@@ -121,7 +94,7 @@ namespace {
 template <typename T, int MODE>
 int launch(bh_posterior_sets *p, PostArgs &a, SetArgs &s, int nc, size_t lds_bytes)
 {
-    dim3 grid((unsigned)p->chunk_blocks(s.first, nc), (unsigned)((p->D + kTile - 1) / kTile), (unsigned)nc);
+    dim3 grid((unsigned)p->chunk_blocks(s.first, nc), (unsigned)((p->n + kTile - 1) / kTile), (unsigned)nc);
     hipLaunchKernelGGL((post_sets_kernel<T, MODE>), grid, dim3(kThreads), lds_bytes, p->st, a, s);
     BH_HIP(hipGetLastError());
     return BH_OK;
@@ -133,15 +106,6 @@ int run(bh_posterior_sets *p, PostArgs &a, SetArgs &s, int nc, size_t lds_bytes)
     return p->fp64 ? launch<double, MODE>(p, a, s, nc, lds_bytes) : launch<float, MODE>(p, a, s, nc, lds_bytes);
 }
 
-// the chunk's slab, added up per set into red
-int reduce_chunk(bh_posterior_sets *p, int first, int nc)
-{
-    hipLaunchKernelGGL(sets_reduce_kernel, dim3((unsigned)((nc * p->D + 255) / 256)), dim3(256), 0, p->st,
-                       (const double *)p->slab, (const long long *)p->dstart, first, nc, p->Gmax, p->D, p->red);
-    BH_HIP(hipGetLastError());
-    return BH_OK;
-}
-
 PostArgs base_args(const bh_posterior_sets *p)
 {
     PostArgs a;
@@ -150,13 +114,23 @@ PostArgs base_args(const bh_posterior_sets *p)
     a.nrows = p->nrows;
     a.stride = p->stride;
     a.width = p->width;
-    a.D = p->D;
+    a.D = p->n;
     a.w = p->w;
     a.misfit = p->misfit;
     a.dep = p->dep;
     a.slab = p->slab;
     a.maxn = p->maxn;
     return a;
+}
+
+SetArgs set_args(const bh_posterior_sets *p)
+{
+    SetArgs s;
+    std::memset(&s, 0, sizeof(s));
+    s.start = p->dstart;
+    s.goff = p->dgoff;
+    s.sflags = p->dskip;
+    return s;
 }
 
 template <typename T>
@@ -174,16 +148,13 @@ extern "C" {
 int bh_posterior_sets_set_chunk_bytes(bh_posterior_sets *p, long long bytes)
 {
     if (!p) return bh::fail_arg_("post is NULL");
-    if (p->slab) return bh::fail_arg_("bh_posterior_sets_set_chunk_bytes after bh_posterior_sets_scan");
-    const long long fit = (bytes > 0 ? bytes : kDigitBudget) / ((long long)p->D * 2 * 256 * (long long)sizeof(u64));
-    p->chunk = (int)(fit < 1 ? 1 : fit > p->nsets ? p->nsets : fit);
+    p->chunk_bytes = bytes > 0 ? bytes : 0;
     return BH_OK;
 }
 
 const char *bh_posterior_sets_status_text(int status)
 {
-    return status == BH_POSTERIOR_SET_EMPTY ? bh::scan_fault(0, 0)
-           : status == BH_POSTERIOR_SET_OVERFLOW ? bh::scan_fault(~0ull, 0) : "";
+    return bh::set_status_text(status);
 }
 
 int bh_posterior_sets_create(const void *rows, int fp64, long long nrows, long long stride, int width,
@@ -197,10 +168,7 @@ int bh_posterior_sets_create(const void *rows, int fp64, long long nrows, long l
     if (nrows > (1ll << 32)) return bh::fail_arg_("bh_posterior_sets_create: more than 2^32 rows (the weight total could overflow)");
     if (width < 2 || width > 2 * BH_MAX_LAYERS + 2 || stride < width) return bh::fail_arg_("bh_posterior_sets_create: width / stride");
     if (nsets < 1 || nsets > 65535) return bh::fail_arg_("bh_posterior_sets_create: 1 to 65535 sets");
-    if (!set_start || set_start[0] != 0 || set_start[nsets] != nrows)
-        return bh::fail_arg_("bh_posterior_sets_create: set_start must begin at 0 and end at nrows");
-    for (int z = 0; z < nsets; z++)
-        if (set_start[z] > set_start[z + 1]) return bh::fail_arg_("bh_posterior_sets_create: set_start must be ascending");
+    if (int rc = bh::check_set_start("bh_posterior_sets_create", set_start, nsets, nrows)) return rc;
     if (!dep || ndep < 1 || !bh::ascending(dep, ndep)) return bh::fail_arg_("bh_posterior_sets_create: the depth grid must be ascending");
     if ((long long)nsets * ndep > 0x3fffffff) return bh::fail_arg_("bh_posterior_sets_create: more than 2^30 (set, depth) columns");
     if (nifedges && (nifedges < 2 || !ifedges || !bh::ascending(ifedges, nifedges)))
@@ -215,29 +183,17 @@ int bh_posterior_sets_create(const void *rows, int fp64, long long nrows, long l
     p->width = width;
     p->w = weights;
     p->misfit = misfits;
-    p->D = ndep;
+    p->n = ndep;
     p->nsets = nsets;
     p->nif = nifedges;
     p->maxn = width / 2;
     p->st = (hipStream_t)stream;
-    p->start.assign(set_start, set_start + nsets + 1);
-    p->total.assign(nsets, 0);
-    p->status.assign(nsets, BH_POSTERIOR_SET_EMPTY);
-    p->Gmax = p->chunk_blocks(0, nsets);
-    (void)bh_posterior_sets_set_chunk_bytes(p.get(), 0);
-    const size_t cols = (size_t)nsets * ndep;
-    BH_HIP(p->bufs.alloc(p->dstart, (size_t)nsets + 1));
-    BH_HIP(p->bufs.alloc(p->red, cols));
-    BH_HIP(p->bufs.alloc(p->dmean, cols));
-    BH_HIP(p->bufs.alloc(p->kmin, cols));
-    BH_HIP(p->bufs.alloc(p->kmax, cols));
+    if (int rc = p->alloc_sets(set_start)) return rc;
     BH_HIP(p->bufs.alloc(p->dep, ndep));
     BH_HIP(p->bufs.alloc(p->cnt, 2 * (size_t)nsets));
     BH_HIP(p->bufs.alloc(p->nlay, (size_t)nsets * (p->maxn + 1)));
-    BH_HIP(p->bufs.alloc(p->mfkey, (size_t)nsets * p->Gmax));
-    BH_HIP(p->bufs.alloc(p->mfrow, (size_t)nsets * p->Gmax));
-    BH_HIP(p->bufs.alloc(p->sflags, nsets));
-    BH_HIP(hipMemcpyAsync(p->dstart, p->start.data(), sizeof(long long) * (nsets + 1), hipMemcpyHostToDevice, p->st));
+    BH_HIP(p->bufs.alloc(p->mfkey, (size_t)p->goff[nsets]));
+    BH_HIP(p->bufs.alloc(p->mfrow, (size_t)p->goff[nsets]));
     BH_HIP(hipMemcpyAsync(p->dep, dep, sizeof(double) * ndep, hipMemcpyHostToDevice, p->st));
     if (nifedges) {
         BH_HIP(p->bufs.alloc(p->ifedges, nifedges));
@@ -262,14 +218,9 @@ int bh_posterior_sets_scan(bh_posterior_sets *p, long long *total, double *vmin,
 {
     if (!p) return bh::fail_arg_("post is NULL");
     if (!status) return bh::fail_arg_("bh_posterior_sets_scan: status is NULL");
-    p->scanned = 0;
-    if (!p->slab) BH_HIP(p->bufs.alloc(p->slab, (size_t)p->chunk * p->Gmax * p->D));   // the chunk is settled now
-    const int D = p->D, S = p->nsets, nl1 = p->maxn + 1, nih = p->nif > 1 ? p->nif - 1 : 0;
-    const int cols = S * D;
-    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmin, cols, ~0ull);
-    hipLaunchKernelGGL(bh::stats_fill_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, p->st, p->kmax, cols, 0ull);
-    BH_HIP(hipGetLastError());
-    BH_HIP(hipMemsetAsync(p->cnt, 0, sizeof(u64) * 2 * S, p->st));
+    const int S = p->nsets, nl1 = p->maxn + 1, nih = p->nif > 1 ? p->nif - 1 : 0;
+    int rc = p->begin_scan(p->cnt, 2 * (size_t)S);
+    if (rc) return rc;
     BH_HIP(hipMemsetAsync(p->nlay, 0, sizeof(u64) * (size_t)S * nl1, p->st));
     if (nih) BH_HIP(hipMemsetAsync(p->ifhist, 0, sizeof(u64) * (size_t)S * nih, p->st));
     PostArgs a = base_args(p);
@@ -285,51 +236,26 @@ int bh_posterior_sets_scan(bh_posterior_sets *p, long long *total, double *vmin,
     a.mfrow = p->mfrow;
     a.off_nlay = 0;
     a.off_if = nl1;
-    const size_t lds = sizeof(u64) * (size_t)(nl1 + nih);
-    SetArgs s;
-    std::memset(&s, 0, sizeof(s));
-    s.start = p->dstart;
-    s.Gmax = p->Gmax;
-    for (int first = 0; first < S; first += p->chunk) {
-        const int nc = S - first < p->chunk ? S - first : p->chunk;
-        s.first = first;
-        int rc = run<MODE_SCAN>(p, a, s, nc, lds);
-        if (!rc) rc = reduce_chunk(p, first, nc);
-        if (rc) return rc;
-    }
-    std::vector<u64> cnt, nl, ih, mk, kmn, kmx;
+    SetArgs s = set_args(p);
+    rc = run<MODE_SCAN>(p, a, s, S, sizeof(u64) * (size_t)(nl1 + nih));
+    std::vector<u64> cnt, nl, ih, mk;
     std::vector<long long> mr;
     std::vector<double> sum;
-    int rc = fetch(cnt, p->cnt, 2 * (size_t)S, p->st);
+    if (!rc) rc = fetch(cnt, p->cnt, 2 * (size_t)S, p->st);
     if (!rc) rc = fetch(nl, p->nlay, (size_t)S * nl1, p->st);
     if (!rc) rc = fetch(ih, p->ifhist, (size_t)S * nih, p->st);
-    if (!rc && p->misfit) rc = fetch(mk, p->mfkey, (size_t)S * p->Gmax, p->st);
-    if (!rc && p->misfit) rc = fetch(mr, p->mfrow, (size_t)S * p->Gmax, p->st);
-    if (!rc) rc = fetch(sum, p->red, (size_t)cols, p->st);
-    if (!rc) rc = fetch(kmn, p->kmin, (size_t)cols, p->st);
-    if (!rc) rc = fetch(kmx, p->kmax, (size_t)cols, p->st);
+    if (!rc && p->misfit) rc = fetch(mk, p->mfkey, (size_t)p->goff[S], p->st);
+    if (!rc && p->misfit) rc = fetch(mr, p->mfrow, (size_t)p->goff[S], p->st);
+    if (!rc) rc = p->reduce_slab(sum);             // synchronises the stream
     if (rc) return rc;
-    BH_HIP(hipStreamSynchronize(p->st));
-    for (int z = 0; z < S; z++)
-        if (cnt[2 * z + 1])
-            return bh::fail_arg_((std::string("bh_posterior_sets_scan: ") + bh::scan_fault(cnt[2 * z], cnt[2 * z + 1])).c_str());
-    std::vector<double> mu((size_t)cols);
-    const double nan = std::nan("");
+    std::vector<u64> included(S), negative(S);
     for (int z = 0; z < S; z++) {
-        const u64 included = cnt[2 * z];
-        p->total[z] = included;
-        p->status[z] = included == 0 ? BH_POSTERIOR_SET_EMPTY
-                       : included > (1ull << 53) ? BH_POSTERIOR_SET_OVERFLOW : BH_POSTERIOR_SET_OK;
-        status[z] = p->status[z];
-        const bool live = p->status[z] == BH_POSTERIOR_SET_OK;
-        for (int c = 0; c < D; c++) {
-            const size_t i = (size_t)z * D + c;
-            mu[i] = live ? sum[i] / (double)included : nan;
-            if (vmin) vmin[i] = live ? bh::post_unkey64(kmn[i]) : nan;
-            if (vmax) vmax[i] = live ? bh::post_unkey64(kmx[i]) : nan;
-            if (mean) mean[i] = mu[i];
-        }
-        if (total) total[z] = (long long)included;
+        included[z] = cnt[2 * (size_t)z];
+        negative[z] = cnt[2 * (size_t)z + 1];
+    }
+    rc = p->end_scan("bh_posterior_sets_scan", included, negative, sum, total, status, vmin, vmax, mean);
+    if (rc) return rc;
+    for (int z = 0; z < S; z++) {
         if (nlayers)
             for (int i = 0; i < nl1; i++) nlayers[(size_t)z * nl1 + i] = (long long)nl[(size_t)z * nl1 + i];
         if (ifhist)
@@ -339,16 +265,13 @@ int bh_posterior_sets_scan(bh_posterior_sets *p, long long *total, double *vmin,
             u64 bk = 0;
             const int G = p->G(z);
             for (int g = 0; p->misfit && g < G; g++) {
-                const u64 k = mk[(size_t)z * p->Gmax + g];
-                const long long r = mr[(size_t)z * p->Gmax + g];
+                const u64 k = mk[(size_t)p->goff[z] + g];
+                const long long r = mr[(size_t)p->goff[z] + g];
                 if (r >= 0 && (best < 0 || k < bk || (k == bk && r < best))) { best = r; bk = k; }
             }
             argmin[z] = best;
         }
     }
-    BH_HIP(hipMemcpyAsync(p->dmean, mu.data(), sizeof(double) * cols, hipMemcpyHostToDevice, p->st));
-    BH_HIP(hipStreamSynchronize(p->st));
-    p->scanned = 1;
     return BH_OK;
 }
 
@@ -357,13 +280,14 @@ int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const i
 {
     if (!p) return bh::fail_arg_("post is NULL");
     if (!p->scanned) return bh::fail_arg_("bh_posterior_sets_finish before bh_posterior_sets_scan");
-    const int D = p->D, S = p->nsets;
+    const int D = p->n, S = p->nsets;
     const bool want_hist = vedges != nullptr;
     if (want_hist && (!vedge_off || vedge_off[0] != 0 || !dbin || ndbins < 1 || !hist))
         return bh::fail_arg_("bh_posterior_sets_finish: Vs edges need their offsets (from 0), depth bins and histogram");
     const int tile_fits = want_hist ? tiles_fit(dbin, D, ndbins) : 1;
     if (tile_fits < 0) return bh::fail_arg_("bh_posterior_sets_finish: depth bin out of range");
-    std::vector<int> sflags(S, 0);
+    std::vector<int> &sflags = p->skip;
+    sflags.assign(S, 0);
     std::vector<u64> hoff((size_t)S + 1, 0);
     for (int z = 0; z < S; z++) {
         bool live = p->status[z] == BH_POSTERIOR_SET_OK;
@@ -382,12 +306,8 @@ int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const i
     bh::CallBufs tmp(p->st);
     PostArgs a = base_args(p);
     a.mean = p->dmean;
-    SetArgs s;
-    std::memset(&s, 0, sizeof(s));
-    s.start = p->dstart;
-    s.Gmax = p->Gmax;
-    s.sflags = p->sflags;
-    BH_HIP(hipMemcpyAsync(p->sflags, sflags.data(), sizeof(int) * S, hipMemcpyHostToDevice, p->st));
+    SetArgs s = set_args(p);
+    if (int rc = p->upload_skip()) return rc;
     if (want_hist) {
         double *dve = nullptr;
         int *ddb = nullptr, *dvo = nullptr;
@@ -417,8 +337,11 @@ int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const i
     a.off_radix = 0;
     a.off_hist = median ? kTile * 2 * 256 : 0;
     const double nan = std::nan("");
-    for (int first = 0; first < S; first += p->chunk) {
-        const int nc = S - first < p->chunk ? S - first : p->chunk;
+    // sets per chunk: the digit table of the select is what the budget bounds
+    const long long fit = (p->chunk_bytes > 0 ? p->chunk_bytes : kDigitBudget) / ((long long)D * 2 * 256 * (long long)sizeof(u64));
+    const int chunk = (int)(fit < 1 ? 1 : fit > S ? S : fit);
+    for (int first = 0; first < S; first += chunk) {
+        const int nc = S - first < chunk ? S - first : chunk;
         s.first = first;
         int tile = 0;                  // the widest LDS histogram tile of the chunk
         for (int z = first; want_hist && z < first + nc; z++)
@@ -454,9 +377,8 @@ int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const i
             int rc = median ? sel.begin_pass(p->st) : BH_OK;
             a.shift = median ? sel.shift : 0;
             if (!rc) rc = run<MODE_FINISH>(p, a, s, nc, lds);
-            if (!rc && pass1 && stdev) rc = reduce_chunk(p, first, nc);
             if (rc) return rc;
-            a.flags &= ~(F_SQ | F_HIST | F_HIST_GLOBAL);   // later passes: digits only
+            a.flags &= ~(F_SQ | F_HIST | F_HIST_GLOBAL);   // later passes: digits only (they leave the slab alone)
             lds = sizeof(u64) * (size_t)(kTile * 2 * 256);
             if (!median) break;
             rc = sel.end_pass(p->st);
@@ -468,17 +390,8 @@ int bh_posterior_sets_finish(bh_posterior_sets *p, const double *vedges, const i
                     median[(size_t)(first + zl) * D + c] =
                         (sflags[first + zl] & S_SKIP) ? nan : median_of(sel, p->fp64, zl * D + c);
     }
-    if (stdev) {
-        std::vector<double> sq;
-        int rc = fetch(sq, p->red, (size_t)S * D, p->st);
-        if (rc) return rc;
-        BH_HIP(hipStreamSynchronize(p->st));
-        for (int z = 0; z < S; z++)
-            for (int c = 0; c < D; c++) {
-                const size_t i = (size_t)z * D + c;
-                stdev[i] = (sflags[z] & S_SKIP) ? nan : std::sqrt(sq[i] / (double)p->total[z]);
-            }
-    }
+    if (stdev)                         // every chunk's first pass has written its sets' slab rows
+        if (int rc = p->read_stdev(stdev)) return rc;
     if (want_hist && hoff[S]) return bh::read_hist(a.hist, (size_t)hoff[S], hist, p->st);
     return BH_OK;
 }

@@ -52,6 +52,20 @@ BH_HD int post_bin(const double *edges, int ne, double v)
     return lo;
 }
 
+// The slab of the segmented reductions (stats_host.h: SetStats): set z owns blocks_of(its rows) slab rows from goff[z],
+// an empty set none, and goff[nsets] rows are the slab.  -> the blocks of the largest set, 1 at least (a grid extent)
+inline int set_slab_offsets(const long long *start, int nsets, int (*blocks_of)(long long), long long *goff)
+{
+    int gmax = 1;
+    goff[0] = 0;
+    for (int z = 0; z < nsets; z++) {
+        const int g = blocks_of(start[z + 1] - start[z]);
+        goff[z + 1] = goff[z] + g;
+        gmax = g > gmax ? g : gmax;
+    }
+    return gmax;
+}
+
 // Host side of the exact weighted order statistics: an 8-bit radix select over the keys of ncols columns,
 // nranks 0-based ranks (the same in every column, or one list per column), most significant digit first.  Per
 // (rank, column) it holds the key prefix found so far and the rank left among the keys with that prefix.  A pass is

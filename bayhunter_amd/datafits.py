@@ -19,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .posterior import _Handle, _to_device, _torch_device, pool_rows
+from .posterior import SetList, _Handle, _to_device, _torch_device, check_set_start, pool_rows, raise_first_failed
 
 DEFAULT_Q = (2.5, 16, 50, 84, 97.5)
 CHUNK = 65536                     # rows per layers_from_voronoi call: bounds the packed-model temporaries
@@ -367,27 +367,20 @@ def set_ranks(q, totals):
     return rk, ranks
 
 
-class SetFits(list):
+class SetFits(SetList):
     """summarize_sets' list: entry s is summarize()'s dict of set s, or None for a set in `failed`
     ({set index: message})."""
-
-    def __init__(self, results, failed):
-        list.__init__(self, results)
-        self.failed = failed
 
 
 def _summarize_sets(stations, models, set_start, vpvs, weights, misfits, mantle, q, nbins, device, rf_p, max_rows,
                     pick=None, chunk_bytes=None, backend=None):
     stations = list(stations)
-    set_start = np.ascontiguousarray(set_start, dtype=np.int64)
-    S = set_start.size - 1
     if not hasattr(models, 'shape') or not hasattr(models, 'dtype'):
         models = np.asarray(models)
     if models.ndim != 2:
         raise ValueError("models: [rows, 2*maxlayers]")
     R = models.shape[0]
-    if set_start.ndim != 1 or S < 1 or set_start[0] != 0 or set_start[-1] != R or np.any(np.diff(set_start) < 0):
-        raise ValueError("set_start: [sets + 1], ascending from 0 to the number of rows")
+    set_start, S = check_set_start(set_start, R)
     if len(stations) != S:
         raise ValueError("one JointTarget per set")
     if int(nbins) < 1:
@@ -522,9 +515,7 @@ def stations_datafits(spool, selection='weighted', dev=0.05, exclude_outliers=Tr
                           w.astype(np.int32), mis, pool.priors.get('mantle'), q, nbins, device, rf_p, max_rows,
                           pick=pick, backend=backend)
     res.failed.update(failed)
-    if res.failed and strict:
-        z = min(res.failed)
-        raise ValueError("station %r: %s" % (spool.names[z], res.failed[z]))
+    raise_first_failed(res.failed, strict, "station", spool.names)
     for z, r in enumerate(res):
         if r is None:
             continue

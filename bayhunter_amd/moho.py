@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .datafits import _Fits
-from .posterior import _to_device, _torch_device, pool_rows, station_rows
+from .posterior import _to_device, _torch_device, check_set_start, pool_rows, station_rows
 
 NAMES = ('moho', 'vs_crust', 'vs_last', 'vs_jump')          # the columns of the derived matrix
 TRADEOFF = ('vs_last', 'vs_crust', 'vs_jump')               # x axes of the joint histograms, in the reference's order
@@ -130,13 +130,9 @@ def summarize_sets(models, set_start, weights=None, moho=(0., 100.), mohovs=4.2,
     import torch
     dev = _torch_device(device)
     zlo, zhi, mohovs, nbins = _window(moho, mohovs, nbins)
-    set_start = np.ascontiguousarray(set_start, dtype=np.int64)
-    S = set_start.size - 1
     if not isinstance(models, torch.Tensor):
         models = np.asarray(models)
-    nrows = models.shape[0] if models.ndim == 2 else -1
-    if set_start.ndim != 1 or S < 1 or set_start[0] != 0 or set_start[-1] != nrows or np.any(np.diff(set_start) < 0):
-        raise ValueError("set_start: [sets + 1], ascending from 0 to the number of rows")
+    set_start, S = check_set_start(set_start, models.shape[0] if models.ndim == 2 else -1)
     rows, w = _rows_weights(models, weights, dev)
     edges = np.linspace(zlo, zhi, nbins + 1)
     cnt, nex = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64)

@@ -239,6 +239,30 @@ def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, dev
 
 # ---- many sets of rows in one pass ------------------------------------------------------------------------
 
+def check_set_start(set_start, nrows):
+    """-> (set_start as contiguous int64 [sets + 1], sets); ValueError unless it ascends from 0 to nrows."""
+    set_start = np.ascontiguousarray(set_start, dtype=np.int64)
+    S = set_start.size - 1
+    if set_start.ndim != 1 or S < 1 or set_start[0] != 0 or set_start[-1] != nrows or np.any(np.diff(set_start) < 0):
+        raise ValueError("set_start: [sets + 1], ascending from 0 to the number of rows")
+    return set_start, S
+
+
+def raise_first_failed(failed, strict, what, names=None):
+    """strict: the first set (station, with `names`) of `failed` {index: message} is a ValueError."""
+    if failed and strict:
+        z = min(failed)
+        raise ValueError(("%s %r: %s" if names else "%s %d: %s") % (what, names[z] if names else z, failed[z]))
+
+
+class SetList(list):
+    """A per-set result list: entry s is the dict of set s, or None for a set in `failed` ({set index: message})."""
+
+    def __init__(self, results, failed):
+        list.__init__(self, results)
+        self.failed = failed
+
+
 class _Sets(_Handle):
     """One bh_posterior_sets handle: the rows, in contiguous sets, on one depth grid."""
 
@@ -289,13 +313,13 @@ class _Sets(_Handle):
         return hists, std, median
 
 
-class SetResults(list):
+class SetResults(SetList):
     """summarize_sets' list: entry s is summarize()'s dict of set s, or None for a set in `failed`
     ({set index: message}).  `std[s]` is the set's standard deviation per depth (summarize reports mean -+ std)."""
 
     def __init__(self, results, failed, dep_int, std):
-        list.__init__(self, results)
-        self.failed, self.dep, self.std = failed, dep_int, std
+        SetList.__init__(self, results, failed)
+        self.dep, self.std = dep_int, std
 
     def section(self):
         """The single models stacked: dict(dep [D], mean / median / std / vmin / vmax [sets, D], mode [sets, D - 1]),
@@ -333,10 +357,7 @@ def summarize_sets(models, set_start, weights=None, dep_int=None, misfits=None, 
         models = np.asarray(models)
     if models.ndim != 2:
         raise ValueError("models: [rows, 2*maxlayers]")
-    set_start = np.ascontiguousarray(set_start, dtype=np.int64)
-    S = set_start.size - 1
-    if set_start.ndim != 1 or S < 1 or set_start[0] != 0 or set_start[-1] != models.shape[0] or np.any(np.diff(set_start) < 0):
-        raise ValueError("set_start: [sets + 1], ascending from 0 to the number of rows")
+    set_start, S = check_set_start(set_start, models.shape[0])
     fdtype = torch.float32 if str(models.dtype).endswith('float32') else torch.float64
     rows = _to_device(models, fdtype, dev)
     w = None if weights is None else _to_device(weights, torch.int32, dev)
@@ -374,9 +395,7 @@ def summarize_sets(models, set_start, weights=None, dep_int=None, misfits=None, 
             sz['total'] = int(s['total'][z])
             results[z] = _result(sz, dep_int, vedges[z], mhist[z], std[z], median[z], h2[z], vsb[z], depbins,
                                  None if best is None else best[i])
-    if failed and strict:
-        z = min(failed)
-        raise ValueError("set %d: %s" % (z, failed[z]))
+    raise_first_failed(failed, strict, "set")
     return SetResults(results, failed, dep_int, std)
 
 
@@ -537,9 +556,7 @@ def stations_posterior(spool, dep_int=None, depint=1, dev=0.05, exclude_outliers
         dep_int = models2d_dep_int(pool.priors['z'], depint)
     res = summarize_sets(pool.models[ci, ri], set_start, w.astype(np.int32), dep_int=dep_int, device=device, strict=False)
     res.failed.update(failed)
-    if res.failed and strict:
-        z = min(res.failed)
-        raise ValueError("station %r: %s" % (spool.names[z], res.failed[z]))
+    raise_first_failed(res.failed, strict, "station", spool.names)
     for z, r in enumerate(res):
         if r is not None:
             r['chains'] = np.unique(ci[set_start[z]:set_start[z + 1]]) - z * c

@@ -624,10 +624,10 @@ void bh_posterior_destroy(bh_posterior *post);
  *                              out like a failed one), dbin [ndep] and ndbins as for bh_posterior_finish, and hist
  *                              the sets' histograms one after the other, set s owning ndbins * (edges of s - 1)
  *                              counters.  std and median [nsets][ndep] when not NULL; NaN for a set left out
- *   bh_posterior_sets_set_chunk_bytes   the sets of a handle are processed in chunks (one after the other on the
+ *   bh_posterior_sets_set_chunk_bytes   the finish takes the sets of a handle in chunks (one after the other on the
  *                              handle's stream, a set never split) so that the radix select's digit table of a chunk,
  *                              2 * 256 * 8 B per (set, depth), stays under 64 MiB.  This sets the handle's own bound
- *                              (<= 0: the default), before its first scan.  No result depends on it
+ *                              (<= 0: the default) for the finishes that follow.  No result depends on it
  * Every output is a HOST buffer; each call returns when its results are there. */
 #define BH_POSTERIOR_SET_OK       0
 #define BH_POSTERIOR_SET_EMPTY    1   /* no included row with a positive weight */

@@ -115,13 +115,16 @@ def dfsim():
     d = os.path.join(ROOT, 'tests', 'hostsim')
     so = os.path.join(d, 'libdatafits_sets_sim.so')
     srcs = [os.path.join(d, 'datafits_sets_sim.cpp')] + [os.path.join(ROOT, 'bayhunter_amd', 'csrc', h)
-                                                         for h in ('datafits_kernel.h', 'stats_core.h', 'bh_common.h')]
+                                                         for h in ('datafits_kernel.h', 'posterior_kernel.h',
+                                                                   'posterior_core.h', 'stats_core.h', 'bh_common.h')]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.run(['g++', '-O2', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=off', '-o', so, srcs[0]], check=True)
     sim = C.CDLL(so)
     sim.dfs_blocks_of.argtypes = [C.c_longlong]
     sim.dfs_sets_per_chunk.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong]
     sim.dfs_chunks.argtypes = [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p]
+    sim.pos_blocks_of.argtypes = [C.c_longlong]
+    sim.sets_slab_offsets.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     return sim
 
 
@@ -129,6 +132,27 @@ def test_blocks_of_a_set_are_those_of_a_single_handle(dfsim):
     for rows, blocks in ((0, 0), (1, 1), (31, 1), (32, 1), (33, 2), (64, 2), (65, 3), (32 * 1024, 1024),
                          (32 * 1024 + 5, 1024), (1 << 32, 1024)):
         assert dfsim.dfs_blocks_of(rows) == blocks, rows
+
+
+@pytest.mark.parametrize('posterior', [0, 1])
+def test_slab_offsets_give_every_set_the_blocks_of_a_single_handle(dfsim, posterior):
+    """The compact slab of the segmented reductions (SetStats::alloc_sets): set z owns goff[z] .. goff[z + 1], as many
+    rows as the file's own blocks_of gives a handle over the set's rows -- row counts around both files' rows per block
+    (32 and 256) and caps (1024 blocks) -- an empty set none, and goff[nsets] rows are the slab."""
+    blocks_of = dfsim.pos_blocks_of if posterior else dfsim.dfs_blocks_of
+    per_block = 256 if posterior else 32
+    rows = np.array([0, 1, 31, 32, 33, 255, 256, 257, 0, 32 * 1024 + 5, 256 * 1024 + 1, 0], dtype=np.int64)
+    start = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+    goff = np.full(rows.size + 1, -1, dtype=np.int64)
+    gmax = dfsim.sets_slab_offsets(posterior, start.ctypes.data, rows.size, goff.ctypes.data)
+    want = np.minimum(-(-rows // per_block), 1024)                     # ceil(rows / rows per block), capped
+    assert [blocks_of(int(r)) for r in rows] == want.tolist()
+    assert goff[0] == 0 and np.array_equal(np.diff(goff), want)
+    assert np.all(np.diff(goff)[rows == 0] == 0)                       # an empty set owns no slab row
+    assert goff[-1] == want.sum() and gmax == want.max() == 1024
+    # sets that are all empty still launch one block column
+    assert dfsim.sets_slab_offsets(posterior, np.zeros(4, dtype=np.int64).ctypes.data, 3, goff.ctypes.data) == 1
+    assert goff[:4].tolist() == [0, 0, 0, 0]
 
 
 @pytest.mark.parametrize('nsets,ncols,nranks,budget', [(7, 17, 12, 2 * 17 * 12 * 2048 + 1), (7, 17, 12, 1), (7, 17, 12, 0),
@@ -409,8 +433,9 @@ PARENT_VGPR = {'df_kernelILi1E': 28, 'df_kernelILi2E': 26, 'df_kernelILi3E': 26,
 def test_sets_kernels_use_no_scratch_and_df_kernel_did_not_grow():
     from kernel_resources import kernel_resources
     sets = kernel_resources('datafits_sets.hip')
-    mine = {k: v for k, v in sets.items() if 'df_sets_' in k}
-    assert len(mine) == 5, sorted(sets)                              # mask, reduce and the three modes
+    mine = {k: v for k, v in sets.items() if 'df_sets_' in k or 'stats_sets_reduce_kernel' in k}
+    assert len(mine) == 5, sorted(sets)                              # mask, the shared reduce and the three modes
+    assert len([k for k in mine if 'df_sets_' in k]) == 4, sorted(mine)
     for name, row in mine.items():
         assert row['scratch'] == 0, (name, row)
     single = kernel_resources('datafits.hip')

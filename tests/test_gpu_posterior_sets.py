@@ -237,6 +237,47 @@ def test_failed_sets_between_live_ones(lib):
         summarize_sets(rows, start, w, dep_int=DEP, misfits=mis, strict=False)
 
 
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_compact_slab_with_empty_sets_between_multi_block_ones(lib, dtype):
+    """Sets of 0, 1, 257, 0, 513 and 256 rows (G = 0, 1, 2, 0, 3, 1 slab rows, one after the other) in chunks of two
+    sets on the depth grid: a chunk boundary between sets of different G, an empty set opening a chunk, an empty set
+    between multi-block ones inside the slab.  The live sets equal summarize() of their rows, the empty ones fail with
+    the scan's words, and the 513-row set's argmin -- planted in its second block -- comes back as that row."""
+    import torch
+    from bayhunter_amd.posterior import _Sets, summarize_sets
+    rs = np.random.RandomState(80)
+    sizes = (0, 1, 257, 0, 513, 256)
+    start = np.concatenate(([0], np.cumsum(sizes)))
+    R = int(start[-1])
+    rows = random_rows(rs, R, width=16)
+    rows[0] = np.nan                                                  # the set of one row: three layers
+    rows[0, :3], rows[0, 3:6] = (2.0, 3.0, 4.0), (5.0, 20.0, 40.0)
+    rows = rows.astype(dtype)
+    w = rs.randint(1, 301, R).astype(np.int32)
+    mis = np.round(rs.uniform(1, 2, R), 2)
+    planted = int(start[4]) + 256
+    mis[planted] = 0.5
+    budget = 500000
+    assert budget // (DEP.size * 2 * 256 * 8) == 2
+    got = summarize_sets(rows, start, w, dep_int=DEP, misfits=mis, strict=False, chunk_bytes=budget)
+    assert len(got) == 6 and sorted(got.failed) == [0, 3] and got[0] is None and got[3] is None
+    for z in (0, 3):
+        assert got.failed[z] == 'empty selection (no included row with a positive weight)'
+    live = (1, 2, 4, 5)
+    want = singles(rows, start, w, mis, only=live)
+    assert len(want) == 4
+    for z in live:
+        assert set(got[z]) == FIELDS and set(got[z]['singlemodels']) == SINGLE
+        assert_equal_trees(got[z], want[z], 'set %d' % z)
+    dev = torch.device('cuda')
+    with _Sets(torch.from_numpy(rows).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(mis).to(dev), start, DEP,
+               None, torch.cuda.current_stream().cuda_stream, chunk_bytes=budget) as sets:
+        s = sets.scan()
+    assert s['status'].tolist() == [1, 0, 0, 1, 0, 0] and s['argmin'][4] == planted
+    assert s['argmin'][0] == -1 and s['argmin'][3] == -1 and s['argmin'][1] == 0
+    assert np.array_equal(s['total'], [w[start[z]:start[z + 1]].sum() for z in range(6)])
+
+
 def test_station_pool_posterior_equals_every_station_views(lib):
     from bayhunter_amd.posterior import summarize_sets
     from bayhunter_amd.stations import StationPool
