@@ -1,21 +1,13 @@
-// capi.hip -- the C ABI of libbayhunter_amd.so (include/bayhunter_amd.h): errors and the device, the work-queue slot
-// ring, the form planner, the dispersion entry points, the self-tests and the plumbing.  The receiver-function entry
-// points are in rf_capi.hip, the likelihood's in like_capi.hip.  Host code only.
+// capi.hip -- the C ABI of libbayhunter_amd.so (include/bayhunter_amd.h): errors and the device check, the per-thread
+// scratch, the order keys and the Voronoi kernel, the single-model dispersion drop-ins, the self-tests and the plumbing
+// (malloc, memcpy, streams).  The dispersion launch path is in swd_launch.hip, the receiver-function entry points in
+// rf_capi.hip, the likelihood's in like_capi.hip.  Host code only.
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <cmath>
 #include <cstdio>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 #include "host_common.h"
 #include "kernels.h"
-#include "swd_form_table.h"
 #include "math_probe.h"
 
 using bh::fail_arg_;
@@ -25,11 +17,12 @@ namespace {
 thread_local std::string g_err;
 }
 
-int bh::fail_arg_(const char *what)
+int bh::fail_(int code, const char *what)
 {
     g_err = what;
-    return BH_ERR_ARG;
+    return code;
 }
+int bh::fail_arg_(const char *what) { return fail_(BH_ERR_ARG, what); }
 int bh::fail_hip_(int e, const char *what)
 {
     g_err = std::string(what) + ": " + hipGetErrorString((hipError_t)e);
@@ -44,10 +37,7 @@ int bh::require_device()
     if (ok) return BH_OK;
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        g_err = "no usable HIP device (libbayhunter_amd has no CPU fallback)";
-        return BH_ERR_NO_DEVICE;
-    }
+    if (e != hipSuccess || n <= 0) return fail_(BH_ERR_NO_DEVICE, "no usable HIP device (libbayhunter_amd has no CPU fallback)");
     ok = 1;
     return BH_OK;
 }
@@ -65,352 +55,6 @@ int bh::Scratch::ensure(size_t bytes)
     n = bytes;
     return BH_OK;
 }
-
-namespace {
-
-// Work-queue heads for the dispersion kernels: a ring of slots per device so that launches in flight
-// on different streams never share a counter; each launch zeroes its slot on its own stream.  A slot
-// is handed out again only when the launch that used it last has finished: every slot carries an
-// event recorded behind its launch (release_queue_slot), and a slot whose event is still pending is
-// waited for -- with more launches in flight than slots the caller blocks instead of two kernels
-// sharing (and corrupting) one counter.  BH_SWD_QUEUE_SLOTS shrinks the ring (test hook).
-constexpr int kQueueSlots = 256;
-constexpr int kAuxStreams = 2;       // + the caller's stream: at most three kernel forms per call
-struct QueueSlot {
-    // `done` is recorded behind the slot's launch.  A call whose targets go to different kernel forms launches them
-    // on the caller's stream and on DevState::aux; its fork/join events belong to the slot, like `done`.
-    hipEvent_t done, fork, join[kAuxStreams];
-    // The stream `done` / `fork` were last recorded on.  A HIP event keeps a pointer to that stream and
-    // hipEventQuery / hipEventSynchronize / hipStreamWaitEvent look at its capture state: an event must not
-    // outlive the stream it was recorded on.  The caller's stream is the caller's to destroy, so the owner of a
-    // stream retires it first (bh_stream_retire: evaluation plans do, evalplan.hip plan_free) and the slot's
-    // events are destroyed with it.  (Round 3 did not: a plan's streams died under recorded slot events, and a
-    // later launch that claimed such a slot queried freed memory -- "operation not permitted when stream is
-    // capturing" in the driver's bench run)
-    hipStream_t done_stream, fork_stream;
-    bool used, forked;                // `done` / `fork` and `join` exist
-    bool claimed;                     // taken by a host thread that has not recorded its event yet
-};
-struct DevState {
-    unsigned int *queue = nullptr;
-    unsigned long next = 0;
-    int cus = 0, nslots = kQueueSlots;
-    unsigned long waits = 0;          // how often a launch had to wait for its slot (diagnostic)
-    hipStream_t aux[kAuxStreams] = {nullptr, nullptr};    // shared by all calls on the device
-    QueueSlot slot[kQueueSlots] = {};
-};
-std::mutex g_dev_mutex;
-std::map<int, DevState> g_dev;
-
-int get_queue_slot(unsigned int **slot, int *slot_index, int *resident_waves)
-{
-    int dev = 0;
-    BH_HIP(hipGetDevice(&dev));
-    std::unique_lock<std::mutex> lock(g_dev_mutex);
-    DevState &d = g_dev[dev];
-    if (!d.queue) {
-        BH_HIP(hipMalloc((void **)&d.queue, (size_t)kQueueSlots * bh::BH_NT * sizeof(unsigned int)));
-        hipDeviceProp_t prop;
-        BH_HIP(hipGetDeviceProperties(&prop, dev));
-        d.cus = prop.multiProcessorCount;
-        if (const char *e = std::getenv("BH_SWD_QUEUE_SLOTS")) {
-            int v = std::atoi(e);
-            if (v >= 1 && v <= kQueueSlots) d.nslots = v;
-        }
-    }
-    int i = (int)(d.next++ % (unsigned long)d.nslots);
-    for (int tries = 0; d.slot[i].claimed; tries++) {  // another thread is between get and release
-        if (tries >= d.nslots) {
-            g_err = "all work-queue slots are claimed by concurrent launches";
-            return BH_ERR_WORKSPACE;
-        }
-        i = (int)(d.next++ % (unsigned long)d.nslots);
-    }
-    QueueSlot &s = d.slot[i];
-    s.claimed = true;
-    if (s.used) {
-        hipError_t q = hipEventQuery(s.done);
-        if (q == hipErrorNotReady) {
-            d.waits++;
-            hipEvent_t ev = s.done;
-            // the ring is full of launches in flight: wait for the oldest one.  Slot i stays ours
-            // (next has moved on), so the mutex need not be held while waiting.
-            lock.unlock();
-            hipError_t we = hipEventSynchronize(ev);
-            lock.lock();
-            if (we != hipSuccess) { s.claimed = false; return fail_hip_((int)we, "hipEventSynchronize(queue slot)"); }
-        } else if (q != hipSuccess) {
-            s.claimed = false;
-            return fail_hip_((int)q, "hipEventQuery(queue slot)");
-        }
-    } else {
-        hipError_t ce = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
-        if (ce != hipSuccess) { s.claimed = false; return fail_hip_((int)ce, "hipEventCreate(queue slot)"); }
-        s.used = true;
-    }
-    *slot = d.queue + (size_t)i * bh::BH_NT;
-    *slot_index = i;
-    *resident_waves = d.cus * 8;   // 2 waves/SIMD x 4 SIMDs (VGPR-limited, kernels.hip)
-    static const char *e = std::getenv("BH_SWD_RESIDENT_WAVES");   // test hook: forces the queue path
-    if (e && std::atoi(e) > 0) *resident_waves = std::atoi(e);
-    return BH_OK;
-}
-
-// marks the end of the launch that used slot `i` on `stream`
-int release_queue_slot(int i, hipStream_t stream)
-{
-    int dev = 0;
-    BH_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_dev_mutex);
-    QueueSlot &s = g_dev[dev].slot[i];
-    hipError_t e = hipEventRecord(s.done, stream);
-    s.done_stream = stream;
-    s.claimed = false;
-    if (e != hipSuccess) return fail_hip_((int)e, "hipEventRecord(queue slot)");
-    return BH_OK;
-}
-
-// streams and events for a call that launches `naux` kernels beside the one on the caller's stream (slot `i` is
-// claimed by the calling thread)
-struct SlotStreams {
-    hipStream_t aux[kAuxStreams];
-    hipEvent_t fork, join[kAuxStreams];
-};
-int get_slot_streams(int i, int naux, SlotStreams *out)
-{
-    int dev = 0;
-    BH_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_dev_mutex);
-    DevState &d = g_dev[dev];
-    QueueSlot &s = d.slot[i];
-    if (naux > kAuxStreams) return fail_arg_("too many concurrent kernel forms");
-    for (int k = 0; k < naux; k++)
-        if (!d.aux[k]) BH_HIP(hipStreamCreateWithFlags(&d.aux[k], hipStreamNonBlocking));
-    if (!s.forked) {
-        BH_HIP(hipEventCreateWithFlags(&s.fork, hipEventDisableTiming));
-        for (int k = 0; k < kAuxStreams; k++) BH_HIP(hipEventCreateWithFlags(&s.join[k], hipEventDisableTiming));
-        s.forked = true;
-    }
-    out->fork = s.fork;
-    for (int k = 0; k < kAuxStreams; k++) { out->aux[k] = d.aux[k]; out->join[k] = s.join[k]; }
-    return BH_OK;
-}
-
-// the fork event of slot `i` (claimed by the calling thread) was recorded on `stream`
-void note_fork_stream(int i, hipStream_t stream)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lock(g_dev_mutex);
-    g_dev[dev].slot[i].fork_stream = stream;
-}
-
-// Everything the library has recorded on `stream` is finished and forgotten: the caller may destroy it.
-int retire_stream(hipStream_t stream)
-{
-    if (!stream) return BH_OK;                       // the null stream is never destroyed
-    BH_HIP(hipStreamSynchronize(stream));
-    std::unique_lock<std::mutex> lock(g_dev_mutex);
-    hipError_t first = hipSuccess;
-    auto note = [&](hipError_t e) { if (e != hipSuccess && first == hipSuccess) first = e; };
-    for (auto &kv : g_dev) {
-        DevState &d = kv.second;
-        if (!d.queue) continue;
-        for (int i = 0; i < kQueueSlots; i++) {
-            QueueSlot &s = d.slot[i];
-            // A slot another thread holds for a launch on ITS stream may still carry this stream's event (that
-            // thread may even be waiting for it -- it completed with the synchronisation above): wait until the
-            // slot is released, by then its event has been recorded anew on the other stream.
-            while (s.claimed && ((s.used && s.done_stream == stream) || (s.forked && s.fork_stream == stream))) {
-                lock.unlock();
-                std::this_thread::yield();
-                lock.lock();
-            }
-            if (s.claimed) continue;
-            if (s.used && s.done_stream == stream) {
-                note(hipEventDestroy(s.done));
-                s.used = false;
-                s.done_stream = nullptr;
-            }
-            if (s.forked && s.fork_stream == stream) {
-                // the join events were recorded on the library's own streams, which live as long as the
-                // process; they go with the fork event only to keep the slot's three events one unit
-                note(hipEventDestroy(s.fork));
-                for (int k = 0; k < kAuxStreams; k++) note(hipEventDestroy(s.join[k]));
-                s.forked = false;
-                s.fork_stream = nullptr;
-            }
-        }
-    }
-    if (first != hipSuccess) return fail_hip_((int)first, "hipEventDestroy(retired stream)");
-    return BH_OK;
-}
-
-// kernel choice of bh_swd_batch: process-wide default (bh_swd_set_kernel), read once per call
-std::atomic<int> g_swd_mode{BH_SWD_AUTO};
-thread_local int g_last_form = -1;                 // what the last bh_swd_batch of this thread launched (bh_swd_last_form)
-thread_local int g_last_forms[bh::BH_NT] = {0};   // per target (bh_swd_last_forms)
-thread_local int g_forced_forms[bh::BH_NT] = {0};
-// what the caller knows about its next batch and the planner cannot see in device memory (bh_swd_hint): the mean
-// layer count of the models (0: unknown) and how many such calls are in flight together (>= 1)
-struct Hint { double mean = 0.0; int load = 1; };
-thread_local Hint g_hint;
-thread_local int g_nforced = 0;                    // > 0: bh_swd_set_forms is in force for calls with that many targets
-
-Hint take_hint()                                   // reads and clears it: a hint is about ONE call, whatever becomes of it
-{
-    const Hint h = g_hint;
-    g_hint = Hint();
-    return h;
-}
-
-long team_threshold()
-{
-    static const char *e = std::getenv("BH_SWD_TEAM_MAX");
-    return e ? std::atol(e) : 0;       // 0: eight searches per resident wave
-}
-
-// Work of one search of a target relative to the table's unit (Rayleigh phase velocity at 21 periods): group
-// velocities solve each period twice (x1.66 period-equation evaluations, bench.py N_DLTAR), a Love layer step
-// costs 0.56 of a Rayleigh one (tools/target_forms.py), mode m runs m root searches per period.
-double target_weight(const bh_swd_target &s)
-{
-    return (s.nper / 21.0) * (s.igr ? 1.66 : 1.0) * (s.iwave == 1 ? 0.56 : 1.0) * (double)s.mode;
-}
-
-// Which kernel form runs each target of a call (width[t]: 0 = lane kernel, else lanes per search).
-// swd_form_table.h holds the measured milliseconds per call of every form by depth regime and number of
-// searches (tools/team_sweep.py on MI355X, 256 CUs, one Rayleigh phase target at 21 periods;
-// profiles/r03_team_widths.txt); the planner interpolates in log(searches), scaled to the CU count, and takes
-// the fastest.  Wide teams (64 W lanes, speculation across root searches) win up to a few thousand searches,
-// the 64-lane teams up to ~20 000, the lane kernel beyond.  bh_swd_set_kernel / bh_swd_set_forms override;
-// BH_SWD_TEAM_MAX (searches) caps the use of team kernels.
-//
-// Several targets: first the one form that is best for all of them (as above, with B x ntargets searches).  One
-// refinement, where it was measured to pay: the call is latency-bound on the lane kernel -- a few thousand models,
-// every search has a SIMD to itself and the call takes as long as its heaviest target (four targets x 8192
-// ten-layer models, 40 periods: 22.7 ms, the Rayleigh group velocities) -- and the batch is small enough for a team
-// kernel to take that target beside the others (B <= 32 searches per CU, at most 20 layers).  The heaviest target
-// then runs on a team kernel on a second stream if the estimate max(max_t lat w_t, sum_t B w_t / rate) drops by
-// 10 % or more (same example: 17.0 ms).  Nothing else is moved: with more models the teams share SIMDs and lose
-// more than the lane kernel gains, and moves between team forms measured worse throughout (tools/auto_forms.py,
-// tools/forced_forms.py, profiles/r03_mixed_forms.txt).  BH_SWD_NO_MIXED=1 keeps one form per call (A/B).
-// Depth.  The table is measured on batches of one depth.  A sampler's batch is ragged -- proposals of a tutorial
-// pool have 2 to 14 layers, 4.8 on average -- and taking the regime of its DEEPEST model prices every search as
-// deep as that one: the planner put pools of 8 192 and 16 384 chains on 128-lane teams where 64-lane teams are 35 %
-// faster (profiles/r04_pool_forms.txt).  With the mean layer count known (bh_swd_hint; the evaluation plan and the
-// engine know it from the host's copy of nlay) a form costs max(its latency on the deepest model, its time for all
-// searches at the mean depth): the deep minority is started first (processing order) and bounds the call from
-// below, the rest is throughput.  `load` calls in flight together (the chain groups of a pool alternate on the
-// device) share the chip: the throughput term is read at load x searches.
-void plan_forms(int B, int Lmax, int ntargets, const bh_swd_target *targets, long cus, int swd_mode, int *width,
-                double mean_layers = 0.0, int load = 1)
-{
-    if (g_nforced == ntargets) {                       // bh_swd_set_forms (tests, experiments)
-        for (int t = 0; t < ntargets; t++) width[t] = g_forced_forms[t];
-        return;
-    }
-    if (swd_mode != BH_SWD_AUTO) {
-        int w = 64;
-        for (int k = 0; k < bh::kSwdForms; k++)
-            if (bh::swd_forms()[k].mode == swd_mode) w = bh::kFormWidth[k];
-        for (int t = 0; t < ntargets; t++) width[t] = w;
-        return;
-    }
-    auto regime_of = [](double L) { return L <= 3 ? 0 : L <= 6 ? 1 : L <= 12 ? 2 : L <= 20 ? 3 : 4; };
-    const int regime = regime_of((double)Lmax);
-    const int regime_thr = (mean_layers > 0.0 && mean_layers < (double)Lmax) ? regime_of(mean_layers) : regime;
-    if (load < 1) load = 1;
-    const long searches = (long)B * ntargets;
-    // (calls of fewer than ~3 000 searches do not feel the other group's: with the load priced in, pools of 512 and
-    // 1 024 chains -- 2 000-2 300 proposals a call -- were put on 32-lane teams where the one-wave team is 10 % faster,
-    // a 1 024-chain inversion 6.1 instead of 5.4 s; from 2 048 chains on -- 3 500 proposals a call -- pricing it is
-    // worth 2-20 %: profiles/r04_plan_load.txt)
-    if (searches < 3000) load = 1;
-    const double scale = 256.0 / (double)cus;                  // the table's chip has 256 CUs
-    auto allowed = [&](int k) {
-        if (bh::kFormWidth[k] == 0) return true;
-        if (team_threshold() > 0 && searches > team_threshold()) return false;
-        return bh::swd_team_lds_bytes(Lmax, bh::kFormWidth[k]) <= bh::kLdsLimit;
-    };
-    // measured range of a form's row t of the table, form k's time for s searches at the depths of regime rg (1e300:
-    // beyond what a wide team was measured for)
-    auto measured = [](const float *t) {
-        int n = bh::kFormSizes;
-        while (n > 1 && t[n - 1] < 0) n--;
-        return n;
-    };
-    auto form_ms = [&](int rg, int k, double s) {
-        const float *t = bh::kFormMs[rg][k], *S = bh::kFormSearches;
-        const int n = measured(t);
-        if (s <= S[0]) return (double)t[0];
-        if (s > S[n - 1]) return n < bh::kFormSizes ? 1e300 : (double)t[n - 1] * s / S[n - 1];
-        if (s == S[n - 1]) return (double)t[n - 1];
-        int i = 0;
-        while (S[i + 1] <= s) i++;
-        const double f = (std::log(s) - std::log(S[i])) / (std::log(S[i + 1]) - std::log(S[i]));
-        return t[i] + f * (t[i + 1] - t[i]);
-    };
-    // Targets that are not the table's (one Rayleigh phase velocity at 21 periods): the call's work is that of
-    // B x sum of the target weights such searches, and it cannot be shorter than the form's latency for the heaviest
-    // target (x 0.7: a search of weight w is w times the evaluations, not w times the rounds).  Four targets x 40
-    // periods on ten layers, 2 048 / 4 096 / 8 192 / 16 384 models: this picks 16- / 16- / 8-lane teams / the lane
-    // kernel -- measured best of the uniform plans: 16 / 8 (16: +17 %) / 8 / lane (profiles/r04_mixed_tpl.txt).
-    double wsum = 0.0, wmax = 0.0;
-    for (int t = 0; t < ntargets; t++) {
-        const double w = target_weight(targets[t]);
-        wsum += w;
-        wmax = std::fmax(wmax, w);
-    }
-    const double eff = (double)B * wsum * scale;
-    const double heavy = std::fmax(1.0, 0.7 * wmax);
-    int uniform = 0;
-    double best = 1e300;
-    for (int k = 0; k < 8; k++) {
-        if (!allowed(k)) continue;
-        // latency of the deepest model | throughput (ragged batch: at the mean depth; shared chip: of all calls in flight)
-        const double cost = std::fmax(heavy * (double)bh::kFormMs[regime][k][0], form_ms(regime_thr, k, eff * load));
-        if (cost < best) { best = cost; uniform = k; }
-    }
-    int form[bh::BH_NT];
-    for (int t = 0; t < ntargets; t++) form[t] = uniform;
-    static const bool no_mixed = std::getenv("BH_SWD_NO_MIXED") != nullptr;
-    // the form the heaviest target moves to: 128-lane teams from seven layers up, 8-lane teams below (of 8-, 64-
-    // and 128-lane teams beside the lane kernel, seven shapes: profiles/r03_mixed_forms.txt, part 4)
-    const int moved = (regime >= 2 && allowed(5)) ? 5 : 1;
-    if (ntargets > 1 && !no_mixed && uniform == 0 && regime <= 3 && (long)B <= 32 * cus && allowed(moved)) {
-        double w[bh::BH_NT];
-        for (int t = 0; t < ntargets; t++) w[t] = target_weight(targets[t]);
-        // latency (chip mostly idle) and saturation rate (searches per ms) of a form, from the table's ends
-        auto lat = [&](int k) { return (double)bh::kFormMs[regime][k][0]; };
-        auto thr = [&](int k) {
-            const int n = measured(bh::kFormMs[regime][k]);
-            return (double)bh::kFormSearches[n - 1] / bh::kFormMs[regime][k][n - 1] / scale;
-        };
-        auto cost_of = [&](const int *fm) {
-            double l = 0.0, sum = 0.0;
-            for (int t = 0; t < ntargets; t++) {
-                l = std::fmax(l, lat(fm[t]) * w[t]);
-                sum += (double)B * w[t] / thr(fm[t]);
-            }
-            return std::fmax(l, sum);
-        };
-        double cur = cost_of(form);
-        for (int pass = 0; pass + 1 < ntargets; pass++) {
-            int worst = -1;                                  // the lane-kernel target the call is waiting for
-            for (int t = 0; t < ntargets; t++)
-                if (form[t] == 0 && (worst < 0 || w[t] > w[worst])) worst = t;
-            if (worst < 0) break;
-            form[worst] = moved;
-            const double c = cost_of(form);
-            if (c > 0.9 * cur) { form[worst] = 0; break; }
-            cur = c;
-        }
-    }
-    for (int t = 0; t < ntargets; t++) width[t] = bh::kFormWidth[form[t]];
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -434,186 +78,6 @@ int bh_set_device(int device)
     int rc = bh::require_device();
     if (rc) return rc;
     BH_HIP(hipSetDevice(device));
-    return BH_OK;
-}
-
-int bh_swd_set_kernel(int mode)
-{
-    if (mode < BH_SWD_AUTO || mode > BH_SWD_TEAM512) return fail_arg_("unknown kernel mode");
-    g_swd_mode.store(mode, std::memory_order_relaxed);
-    return BH_OK;
-}
-
-size_t bh_swd_workspace_bytes(int B, int ntargets, const bh_swd_target *targets)
-{
-    if (!targets || B <= 0) return 0;
-    for (int t = 0; t < ntargets; t++)
-        if (targets[t].mode > 1) return (size_t)ntargets * 2 * bh::BH_NP * (size_t)B * sizeof(double);
-    return 0;
-}
-
-int bh_swd_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h,
-                 const double *vp, const double *vs, const double *rho, int ntargets,
-                 const bh_swd_target *targets, const double *periods, double *out, int out_stride,
-                 int *err, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return bh_swd_batch_ordered(B, Lmax, model_stride, nlay, h, vp, vs, rho, ntargets, targets, periods, out,
-                                out_stride, err, nullptr, workspace, workspace_bytes, stream);
-}
-
-int bh_swd_batch_ordered(int B, int Lmax, int model_stride, const int *nlay, const double *h,
-                         const double *vp, const double *vs, const double *rho, int ntargets,
-                         const bh_swd_target *targets, const double *periods, double *out,
-                         int out_stride, int *err, const int *order, void *workspace,
-                         size_t workspace_bytes, void *stream)
-{
-    const Hint hint = take_hint();
-    if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return fail_arg_("B/Lmax out of range");
-    if (model_stride < Lmax) return fail_arg_("model_stride < Lmax");
-    if (ntargets < 1 || ntargets > BH_MAX_TARGETS) return fail_arg_("ntargets out of range");
-    if (B == 0) return BH_OK;   // nothing to do; an empty device buffer may legitimately be NULL
-    if (!nlay || !h || !vp || !vs || !rho || !targets || !periods || !out || !err)
-        return fail_arg_("NULL pointer");
-    int rc = bh::require_device();
-    if (rc) return rc;
-    bh::SwdArgs A;
-    std::memset(&A, 0, sizeof(A));
-    for (int t = 0; t < ntargets; t++) {
-        const bh_swd_target &s = targets[t];
-        if (s.iwave != 1 && s.iwave != 2) return fail_arg_("iwave must be 1 (Love) or 2 (Rayleigh)");
-        if (s.nper < 0 || s.nper > BH_MAX_PERIODS) return fail_arg_("nper out of range (max 60)");
-        if (s.mode < 1) return fail_arg_("mode must be >= 1");
-        if (s.out_off < 0 || s.out_off + s.nper > out_stride) return fail_arg_("target does not fit the output row");
-        A.tg[t] = bh::SwdTargetDev{s.iwave, s.igr, s.mode, s.iflsph, s.nper, s.per_off, s.out_off, 0};
-    }
-    size_t need = bh_swd_workspace_bytes(B, ntargets, targets);
-    if (need > 0 && (!workspace || workspace_bytes < need)) {
-        g_err = "workspace too small for mode > 1 (bh_swd_workspace_bytes)";
-        return BH_ERR_WORKSPACE;
-    }
-    A.B = B; A.Lmax = Lmax; A.ntargets = ntargets; A.out_stride = out_stride; A.mstride = model_stride;
-    A.nlay = nlay; A.order = order; A.h = h; A.vp = vp; A.vs = vs; A.rho = rho; A.periods = periods;
-    A.out = out; A.err = err; A.ws = (double *)workspace;
-    A.vec2 = (Lmax % 2 == 0 && model_stride % 2 == 0 &&
-              (((uintptr_t)h | (uintptr_t)vp | (uintptr_t)vs | (uintptr_t)rho) & 15) == 0) ? 1 : 0;
-    int resident = 0, slot = 0;
-    rc = get_queue_slot(&A.counters, &slot, &resident);
-    if (rc) return rc;
-    const long cus = resident > 0 ? resident / 8 : 256;
-    int width[bh::BH_NT];
-    plan_forms(B, Lmax, ntargets, targets, cus, g_swd_mode.load(std::memory_order_relaxed), width, hint.mean, hint.load);
-    // one launch per kernel form; the form with the heaviest target goes first, on the caller's stream
-    struct Launch { int width, n; double weight; unsigned char sel[bh::BH_NT]; };
-    Launch launches[bh::BH_NT];
-    int nlaunch = 0;
-    for (int t = 0; t < ntargets; t++) {
-        int k = 0;
-        while (k < nlaunch && launches[k].width != width[t]) k++;
-        if (k == nlaunch) { launches[k].width = width[t]; launches[k].n = 0; launches[k].weight = 0.0; nlaunch++; }
-        launches[k].sel[launches[k].n++] = (unsigned char)t;
-        launches[k].weight = std::fmax(launches[k].weight, target_weight(targets[t]));
-        g_last_forms[t] = width[t];
-    }
-    for (int a = 1; a < nlaunch; a++)
-        if (launches[a].weight > launches[0].weight) std::swap(launches[a], launches[0]);
-    hipStream_t main_stream = (hipStream_t)stream;
-    // the work-queue heads: only the lane kernel and the narrow teams pull searches from a queue (a wide team is one
-    // workgroup per search) -- small pools on wide teams are spared a fill kernel per call
-    bool queued = false;
-    for (int a = 0; a < nlaunch; a++) queued = queued || launches[a].width < 64;
-    hipError_t le = queued ? hipMemsetAsync(A.counters, 0, bh::BH_NT * sizeof(unsigned int), main_stream) : hipSuccess;
-    SlotStreams ss{};
-    bool forked = false;                 // the aux streams and the slot's fork/join events are in `ss`
-    if (le == hipSuccess && nlaunch > 1) {
-        rc = get_slot_streams(slot, nlaunch - 1, &ss);
-        if (rc) { release_queue_slot(slot, main_stream); return rc; }
-        forked = true;
-        le = hipEventRecord(ss.fork, main_stream);            // the models (and the zeroed counters) are ready
-        note_fork_stream(slot, main_stream);
-    }
-    for (int a = 0; a < nlaunch && le == hipSuccess; a++) {
-        const Launch &l = launches[a];
-        hipStream_t st = a == 0 ? main_stream : ss.aux[a - 1];
-        if (a > 0) le = hipStreamWaitEvent(st, ss.fork, 0);
-        if (le != hipSuccess) break;
-        A.nsel = l.n;
-        A.tmask = 0;
-        for (int k = 0; k < l.n; k++) A.tmask |= 1u << l.sel[k];
-        for (int k = 0; k < l.n; k++) {                       // heaviest first (insertion sort, at most BH_NT entries)
-            int i = k;
-            while (i > 0 && target_weight(targets[A.tord[i - 1]]) < target_weight(targets[l.sel[k]])) { A.tord[i] = A.tord[i - 1]; i--; }
-            A.tord[i] = l.sel[k];
-        }
-        if (l.width > 0) {
-            int w = l.width;
-            while (w > 64 && bh::swd_team_lds_bytes(Lmax, w) > bh::kLdsLimit) w /= 2;
-            int team_resident = resident;
-            if (w < 64) {           // persistent waves of a narrow-team kernel that stay resident
-                long per_cu = (long)(bh::kLdsLimit / bh::swd_team_lds_bytes(Lmax, w));
-                long waves = cus * (per_cu > 4 * bh::BH_NARROW_WAVES ? 4 * bh::BH_NARROW_WAVES : per_cu);
-                team_resident = (int)(waves > 0 ? waves : 1);
-            }
-            le = bh::launch_swd_team(A, w, team_resident, st);
-        } else {
-            le = bh::launch_swd(A, resident, st);
-        }
-        if (a > 0 && le == hipSuccess) le = hipEventRecord(ss.join[a - 1], st);
-    }
-    // the caller's stream continues when every launch is done -- also after a failed launch, for those that
-    // were started
-    // (an event that was not recorded in this call is complete: waiting for it costs nothing)
-    for (int a = 1; a < nlaunch && forked; a++) {
-        hipError_t we = hipStreamWaitEvent(main_stream, ss.join[a - 1], 0);
-        if (le == hipSuccess) le = we;
-    }
-    g_last_form = launches[0].width;
-    rc = release_queue_slot(slot, main_stream);    // also after a failed launch: the slot is free
-    if (le != hipSuccess) return fail_hip_((int)le, "dispersion kernel launch");
-    return rc;
-}
-
-int bh_swd_last_form(void) { return g_last_form; }
-
-int bh_swd_plan_forms(int B, int Lmax, int ntargets, const bh_swd_target *targets, int cus, int *forms)
-{
-    const Hint hint = take_hint();
-    if (B < 1 || Lmax < 1 || Lmax > BH_MAX_LAYERS || ntargets < 1 || ntargets > BH_MAX_TARGETS || !targets || !forms)
-        return fail_arg_("bh_swd_plan_forms: bad argument");
-    plan_forms(B, Lmax, ntargets, targets, cus > 0 ? cus : 256, g_swd_mode.load(std::memory_order_relaxed), forms,
-               hint.mean, hint.load);
-    return BH_OK;
-}
-
-int bh_swd_hint(double mean_layers, int concurrent_calls)
-{
-    if (!(mean_layers >= 0.0) || concurrent_calls < 1) return fail_arg_("bh_swd_hint: mean_layers >= 0, concurrent_calls >= 1");
-    g_hint = Hint{mean_layers, concurrent_calls};
-    return BH_OK;
-}
-
-int bh_swd_set_forms(const int *forms, int ntargets)
-{
-    if (ntargets == 0 || !forms) { g_nforced = 0; return BH_OK; }
-    if (ntargets < 0 || ntargets > BH_MAX_TARGETS) return fail_arg_("bh_swd_set_forms: ntargets out of range");
-    int distinct = 0;
-    for (int t = 0; t < ntargets; t++) {
-        const int w = forms[t];
-        if (bh::swd_form_of_width(w) < 0)
-            return fail_arg_("bh_swd_set_forms: a form is 0 (lane kernel) or 8, 16, ..., 512 lanes per search");
-        bool seen = false;
-        for (int u = 0; u < t; u++) seen = seen || forms[u] == w;
-        distinct += seen ? 0 : 1;
-    }
-    if (distinct > kAuxStreams + 1) return fail_arg_("bh_swd_set_forms: at most three different forms per call");
-    for (int t = 0; t < ntargets; t++) g_forced_forms[t] = forms[t];
-    g_nforced = ntargets;
-    return BH_OK;
-}
-
-int bh_swd_last_forms(int *forms, int ntargets)
-{
-    if (!forms || ntargets < 0 || ntargets > BH_MAX_TARGETS) return fail_arg_("bh_swd_last_forms: bad argument");
-    for (int t = 0; t < ntargets; t++) forms[t] = g_last_forms[t];
     return BH_OK;
 }
 
@@ -779,7 +243,6 @@ int bh_stream_synchronize(void *stream)
     BH_HIP(hipStreamSynchronize((hipStream_t)stream));
     return BH_OK;
 }
-int bh_stream_retire(void *stream) { return retire_stream((hipStream_t)stream); }
 int bh_stream_create(void **stream)
 {
     if (!stream) return fail_arg_("stream is NULL");
@@ -793,7 +256,7 @@ int bh_stream_create(void **stream)
 int bh_stream_destroy(void *stream)
 {
     if (!stream) return fail_arg_("the null stream cannot be destroyed");
-    int rc = retire_stream((hipStream_t)stream);
+    int rc = bh_stream_retire(stream);
     if (rc) return rc;
     BH_HIP(hipStreamDestroy((hipStream_t)stream));
     return BH_OK;

@@ -111,7 +111,7 @@ static void plan_free(bh_eval_plan *p)
     if (p->fork) (void)hipEventDestroy(p->fork);
     if (p->join) (void)hipEventDestroy(p->join);
     if (p->done) (void)hipEventDestroy(p->done);
-    // the library's own events on these streams (work-queue slot guards, capi.hip) go before the streams do
+    // the library's own events on these streams (work-queue slot guards, swd_launch.hip) go before the streams do
     if (p->st) (void)bh_stream_retire(p->st);
     if (p->side) (void)bh_stream_retire(p->side);
     if (p->st) (void)hipStreamDestroy(p->st);
@@ -389,7 +389,7 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
                                          (size_t)count, 0, 32, p->st));
         order = p->order;
     }
-    // the batch is ragged: the planner prices it by its mean depth, not by its deepest model (capi.hip: plan_forms)
+    // the batch is ragged: the planner prices it by its mean depth, not by its deepest model (swd_launch.hip: plan_forms)
     hipStream_t rst = overlap ? p->side : p->st;
     if ((rc = forward_batch(count, Leff, 4 * L, dnlay, h, vp, vs, rho, p->nswd, p->swd.data(), p->periods,
                             (int)p->interp.size(), p->interp.data(), p->nrf, p->rf.data(), order,

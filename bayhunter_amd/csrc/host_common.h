@@ -19,6 +19,7 @@ namespace bh {
 constexpr size_t kLdsLimit = 160 * 1024;        // LDS of a CU: the most a workgroup's launch may ask for
 
 // capi.hip.  The message goes to the calling thread's bh_last_error; the return value is the error code.
+__attribute__((visibility("hidden"))) int fail_(int code, const char *what);   // `code`, any BH_ERR_*; not exported
 int fail_arg_(const char *what);                // BH_ERR_ARG
 int fail_hip_(int e, const char *what);         // BH_ERR_HIP, `e` a hipError_t: "<what>: <hipGetErrorString(e)>"
 int require_device();                           // BH_OK, or BH_ERR_NO_DEVICE (there is no CPU fallback)

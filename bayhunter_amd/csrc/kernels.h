@@ -1,5 +1,5 @@
 // kernels.h -- kernel argument blocks and launchers shared by kernels.hip, like_kernel.hip and the C ABI's host files
-// (capi.hip, rf_capi.hip, like_capi.hip).
+// (capi.hip, swd_launch.hip, rf_capi.hip, like_capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rf_core.h"
@@ -32,7 +32,7 @@ struct SwdArgs {
     SwdTargetDev tg[BH_NT];
     // A launch covers the targets whose bit is set in tmask (nsel of them): the grid always spans all targets
     // in y and the workgroups of the others leave at once.  bh_swd_batch may give the targets of one call to
-    // different kernel forms (capi.hip: plan_forms), one launch per form on concurrent streams.  (A list of
+    // different kernel forms (swd_launch.hip: plan_forms), one launch per form on concurrent streams.  (A list of
     // target indices looked up by blockIdx.y cost swd_kernel six VGPRs -- 195, allocated as 200 -- and with
     // them the co-residency with rf_kernel: 2 x 192 + 128 is all a SIMD has.)
     unsigned int tmask;

@@ -839,7 +839,7 @@ __device__ __forceinline__ void swd_tpl_body(const SwdArgs &A)
     TeamLay lay{(float *)(nevt + 24 + (K + 1) / 2), A.Lmax};
     // Every wave of a launch drains the targets' queues one after the other, heaviest target first (A.tord; whatever
     // blockIdx.y says): the targets of a call differ in weight by a factor of three (BASELINE cfg3: Rayleigh group
-    // velocities 3.2, Love phase velocities 1.1 table searches per model, capi.hip: target_weight), and with a fixed
+    // velocities 3.2, Love phase velocities 1.1 table searches per model, swd_launch.hip: target_weight), and with a fixed
     // share of the waves each the call took as long as its heaviest target on a quarter of the chip -- and how long
     // that was depended on which waves the dispatcher had happened to pair on a SIMD (15.1 or 17.2 ms for the same
     // launch, profiles/r04_order_effect.txt).  Longest searches first is the list-scheduling order.

@@ -97,7 +97,7 @@ size_t bh_swd_workspace_bytes(int B, int ntargets, const bh_swd_target *targets)
  *   TEAM128/256/512 2, 4, 8 waves per search: deeper speculation for deep models / few searches
  *   TEAM32/16/8     2, 4, 8 searches per wave: less speculation, more searches resident
  * BH_SWD_AUTO (default) picks by a measured latency / saturation-rate table on searches per call,
- * deepest model and CU count (capi.hip; profiles/r02_team_widths.txt).  Process-wide setting,
+ * deepest model and CU count (swd_launch.hip; profiles/r02_team_widths.txt).  Process-wide setting,
  * read once per call. */
 #define BH_SWD_AUTO 0
 #define BH_SWD_LANE 1

@@ -1,5 +1,5 @@
 """What the form planner answers over a grid of calls (bh_swd_plan_forms, host only: no GPU), and which widths
-bh_swd_set_forms takes -- recorded from the built library, so that a change to capi.hip that is meant to leave the
+bh_swd_set_forms takes -- recorded from the built library, so that a change to swd_launch.hip that is meant to leave the
 plans alone can be held to it (tests/test_capi_host.py: test_form_plans_are_the_recorded_ones).
 
     python tests/golden/make_golden_form_plans.py      (writes tests/golden/form_plans.json)

@@ -561,7 +561,7 @@ def test_rf_ill_conditioned_models_are_bounded_by_the_references_own_error(lib):
 @pytest.mark.parametrize('case', ['cfg3', 'modes'])
 def test_targets_of_one_call_on_different_kernel_forms(lib, case):
     """A latency-bound call with several targets (BASELINE cfg3: 8192 models, Rayleigh + Love, phase + group, 40
-    periods) can run its targets on different kernel forms, each on a stream of its own (capi.hip: plan_forms,
+    periods) can run its targets on different kernel forms, each on a stream of its own (swd_launch.hip: plan_forms,
     bh_swd_set_forms).  The values must not depend on that: same rows, bit for bit, as with every target on the lane
     kernel -- also for a target with higher modes (its workspace block and err column keep their index)."""
     import ctypes as C

@@ -25,7 +25,7 @@ def test_swd_and_rf_kernels_fit_one_simd_together():
     assert _alloc(r['swd_kernel']['vgpr']) <= 192 and _alloc(r['rf_kernel<false>']['vgpr']) <= 128, r
     assert 2 * _alloc(r['swd_kernel']['vgpr']) + _alloc(r['rf_kernel<false>']['vgpr']) <= 512
     # a multi-target call that is latency-bound on the lane kernel moves its heaviest target to 128-lane teams beside it
-    # (capi.hip: plan_forms; BASELINE cfg3: 22.7 -> 17 ms): one lane-kernel wave and two team waves share a SIMD.
+    # (swd_launch.hip: plan_forms; BASELINE cfg3: 22.7 -> 17 ms): one lane-kernel wave and two team waves share a SIMD.
     # (Ten more registers in the wide teams -- a Neville table in register lanes, round 4 -- and cfg3 took 28.7 ms.)
     assert _alloc(r['swd_kernel']['vgpr']) + 2 * _alloc(r['swd_team128_kernel']['vgpr']) <= 512, r
     # the narrow teams (8 .. 32 lanes per search, a lane's whole period equation like swd_kernel) keep two waves per SIMD

@@ -65,3 +65,25 @@ def test_device_solver_cores_under_asan_ubsan(tmp_path):
         pytest.skip('the sanitizer runtime cannot start in this environment: ' + r.stderr[-300:])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert 'cores ok' in r.stdout and 'runtime error' not in r.stderr, r.stderr[-4000:]
+
+
+@pytest.mark.parametrize('flags', [['-fsanitize=address,undefined', '-fno-omit-frame-pointer'], ['-fsanitize=thread']],
+                         ids=['asan_ubsan', 'tsan'])
+def test_slot_ring_claims_under_asan_ubsan_and_tsan(tmp_path, flags):
+    """csrc/slot_ring.h, the claim flags under SlotClaim (swd_launch.hip), in tests/hostsim/slot_ring_sim.cpp: four
+    threads on a ring of 2 and of 8 slots, no slot with two holders, a claim that leaves its scope frees its slot, "all
+    claimed" only when all are held."""
+    src = os.path.join(ROOT, 'tests', 'hostsim', 'slot_ring_sim.cpp')
+    exe = str(tmp_path / 'slot_ring')
+    c = subprocess.run(['g++', '-O1', '-g', '-std=c++17', '-pthread'] + flags + [src, '-o', exe], capture_output=True, text=True)
+    if c.returncode != 0 and ('cannot find' in c.stderr or 'sanitizer' in c.stderr.lower()):
+        pytest.skip('sanitizer runtime not installed: ' + c.stderr[-300:])
+    assert c.returncode == 0, c.stderr[-4000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, UBSAN_OPTIONS='print_stacktrace=1', TSAN_OPTIONS='halt_on_error=1'))
+    if ('unexpected memory mapping' in r.stderr or 'Shadow memory range interleaves' in r.stderr
+            or 'ReserveShadowMemoryRange failed' in r.stderr):
+        pytest.skip('the sanitizer runtime cannot start in this environment: ' + r.stderr[-300:])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert 'slot ring ok' in r.stdout and 'runtime error' not in r.stderr and 'WARNING: ThreadSanitizer' not in r.stderr, \
+        r.stderr[-4000:]
