@@ -73,7 +73,7 @@ def noise_priors(priors, targets):
     return out
 
 
-class _CallEvaluator(object):
+class CallEvaluator(object):
     """Adapter for a plain function (packed, nlay, noise) -> (logL, misfits)."""
 
     def __init__(self, fn):
@@ -296,7 +296,7 @@ class ChainPool(object):
         if evaluator is None:
             evaluator = GpuEvaluator(targets)
         elif not hasattr(evaluator, 'submit'):
-            evaluator = _CallEvaluator(evaluator)
+            evaluator = CallEvaluator(evaluator)
         self.evaluator = evaluator
         if groups is None:
             groups = 2 if self.nchains >= GROUPS_MIN_CHAINS else 1
@@ -548,7 +548,7 @@ class ChainPool(object):
         """PlotFromStorage.get_outliers (src/Plotting.py:113-154) on the likes save() writes: chains whose
         median main-phase likelihood deviates from the best chain's by more than `dev` (relative).  Global
         chain indices; chains without main-phase rows are not listed."""
-        from .posterior import pool_outliers
+        from .selection import pool_outliers
         return pool_outliers(self, dev)
 
     def posterior(self, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None):

@@ -18,8 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from .posterior import SetList, _Handle, _to_device, _torch_device, check_set_start, pool_rows, raise_first_failed
+from . import _device, _lib, selection as sel      # (`selection` is a parameter of the entry points)
 
 DEFAULT_Q = (2.5, 16, 50, 84, 97.5)
 CHUNK = 65536                     # rows per layers_from_voronoi call: bounds the packed-model temporaries
@@ -60,12 +59,12 @@ def _layers(models, dev):
     return vsn.contiguous(), zv.contiguous(), n.to(torch.int32)
 
 
-class _Fits(_Handle):
+class Fits(_device.Handle):
     """One bh_datafits handle over a device matrix."""
 
     def __init__(self, Y, ncols, weights, err, stream):
         self.ncols = ncols
-        _Handle.__init__(
+        _device.Handle.__init__(
             self, 'datafits', Y.data_ptr(), Y.shape[0], Y.stride(0), ncols, None if weights is None else
             weights.data_ptr(), None if err is None else err.data_ptr(), 0 if err is None else err.shape[1], stream)
 
@@ -101,22 +100,22 @@ def forward_matrix(targets, models, vpvs, mantle=None, device=None, rf_p=None, s
     import torch
     from .engine import ForwardEngine
     from .models import layers_from_voronoi
-    dev = _torch_device(device)
+    dev = _device.torch_device(device)
     bl = targets.batch_layout()
     lay = bl['layout']
     with torch.cuda.device(dev):
         eng = ForwardEngine(swd=lay.swd, rf=lay.rf, device=dev)
-        rows = _to_device(models, torch.float64, dev)
-        vpvs = _to_device(np.broadcast_to(np.asarray(vpvs, dtype=np.float64), (rows.shape[0],))
-                          if not isinstance(vpvs, torch.Tensor) else vpvs, torch.float64, dev)
+        rows = _device.to_device(models, torch.float64, dev)
+        vpvs = _device.to_device(np.broadcast_to(np.asarray(vpvs, dtype=np.float64), (rows.shape[0],))
+                                 if not isinstance(vpvs, torch.Tensor) else vpvs, torch.float64, dev)
         R = rows.shape[0]
         tab = ids = None
         if rf_p is not None and lay.rf:
             rf_p = np.asarray(rf_p, dtype=np.float64)
             if rf_p.ndim != 2 or rf_p.shape[1] != len(lay.rf) or set_id is None or len(set_id) != R:
                 raise ValueError("rf_p: [nstations, %d receiver functions], with one station index per row" % len(lay.rf))
-            tab = _to_device(np.ascontiguousarray(rf_p.T), torch.float64, dev)
-            ids = _to_device(set_id, torch.int32, dev)
+            tab = _device.to_device(np.ascontiguousarray(rf_p.T), torch.float64, dev)
+            ids = _device.to_device(set_id, torch.int32, dev)
         need = R * eng.row * 8 + R * bl['nflags'] * 4
         free = torch.cuda.mem_get_info(dev)[0]
         if need > free:
@@ -180,7 +179,7 @@ def _result(targets, segs, s, rk, ost, hist, std, edges, best, q):
 
 def _summarize(targets, models, vpvs, weights, misfits, mantle, q, nbins, device, pick=None):
     import torch
-    dev = _torch_device(device)
+    dev = _device.torch_device(device)
     if not isinstance(models, torch.Tensor):
         models = np.asarray(models)
     if models.ndim != 2 or models.shape[0] == 0:
@@ -188,7 +187,7 @@ def _summarize(targets, models, vpvs, weights, misfits, mantle, q, nbins, device
     R = models.shape[0]
     if int(nbins) < 1:
         raise ValueError("nbins >= 1")
-    w = None if weights is None else _to_device(weights, torch.int32, dev)
+    w = None if weights is None else _device.to_device(weights, torch.int32, dev)
     if w is not None and w.numel() != R or misfits is not None and np.asarray(misfits).size != R:
         raise ValueError("one weight and one misfit per row")
     eng, Y, err, bl = forward_matrix(targets, models, vpvs, mantle, dev)
@@ -197,7 +196,7 @@ def _summarize(targets, models, vpvs, weights, misfits, mantle, q, nbins, device
     ncols = eng.ncols
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        with _Fits(Y, ncols, w, err, stream) as f:
+        with Fits(Y, ncols, w, err, stream) as f:
             s = f.scan()
             rk = order_ranks(q, s['total'])
             edges, eset = target_edges(s['vmin'], s['vmax'], segs, nbins)
@@ -241,7 +240,7 @@ def best_rows(ci, w, misfits):
 
 def pool_datafits(pool, selection='weighted', dev=0.05, exclude_outliers=True, q=DEFAULT_Q, nbins=100, device=None):
     """ChainPool.datafits: summarize() over the rows ChainPool.posterior uses, plus each chain's best fit."""
-    ci, ri, w = pool_rows(pool, selection, dev, exclude_outliers)
+    ci, ri, w = sel.pool_rows(pool, selection, dev, exclude_outliers)
     mis = pool.misfits[ci, ri, -1].astype(np.float64)
     pick = best_rows(ci, w, mis)
     res = _summarize(pool.targets, pool.models[ci, ri], pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32),
@@ -254,14 +253,14 @@ def pool_datafits(pool, selection='weighted', dev=0.05, exclude_outliers=True, q
 
 # ---- many sets of rows in one pass: the stations of a network ---------------------------------------------
 
-class _FitsSets(_Handle):
+class _FitsSets(_device.Handle):
     """One bh_datafits_sets handle over a device matrix whose rows come in contiguous sets."""
 
     def __init__(self, Y, ncols, weights, err, set_start, stream, chunk_bytes=None):
         self.ncols = ncols
         self.set_start = np.ascontiguousarray(set_start, dtype=np.int64)
         self.nsets = self.set_start.size - 1
-        _Handle.__init__(
+        _device.Handle.__init__(
             self, 'datafits_sets', Y.data_ptr(), Y.shape[0], Y.stride(0), ncols, None if weights is None else
             weights.data_ptr(), None if err is None else err.data_ptr(), 0 if err is None else err.shape[1],
             self.set_start.ctypes.data, self.nsets, stream)
@@ -304,7 +303,7 @@ class _DeviceSets(object):
     it, and rows of the matrix back on the host.  (The CPU tier puts a numpy stand-in in its place.)"""
 
     def __init__(self, stations, mantle, device, rf_p, chunk_bytes=None):
-        self.dev = _torch_device(device)
+        self.dev = _device.torch_device(device)
         self.joint, self.mantle, self.rf_p, self.chunk_bytes = stations[0], mantle, rf_p, chunk_bytes
         bl = self.joint.batch_layout()
         desc, lay = bl['desc'], bl['layout']
@@ -324,7 +323,7 @@ class _DeviceSets(object):
 
     def fits(self, Y, err, weights, set_start):
         import torch
-        w = None if weights is None else _to_device(weights, torch.int32, self.dev)
+        w = None if weights is None else _device.to_device(weights, torch.int32, self.dev)
         self._w = w                                    # alive as long as the handle
         return _FitsSets(Y, self.ncols, w, err, set_start, torch.cuda.current_stream(self.dev).cuda_stream,
                          self.chunk_bytes)
@@ -367,7 +366,7 @@ def set_ranks(q, totals):
     return rk, ranks
 
 
-class SetFits(SetList):
+class SetFits(sel.SetList):
     """summarize_sets' list: entry s is summarize()'s dict of set s, or None for a set in `failed`
     ({set index: message})."""
 
@@ -380,7 +379,7 @@ def _summarize_sets(stations, models, set_start, vpvs, weights, misfits, mantle,
     if models.ndim != 2:
         raise ValueError("models: [rows, 2*maxlayers]")
     R = models.shape[0]
-    set_start, S = check_set_start(set_start, R)
+    set_start, S = sel.check_set_start(set_start, R)
     if len(stations) != S:
         raise ValueError("one JointTarget per set")
     if int(nbins) < 1:
@@ -431,9 +430,9 @@ def _summarize_sets(stations, models, set_start, vpvs, weights, misfits, mantle,
                     rows.append(int(cand[np.argmin(mf[cand])]) - lo)
                 best = be.gather(Y, rows)
             if pick is not None:
-                sel = pick[(pick >= lo) & (pick < hi)]
-                got = be.gather(Y, sel - lo) if sel.size else np.zeros((0, be.ncols))
-                of = np.searchsorted(sel, set_start[a:b + 1])
+                own = pick[(pick >= lo) & (pick < hi)]
+                got = be.gather(Y, own - lo) if own.size else np.zeros((0, be.ncols))
+                of = np.searchsorted(own, set_start[a:b + 1])
                 for i in range(b - a):
                     picked[a + i] = [got[of[i]:of[i + 1], c0:c1] for c0, c1 in segs]
         for j, i in enumerate(live):
@@ -464,7 +463,7 @@ def summarize_sets(stations, models, set_start, vpvs, weights=None, misfits=None
     return _summarize_sets(stations, models, set_start, vpvs, weights, misfits, mantle, q, nbins, device, rf_p, max_rows)
 
 
-class StationDatafits(object):
+class StationDatafits(sel.StationResult):
     """StationPool.datafits' result.
 
     stations   {station name: the dict pool.station(name).datafits(...) returns}, failed stations left out
@@ -477,9 +476,8 @@ class StationDatafits(object):
     FIELDS = ('mean', 'std', 'median', 'min', 'max', 'best', 'residual')
 
     def __init__(self, names, results, failed, q):
-        self.names = list(names)
+        sel.StationResult.__init__(self, names, failed)
         self.stations = {n: r for n, r in zip(names, results) if r is not None}
-        self.failed = {names[z]: msg for z, msg in failed.items()}
         self.q = np.asarray(q, dtype=np.float64)
         S = len(self.names)
         first = next((r for r in results if r is not None), None)
@@ -502,9 +500,8 @@ class StationDatafits(object):
 def stations_datafits(spool, selection='weighted', dev=0.05, exclude_outliers=True, q=DEFAULT_Q, nbins=100, device=None,
                       strict=True, max_rows=None, backend=None):
     """StationPool.datafits: summarize_sets() over every station's main-phase rows (see StationPool.datafits)."""
-    from .posterior import station_rows
     pool, c = spool.pool, spool.chains_per_station
-    ci, ri, w, set_start, failed = station_rows(pool, c, selection, dev, exclude_outliers)
+    ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
     mis = pool.misfits[ci, ri, -1].astype(np.float64)
     pick = best_rows(ci, w, mis)
     rf_p = None
@@ -515,11 +512,11 @@ def stations_datafits(spool, selection='weighted', dev=0.05, exclude_outliers=Tr
                           w.astype(np.int32), mis, pool.priors.get('mantle'), q, nbins, device, rf_p, max_rows,
                           pick=pick, backend=backend)
     res.failed.update(failed)
-    raise_first_failed(res.failed, strict, "station", spool.names)
+    sel.raise_first_failed(res.failed, strict, "station", spool.names)
     for z, r in enumerate(res):
         if r is None:
             continue
         mine = pick[(pick >= set_start[z]) & (pick < set_start[z + 1])]
         r['bestfits'] = dict(chains=ci[mine] - z * c, rows=ri[mine], data=r.pop('_picked'))
-        r['chains'] = np.unique(ci[set_start[z]:set_start[z + 1]]) - z * c
+        r['chains'] = sel.station_chains(ci, set_start, z, c)
     return StationDatafits(spool.names, res, res.failed, q)

@@ -13,9 +13,8 @@ Edges are made here with numpy as np.histogram / np.histogram2d make them.
 """
 import numpy as np
 
-from . import _lib
-from .datafits import _Fits
-from .posterior import _to_device, _torch_device, check_set_start, pool_rows, station_rows
+from . import _device, _lib, selection as sel      # (`selection` is a parameter of the entry points)
+from .datafits import Fits
 
 NAMES = ('moho', 'vs_crust', 'vs_last', 'vs_jump')          # the columns of the derived matrix
 TRADEOFF = ('vs_last', 'vs_crust', 'vs_jump')               # x axes of the joint histograms, in the reference's order
@@ -30,20 +29,6 @@ def _window(moho, mohovs, nbins):
     if int(nbins) < 1:
         raise ValueError("nbins >= 1")
     return zlo, zhi, mohovs, int(nbins)
-
-
-def _rows_weights(models, weights, dev):
-    import torch
-    if not isinstance(models, torch.Tensor):
-        models = np.asarray(models)
-    if models.ndim != 2:
-        raise ValueError("models: [rows, 2*maxlayers]")
-    fdtype = torch.float32 if str(models.dtype).endswith('float32') else torch.float64
-    rows = _to_device(models, fdtype, dev)
-    w = None if weights is None else _to_device(weights, torch.int32, dev)
-    if w is not None and w.numel() != rows.shape[0]:
-        raise ValueError("one weight per row")
-    return rows, w
 
 
 def derive(rows, zlo, zhi, mohovs, stream):
@@ -81,16 +66,15 @@ def summarize(models, weights=None, moho=(0., 100.), mohovs=4.2, nbins=50, devic
                         xedges, yedges, mode = (x, y): the cell centres of the first maximum in C order)})
     ValueError when no row has a Moho."""
     import torch
-    dev = _torch_device(device)
     zlo, zhi, mohovs, nbins = _window(moho, mohovs, nbins)
-    rows, w = _rows_weights(models, weights, dev)
+    dev, rows, w, _ = _device.device_rows(models, weights, per_row="one weight per row", device=device)
     if rows.shape[0] == 0:
         raise ValueError("empty selection: no models")
     lib = _lib.load()
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         D = derive(rows, zlo, zhi, mohovs, stream)
-        with _Fits(D, 4, w, None, stream) as f:
+        with Fits(D, 4, w, None, stream) as f:
             try:
                 s = f.scan()
             except _lib.BayHunterAmdError as e:
@@ -128,12 +112,9 @@ def summarize_sets(models, set_start, weights=None, moho=(0., 100.), mohovs=4.2,
     A set without a row that has a Moho is no error: nmodels 0, its statistics NaN, its histogram empty.  A negative
     weight fails the call."""
     import torch
-    dev = _torch_device(device)
     zlo, zhi, mohovs, nbins = _window(moho, mohovs, nbins)
-    if not isinstance(models, torch.Tensor):
-        models = np.asarray(models)
-    set_start, S = check_set_start(set_start, models.shape[0] if models.ndim == 2 else -1)
-    rows, w = _rows_weights(models, weights, dev)
+    dev, rows, w, _ = _device.device_rows(models, weights, per_row="one weight per row", device=device)
+    set_start, S = sel.check_set_start(set_start, rows.shape[0])
     edges = np.linspace(zlo, zhi, nbins + 1)
     cnt, nex = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64)
     st = {k: np.full((S, 4), np.nan) for k in ('min', 'max', 'mean', 'std', 'lo', 'hi')}
@@ -161,20 +142,20 @@ def _widened(models, device):
     """A pool's float32 rows on the device as float64: save() writes them as float64 (the reference fills float64
     matrices, src/Models.py:228-274), so that is the dtype in which PlotFromStorage derives the Moho from them."""
     import torch
-    return _to_device(models, torch.float32 if models.dtype == np.float32 else torch.float64,
-                      _torch_device(device)).to(torch.float64)
+    return _device.to_device(models, torch.float32 if models.dtype == np.float32 else torch.float64,
+                             _device.torch_device(device)).to(torch.float64)
 
 
 def pool_moho(pool, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50, device=None):
     """ChainPool.moho: summarize() over the rows ChainPool.posterior uses, plus 'chains' (global indices used)."""
-    ci, ri, w = pool_rows(pool, selection, dev, exclude_outliers)
+    ci, ri, w = sel.pool_rows(pool, selection, dev, exclude_outliers)
     res = summarize(_widened(pool.models[ci, ri], device), w.astype(np.int32), pool.priors['z'] if moho is None else moho,
                     mohovs, nbins, device)
     res['chains'] = np.unique(ci) + pool.first
     return res
 
 
-class StationMoho(object):
+class StationMoho(sel.StationResult):
     """StationPool.moho's result, every array in the pool's station order.
 
     names      the stations
@@ -186,8 +167,7 @@ class StationMoho(object):
     failed     {station name: message}, as StationPool.posterior reports it (such a station has no rows)"""
 
     def __init__(self, names, res, failed):
-        self.names = list(names)
-        self.failed = {names[z]: msg for z, msg in failed.items()}
+        sel.StationResult.__init__(self, names, failed)
         for k, v in res.items():
             setattr(self, k, v)
 
@@ -196,7 +176,7 @@ def stations_moho(spool, moho=None, mohovs=4.2, selection='weighted', dev=0.05, 
                   device=None):
     """StationPool.moho: summarize_sets() over every station's main-phase rows."""
     pool, c = spool.pool, spool.chains_per_station
-    ci, ri, w, set_start, failed = station_rows(pool, c, selection, dev, exclude_outliers)
+    ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
     res = summarize_sets(_widened(pool.models[ci, ri], device), set_start, w.astype(np.int32),
                          pool.priors['z'] if moho is None else moho, mohovs, nbins, device)
     return StationMoho(spool.names, res, failed)

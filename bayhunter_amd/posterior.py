@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _device, _lib, selection as sel      # (`selection` is a parameter of the entry points)
 
 VS_INTERVAL = 0.025          # km/s: the reference's Vs bin width (Models.py:204, Plotting.py:495)
 
@@ -73,37 +73,7 @@ def stepmodel(row):
     return vs_step, dep_step
 
 
-def _torch_device(device):
-    import torch
-    if device is None:
-        return torch.device('cuda', torch.cuda.current_device())
-    if isinstance(device, int):
-        return torch.device('cuda', device)
-    return torch.device(device)
-
-
-class _Handle(object):
-    """A library handle of bh_<kind>_create(*args, &handle): destroyed by close(), or on leaving its `with` block."""
-
-    def __init__(self, kind, *args):
-        self.lib = _lib.load()
-        self.h = C.c_void_p()
-        self._destroy = getattr(self.lib, 'bh_%s_destroy' % kind)
-        _lib.check(getattr(self.lib, 'bh_%s_create' % kind)(*(args + (C.byref(self.h),))))
-
-    def close(self):
-        if self.h:
-            self._destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class _Grid(_Handle):
+class Grid(_device.Handle):
     """One bh_posterior handle: the rows on one depth grid."""
 
     def __init__(self, rows, weights, misfits, dep, ifedges, stream):
@@ -111,7 +81,7 @@ class _Grid(_Handle):
         self.ifedges = None if ifedges is None else np.ascontiguousarray(ifedges, dtype=np.float64)
         self.width = rows.shape[1]
         nif = 0 if self.ifedges is None else self.ifedges.size
-        _Handle.__init__(
+        _device.Handle.__init__(
             self, 'posterior', rows.data_ptr(), int(rows.dtype.itemsize == 8), rows.shape[0], rows.stride(0),
             self.width, None if weights is None else weights.data_ptr(),
             None if misfits is None else misfits.data_ptr(), self.dep.ctypes.data, self.dep.size,
@@ -138,15 +108,6 @@ class _Grid(_Handle):
                                                 hist.ctypes.data, None if std is None else std.ctypes.data,
                                                 None if median is None else median.ctypes.data))
         return hist, std, median
-
-
-def _to_device(a, dtype, dev):
-    import torch
-    if isinstance(a, torch.Tensor):
-        t = a.to(device=dev, dtype=dtype)
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
-    return t if t.dim() < 2 or t.stride(1) == 1 else t.contiguous()
 
 
 def _grids(dep_int, depint):
@@ -208,28 +169,18 @@ def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, dev
             nmodels      = the weighted number of models (the reference's "%d models"))
     ValueError where the reference raises (all values equal: no mode bin) and for an empty selection."""
     import torch
-    dev = _torch_device(device)
-    if not isinstance(models, torch.Tensor):
-        models = np.asarray(models)
-    if models.ndim != 2:
-        raise ValueError("models: [rows, 2*maxlayers]")
-    fdtype = torch.float32 if str(models.dtype).endswith('float32') else torch.float64
-    rows = _to_device(models, fdtype, dev)
+    dev, rows, w, mf = _device.device_rows(models, weights, misfits, device)
     if rows.shape[0] == 0:
         raise ValueError("empty selection: no models")
-    w = None if weights is None else _to_device(weights, torch.int32, dev)
-    mf = None if misfits is None else _to_device(misfits, torch.float64, dev)
-    if w is not None and w.numel() != rows.shape[0] or mf is not None and mf.numel() != rows.shape[0]:
-        raise ValueError("one weight and one misfit per row")
     dep_int, dep2, depbins = _grids(dep_int, depint)
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
-        with _Grid(rows, w, mf, dep_int, depbins, stream) as ga:
+        with Grid(rows, w, mf, dep_int, depbins, stream) as ga:
             s = ga.scan()
             vedges = mode_edges(s['vmin'], s['vmax'])
             mhist, std, median = ga.finish(vedges, bin_index(dep_int, dep_int), dep_int.size - 1, True)
         # the density of _plot_bestmodels_hist on its half-step grid
-        with _Grid(rows, w, None, dep2, None, stream) as gb:
+        with Grid(rows, w, None, dep2, None, stream) as gb:
             s2 = gb.scan()
             vsb = density_edges(s2['vmin'], s2['vmax'])
             h2, _, _ = gb.finish(vsb, bin_index(dep2, depbins), depbins.size - 1, False)
@@ -239,31 +190,7 @@ def summarize(models, weights=None, dep_int=None, misfits=None, depint=None, dev
 
 # ---- many sets of rows in one pass ------------------------------------------------------------------------
 
-def check_set_start(set_start, nrows):
-    """-> (set_start as contiguous int64 [sets + 1], sets); ValueError unless it ascends from 0 to nrows."""
-    set_start = np.ascontiguousarray(set_start, dtype=np.int64)
-    S = set_start.size - 1
-    if set_start.ndim != 1 or S < 1 or set_start[0] != 0 or set_start[-1] != nrows or np.any(np.diff(set_start) < 0):
-        raise ValueError("set_start: [sets + 1], ascending from 0 to the number of rows")
-    return set_start, S
-
-
-def raise_first_failed(failed, strict, what, names=None):
-    """strict: the first set (station, with `names`) of `failed` {index: message} is a ValueError."""
-    if failed and strict:
-        z = min(failed)
-        raise ValueError(("%s %r: %s" if names else "%s %d: %s") % (what, names[z] if names else z, failed[z]))
-
-
-class SetList(list):
-    """A per-set result list: entry s is the dict of set s, or None for a set in `failed` ({set index: message})."""
-
-    def __init__(self, results, failed):
-        list.__init__(self, results)
-        self.failed = failed
-
-
-class _Sets(_Handle):
+class Sets(_device.Handle):
     """One bh_posterior_sets handle: the rows, in contiguous sets, on one depth grid."""
 
     def __init__(self, rows, weights, misfits, set_start, dep, ifedges, stream, chunk_bytes=None):
@@ -272,7 +199,7 @@ class _Sets(_Handle):
         self.set_start = np.ascontiguousarray(set_start, dtype=np.int64)
         self.width, self.nsets = rows.shape[1], self.set_start.size - 1
         nif = 0 if self.ifedges is None else self.ifedges.size
-        _Handle.__init__(
+        _device.Handle.__init__(
             self, 'posterior_sets', rows.data_ptr(), int(rows.dtype.itemsize == 8), rows.shape[0], rows.stride(0),
             self.width, None if weights is None else weights.data_ptr(),
             None if misfits is None else misfits.data_ptr(), self.set_start.ctypes.data, self.nsets,
@@ -313,12 +240,12 @@ class _Sets(_Handle):
         return hists, std, median
 
 
-class SetResults(SetList):
+class SetResults(sel.SetList):
     """summarize_sets' list: entry s is summarize()'s dict of set s, or None for a set in `failed`
     ({set index: message}).  `std[s]` is the set's standard deviation per depth (summarize reports mean -+ std)."""
 
     def __init__(self, results, failed, dep_int, std):
-        SetList.__init__(self, results, failed)
+        sel.SetList.__init__(self, results, failed)
         self.dep, self.std = dep_int, std
 
     def section(self):
@@ -352,18 +279,8 @@ def summarize_sets(models, set_start, weights=None, dep_int=None, misfits=None, 
     chunk_bytes   bound on the device memory of the median's digit table (default 64 MiB): the sets are processed
                   in chunks that keep to it, and no result depends on it."""
     import torch
-    dev = _torch_device(device)
-    if not isinstance(models, torch.Tensor):
-        models = np.asarray(models)
-    if models.ndim != 2:
-        raise ValueError("models: [rows, 2*maxlayers]")
-    set_start, S = check_set_start(set_start, models.shape[0])
-    fdtype = torch.float32 if str(models.dtype).endswith('float32') else torch.float64
-    rows = _to_device(models, fdtype, dev)
-    w = None if weights is None else _to_device(weights, torch.int32, dev)
-    mf = None if misfits is None else _to_device(misfits, torch.float64, dev)
-    if w is not None and w.numel() != rows.shape[0] or mf is not None and mf.numel() != rows.shape[0]:
-        raise ValueError("one weight and one misfit per row")
+    dev, rows, w, mf = _device.device_rows(models, weights, misfits, device)
+    set_start, S = sel.check_set_start(set_start, rows.shape[0])
     dep_int, dep2, depbins = _grids(dep_int, depint)
     failed, results, std = {}, [None] * S, None
     if rows.shape[0] == 0:
@@ -372,7 +289,7 @@ def summarize_sets(models, set_start, weights=None, dep_int=None, misfits=None, 
         lib = _lib.load()
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            with _Sets(rows, w, mf, set_start, dep_int, depbins, stream, chunk_bytes) as ga:
+            with Sets(rows, w, mf, set_start, dep_int, depbins, stream, chunk_bytes) as ga:
                 s = ga.scan()
                 vedges = [None] * S
                 for z in range(S):
@@ -384,7 +301,7 @@ def summarize_sets(models, set_start, weights=None, dep_int=None, misfits=None, 
                     except ValueError as e:
                         failed[z] = str(e)
                 mhist, std, median = ga.finish(vedges, bin_index(dep_int, dep_int), dep_int.size - 1, True)
-            with _Sets(rows, w, None, set_start, dep2, None, stream, chunk_bytes) as gb:
+            with Sets(rows, w, None, set_start, dep2, None, stream, chunk_bytes) as gb:
                 s2 = gb.scan()
                 vsb = [None if z in failed else density_edges(s2['vmin'][z], s2['vmax'][z]) for z in range(S)]
                 h2, _, _ = gb.finish(vsb, bin_index(dep2, depbins), depbins.size - 1, False)
@@ -395,97 +312,15 @@ def summarize_sets(models, set_start, weights=None, dep_int=None, misfits=None, 
             sz['total'] = int(s['total'][z])
             results[z] = _result(sz, dep_int, vedges[z], mhist[z], std[z], median[z], h2[z], vsb[z], depbins,
                                  None if best is None else best[i])
-    raise_first_failed(failed, strict, "set")
+    sel.raise_first_failed(failed, strict, "set")
     return SetResults(results, failed, dep_int, std)
 
 
-# ---- the chain pool's own sample block ------------------------------------------------------------------
-
-def pool_selection(pool, selection='weighted'):
-    """Main-phase rows of a pool without a per-chain loop -> (chain index [rows] (local), row index [rows],
-    weight [rows] int64).  'weighted': residence time, ChainPool.weighted (next row's iter, or iter_main, minus
-    this row's).  'saved': how many of the rows save() writes are this row -- a row spanning the expanded
-    range [a, a + w) of its chain contributes ceil((a + w) / t) - ceil(a / t) rows at thinning t."""
-    if selection not in ('weighted', 'saved'):
-        raise ValueError("selection: 'weighted' or 'saved'")
-    n = np.asarray(pool.counters()[0], dtype=np.int64)
-    it = pool.iter
-    with np.errstate(invalid='ignore'):
-        main = (np.arange(it.shape[1])[None, :] < n[:, None]) & (it >= 0)
-    ci, ri = np.nonzero(main)
-    if ci.size == 0:
-        return ci, ri, np.zeros(0, dtype=np.int64)
-    iv = it[ci, ri].astype(np.int64)
-    last = np.r_[ci[1:] != ci[:-1], True]
-    nxt = np.r_[iv[1:], 0]
-    nxt[last] = pool.iter_main
-    w = nxt - iv
-    if selection == 'saved':
-        first = np.r_[True, ci[1:] != ci[:-1]]
-        start = np.maximum.accumulate(np.where(first, np.arange(ci.size), 0))
-        a = iv - iv[start]
-        total = pool.iter_main - iv[start]
-        t = -(-total // int(pool.initparams['maxmodels']))
-        w = -(-(a + w) // t) - (-(-a // t))
-    return ci, ri, w
-
-
-def chain_like_medians(pool):
-    """The median of each chain's thinned main-phase likes, as np.median of the float32 values save() writes gives it
-    -> (chains (local indices of those with main-phase rows, ascending), medians float64)."""
-    ci, ri, cnt = pool_selection(pool, 'saved')
-    if ci.size == 0:
-        return np.zeros(0, dtype=np.int64), np.zeros(0)
-    likes = pool.likes[ci, ri]
-    order = np.lexsort((likes, ci))
-    cs, ls = cnt[order], likes[order]
-    cum = np.cumsum(cs)
-    chains = np.unique(ci)
-    tot = np.bincount(ci, weights=cnt, minlength=pool.nchains).astype(np.int64)[chains]
-    off = np.concatenate(([0], np.cumsum(tot)[:-1]))
-    pick = lambda r: ls[np.searchsorted(cum, off + r, side='right')]
-    lo, hi = pick((tot - 1) // 2), pick(tot // 2)
-    # np.median of float32: the middle value, or the float32 mean of the two middle ones
-    return chains, np.where(tot % 2 == 1, lo, (lo + hi) / np.float32(2)).astype(np.float32).astype(np.float64)
-
-
-_NO_BEST_CHAIN = "best chain median likelihood is 0: outliers are undefined (Plotting.py:136-140)"
-
-
-def pool_outliers(pool, dev=0.05):
-    """PlotFromStorage.get_outliers (Plotting.py:113-154) on the likes save() writes: the median of each
-    chain's thinned main-phase likes against the best chain's -> global chain indices (sorted)."""
-    chains, med = chain_like_medians(pool)
-    if chains.size == 0:
-        return np.zeros(0, dtype=np.int64)
-    maxlike = np.max(med)
-    if maxlike > 0:
-        scores = med / maxlike
-    elif maxlike < 0:
-        scores = maxlike / med
-    else:
-        raise ValueError(_NO_BEST_CHAIN)
-    return (chains[(1 - scores) > dev] + pool.first).astype(np.int64)
-
-
-def pool_rows(pool, selection='weighted', dev=0.05, exclude_outliers=True):
-    """The rows ChainPool.posterior and ChainPool.datafits summarize: pool_selection without the outlier chains
-    -> (ci, ri, w).  ValueError when nothing is left or a weight does not fit the device's int32."""
-    ci, ri, w = pool_selection(pool, selection)
-    if exclude_outliers and ci.size:
-        out = pool_outliers(pool, dev) - pool.first
-        keep = ~np.isin(ci, out)
-        ci, ri, w = ci[keep], ri[keep], w[keep]
-    if ci.size == 0:
-        raise ValueError("empty selection: no main-phase rows")
-    if w.max() > np.iinfo(np.int32).max:
-        raise ValueError("a weight above 2^31 - 1")
-    return ci, ri, w
-
+# ---- the chain pool's own sample block, and every station of a station pool --------------------------------
 
 def pool_posterior(pool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True, selection='weighted', device=None):
     """ChainPool.posterior: summarize() over the pool's main-phase rows (see ChainPool.posterior)."""
-    ci, ri, w = pool_rows(pool, selection, dev, exclude_outliers)
+    ci, ri, w = sel.pool_rows(pool, selection, dev, exclude_outliers)
     if dep_int is None:
         dep_int = models2d_dep_int(pool.priors['z'], depint)
     res = summarize(pool.models[ci, ri], w.astype(np.int32), dep_int=dep_int, device=device)
@@ -493,43 +328,7 @@ def pool_posterior(pool, dep_int=None, depint=1, dev=0.05, exclude_outliers=True
     return res
 
 
-# ---- every station of a station pool ----------------------------------------------------------------------
-
-def station_rows(pool, chains_per_station, selection='weighted', dev=0.05, exclude_outliers=True):
-    """pool_rows of every station of a pool whose chains come in runs of `chains_per_station` per station, without
-    a loop over stations: the selection is pool_selection on all chains, the outlier chains are found per station
-    from chain_like_medians on all chains (each chain's median against the best of its own station).
-    -> (ci, ri, w, set_start [stations + 1], failed {station index: message}): station s owns the rows
-    set_start[s]:set_start[s + 1], there ci - s * chains_per_station, ri, w are pool_rows of the station's view.
-    A station in `failed` (its best chain's median likelihood is 0, or a weight does not fit the device's int32: what
-    pool_rows raises for) has no rows; so has one without main-phase rows."""
-    c = int(chains_per_station)
-    S = pool.nchains // c
-    ci, ri, w = pool_selection(pool, selection)
-    failed = {}
-    if exclude_outliers and ci.size:
-        chains, med = chain_like_medians(pool)
-        st = chains // c
-        best = np.full(S, -np.inf)
-        np.maximum.at(best, st, med)
-        best = best[st]
-        with np.errstate(divide='ignore', invalid='ignore'):
-            scores = np.where(best > 0, med / best, best / med)
-        for s in np.unique(st[best == 0]):
-            failed[int(s)] = _NO_BEST_CHAIN
-        out = chains[(best != 0) & ((1 - scores) > dev)]
-        keep = ~np.isin(ci, out) & ~np.isin(ci // c, np.fromiter(failed, dtype=np.int64, count=len(failed)))
-        ci, ri, w = ci[keep], ri[keep], w[keep]
-    big = w > np.iinfo(np.int32).max
-    if big.any():                                          # pool_rows' refusal, for the stations it would refuse
-        for s in np.unique(ci[big] // c):
-            failed.setdefault(int(s), "a weight above 2^31 - 1")
-        keep = ~np.isin(ci // c, np.unique(ci[big] // c))
-        ci, ri, w = ci[keep], ri[keep], w[keep]
-    return ci, ri, w, np.searchsorted(ci // c, np.arange(S + 1)).astype(np.int64), failed
-
-
-class StationPosterior(object):
+class StationPosterior(sel.StationResult):
     """StationPool.posterior's result.
 
     stations   {station name: the dict pool.station(name).posterior(...) returns}, failed stations left out
@@ -540,9 +339,8 @@ class StationPosterior(object):
                station is a row of NaN"""
 
     def __init__(self, names, results, failed):
-        self.names = list(names)
+        sel.StationResult.__init__(self, names, failed)
         self.stations = {n: r for n, r in zip(names, results) if r is not None}
-        self.failed = {names[z]: msg for z, msg in failed.items()}
         for k, v in results.section().items():
             setattr(self, k, v)
 
@@ -551,13 +349,13 @@ def stations_posterior(spool, dep_int=None, depint=1, dev=0.05, exclude_outliers
                        strict=True):
     """StationPool.posterior: summarize_sets() over every station's main-phase rows (see StationPool.posterior)."""
     pool, c = spool.pool, spool.chains_per_station
-    ci, ri, w, set_start, failed = station_rows(pool, c, selection, dev, exclude_outliers)
+    ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
     if dep_int is None:
         dep_int = models2d_dep_int(pool.priors['z'], depint)
     res = summarize_sets(pool.models[ci, ri], set_start, w.astype(np.int32), dep_int=dep_int, device=device, strict=False)
     res.failed.update(failed)
-    raise_first_failed(res.failed, strict, "station", spool.names)
+    sel.raise_first_failed(res.failed, strict, "station", spool.names)
     for z, r in enumerate(res):
         if r is not None:
-            r['chains'] = np.unique(ci[set_start[z]:set_start[z + 1]]) - z * c
+            r['chains'] = sel.station_chains(ci, set_start, z, c)
     return StationPosterior(spool.names, res, res.failed)

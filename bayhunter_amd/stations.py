@@ -35,7 +35,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .chains import DEFAULT_INITPARAMS, DEFAULT_PRIORS, ChainPool, GpuEvaluator, _CallEvaluator, noise_priors
+from .chains import DEFAULT_INITPARAMS, DEFAULT_PRIORS, ChainPool, GpuEvaluator, CallEvaluator, noise_priors
 
 _COV_NAMES = {_lib.COV_NOCORR: 'NOCORR (no yerr)', _lib.COV_NOCORR_SCALED: 'NOCORR_SCALED (yerr given)',
               _lib.COV_EXP: 'EXP', _lib.COV_GAUSS: 'GAUSS'}
@@ -198,11 +198,11 @@ class StationGpuEvaluator(GpuEvaluator):
         return packed, nlay, noise, chain
 
 
-class StationCallEvaluator(_CallEvaluator):
+class StationCallEvaluator(CallEvaluator):
     """Adapter for a plain function (packed, nlay, noise, station[B]) -> (logL, misfits)."""
 
     def __init__(self, fn, station_of_chain):
-        _CallEvaluator.__init__(self, fn)
+        CallEvaluator.__init__(self, fn)
         self.station_of_chain = np.asarray(station_of_chain, dtype=np.int32)
 
     def submit(self, group, packed, nlay, noise):

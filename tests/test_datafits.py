@@ -103,7 +103,7 @@ def pool(oracle):
 
 def test_pool_best_rows_are_the_saved_argmin(pool, tmp_path):
     from bayhunter_amd.datafits import best_rows
-    from bayhunter_amd.posterior import pool_selection
+    from bayhunter_amd.selection import pool_selection
     pool.save(str(tmp_path))
     ci, ri, w = pool_selection(pool, 'saved')
     pick = best_rows(ci, w, pool.misfits[ci, ri, -1].astype(np.float64))

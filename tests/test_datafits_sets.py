@@ -378,7 +378,7 @@ def _fake_station_pool(rs, S, c, nrows, per_station=()):
 
 def test_station_datafits_assembly_with_a_numpy_matrix():
     from bayhunter_amd.datafits import best_rows, stations_datafits
-    from bayhunter_amd.posterior import station_rows
+    from bayhunter_amd.selection import station_rows
     rs = np.random.RandomState(12)
     S, c, nrows = 4, 3, 9
     sp = _fake_station_pool(rs, S, c, nrows)

@@ -232,7 +232,7 @@ POOL_MOHOVS = 3.6            # low enough that short chains from the prior have 
 
 
 def test_station_pool_moho_equals_every_station_views(station_pool):
-    from bayhunter_amd.posterior import pool_rows
+    from bayhunter_amd.selection import pool_rows
     pool = station_pool
     for kw in (dict(selection='weighted'), dict(selection='saved'), dict(selection='weighted', exclude_outliers=False)):
         res = pool.moho(mohovs=POOL_MOHOVS, dev=0.5, **kw)

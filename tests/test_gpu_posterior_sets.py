@@ -110,19 +110,19 @@ def boundary_case(dtype):
 @pytest.mark.parametrize('dtype', [np.float32, np.float64])
 def test_every_set_equals_summarize_of_its_rows(lib, dtype):
     import torch
-    from bayhunter_amd.posterior import _Grid, _Sets
+    from bayhunter_amd.posterior import Grid, Sets
     k = boundary_case(dtype)
     assert_sets_equal_singles(k['got'], k['want'], len(SIZES))
     # the argmin itself: the single-set argmin plus the set's first row
     dev = torch.device('cuda')
     rows, w, mis = (torch.from_numpy(k[n]).to(dev) for n in ('rows', 'w', 'mis'))
     st = torch.cuda.current_stream().cuda_stream
-    with _Sets(rows, w, mis, k['start'], DEP, None, st) as sets:
+    with Sets(rows, w, mis, k['start'], DEP, None, st) as sets:
         s = sets.scan()
     assert not s['status'].any()
     for z in range(len(SIZES)):
         a, b = int(k['start'][z]), int(k['start'][z + 1])
-        with _Grid(rows[a:b], w[a:b], mis[a:b], DEP, None, st) as one:
+        with Grid(rows[a:b], w[a:b], mis[a:b], DEP, None, st) as one:
             s1 = one.scan()
         assert s['argmin'][z] == s1['argmin'] + a and s['total'][z] == s1['total']
     s513, s257, big = (int(k['start'][i]) for i in (4, 3, 5))
@@ -179,20 +179,20 @@ def test_depth_tiles_wider_than_the_lds_histogram(lib, edge_case):
     the global-atomics path.  (summarize's own grids put two half-step depths into each bin and never get there,
     so the handles are driven directly.)"""
     import torch
-    from bayhunter_amd.posterior import _Grid, _Sets, mode_edges
+    from bayhunter_amd.posterior import Grid, Sets, mode_edges
     rows, w, start = edge_case
     dev = torch.device('cuda')
     trows, tw = torch.from_numpy(rows.astype(np.float32)).to(dev), torch.from_numpy(w).to(dev)
     st = torch.cuda.current_stream().cuda_stream
     dbin = (2 * np.arange(DEP.size)).astype(np.int32)
     dbin[5] = -1
-    with _Sets(trows, tw, None, start, DEP, None, st) as sets:
+    with Sets(trows, tw, None, start, DEP, None, st) as sets:
         s = sets.scan()
         edges = [mode_edges(s['vmin'][z], s['vmax'][z]) for z in range(5)]
         hists, std, med = sets.finish(edges, dbin, 2 * DEP.size, True)
     for z in range(5):
         a, b = int(start[z]), int(start[z + 1])
-        with _Grid(trows[a:b], tw[a:b], None, DEP, None, st) as one:
+        with Grid(trows[a:b], tw[a:b], None, DEP, None, st) as one:
             s1 = one.scan()
             e1 = mode_edges(s1['vmin'], s1['vmax'])
             h1, std1, med1 = one.finish(e1, dbin, 2 * DEP.size, True)
@@ -244,7 +244,7 @@ def test_compact_slab_with_empty_sets_between_multi_block_ones(lib, dtype):
     between multi-block ones inside the slab.  The live sets equal summarize() of their rows, the empty ones fail with
     the scan's words, and the 513-row set's argmin -- planted in its second block -- comes back as that row."""
     import torch
-    from bayhunter_amd.posterior import _Sets, summarize_sets
+    from bayhunter_amd.posterior import Sets, summarize_sets
     rs = np.random.RandomState(80)
     sizes = (0, 1, 257, 0, 513, 256)
     start = np.concatenate(([0], np.cumsum(sizes)))
@@ -270,8 +270,8 @@ def test_compact_slab_with_empty_sets_between_multi_block_ones(lib, dtype):
         assert set(got[z]) == FIELDS and set(got[z]['singlemodels']) == SINGLE
         assert_equal_trees(got[z], want[z], 'set %d' % z)
     dev = torch.device('cuda')
-    with _Sets(torch.from_numpy(rows).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(mis).to(dev), start, DEP,
-               None, torch.cuda.current_stream().cuda_stream, chunk_bytes=budget) as sets:
+    with Sets(torch.from_numpy(rows).to(dev), torch.from_numpy(w).to(dev), torch.from_numpy(mis).to(dev), start, DEP,
+              None, torch.cuda.current_stream().cuda_stream, chunk_bytes=budget) as sets:
         s = sets.scan()
     assert s['status'].tolist() == [1, 0, 0, 1, 0, 0] and s['argmin'][4] == planted
     assert s['argmin'][0] == -1 and s['argmin'][3] == -1 and s['argmin'][1] == 0

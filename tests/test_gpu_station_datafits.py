@@ -56,7 +56,7 @@ def pool(lib):
 
 def test_pooled_forward_rows_equal_the_stations_own(pool):
     from bayhunter_amd.datafits import forward_matrix
-    from bayhunter_amd.posterior import station_rows
+    from bayhunter_amd.selection import station_rows
     from bayhunter_amd.stations import rf_slowness_table
     inner = pool.pool
     ci, ri, w, start, failed = station_rows(inner, C_PER, 'weighted', 0.5, True)
@@ -80,7 +80,7 @@ def test_pooled_forward_rows_equal_the_stations_own(pool):
 
 def test_station_pool_datafits_equals_every_station_view(pool):
     from bayhunter_amd.datafits import station_runs
-    from bayhunter_amd.posterior import station_rows
+    from bayhunter_amd.selection import station_rows
     start = station_rows(pool.pool, C_PER, 'weighted', 0.5, True)[3]
     max_rows = int(np.diff(start).max()) + 1
     assert len(station_runs(start, max_rows)) >= 2

@@ -293,7 +293,7 @@ def pool(oracle):
 
 
 def test_pool_selections_are_the_rows_weighted_and_save_produce(pool, tmp_path):
-    from bayhunter_amd.posterior import pool_selection
+    from bayhunter_amd.selection import pool_selection
     ci, ri, w = pool_selection(pool, 'weighted')
     want = np.concatenate([pool.weighted(i)[2][0] for i in range(pool.nchains) if pool.weighted(i)[2] is not None])
     assert np.array_equal(np.repeat(pool.models[ci, ri].astype(np.float64), w, axis=0), want, equal_nan=True)

@@ -3,7 +3,7 @@ StationPool.posterior):
 
 * the radix select with one list of ranks per column (stats_core.h), compiled with g++ and fed numpy's digit
   histograms, finds the order statistics numpy's sort finds in columns of very different weight totals;
-* the pool-wide selection and outlier step (posterior.station_rows) gives every station the rows pool_rows gives
+* the pool-wide selection and outlier step (selection.station_rows) gives every station the rows pool_rows gives
   its view;
 * the C ABI refuses bad arguments before a device is touched, and no kernel of posterior_sets.hip uses scratch.
 """
@@ -154,7 +154,7 @@ def station_pool(oracle):
 @pytest.mark.parametrize('selection', ['weighted', 'saved'])
 @pytest.mark.parametrize('dev,exclude', [(0.05, True), (0.0005, True), (0.05, False)])
 def test_station_rows_are_pool_rows_of_every_view(station_pool, selection, dev, exclude):
-    from bayhunter_amd.posterior import pool_outliers, pool_rows, station_rows
+    from bayhunter_amd.selection import pool_outliers, pool_rows, station_rows
     pool, c = station_pool, station_pool.chains_per_station
     ci, ri, w, start, failed = station_rows(pool.pool, c, selection, dev, exclude)
     assert not failed and start.size == 4 and start[0] == 0 and start[-1] == ci.size
@@ -172,7 +172,7 @@ def test_station_rows_are_pool_rows_of_every_view(station_pool, selection, dev, 
 def test_station_rows_fail_the_stations_pool_rows_refuses(station_pool):
     """A weight above int32 (here: every chain's last row, with a main phase declared 2^40 iterations long) is
     pool_rows' ValueError for the station's view and an entry of `failed` for that station, not an error of the call."""
-    from bayhunter_amd.posterior import pool_rows, station_rows
+    from bayhunter_amd.selection import pool_rows, station_rows
     inner = station_pool.pool
     keep = inner.iter_main
     inner.iter_main = 2 ** 40

@@ -52,7 +52,7 @@ def main():
     import torch
     import bayhunter_amd
     from bayhunter_amd import _lib
-    from bayhunter_amd.datafits import DEFAULT_Q, _Fits, forward_matrix, percentile_ranks, summarize
+    from bayhunter_amd.datafits import DEFAULT_Q, Fits, forward_matrix, percentile_ranks, summarize
     bayhunter_amd.build()
     rs = np.random.RandomState(1)
     joint = joint10(rs)
@@ -71,7 +71,7 @@ def main():
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             st = torch.cuda.current_stream().cuda_stream
-            f = _Fits(Y, eng.ncols, dw, err, st)
+            f = Fits(Y, eng.ncols, dw, err, st)
             s = f.scan()
             virt, lo, hi = percentile_ranks(DEFAULT_Q, s['total'])
             ranks = np.unique(np.r_[lo, hi, (s['total'] - 1) // 2, s['total'] // 2])
