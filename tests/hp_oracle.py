@@ -32,6 +32,28 @@ def _build():
     return C.CDLL(so)
 
 
+def rf_model_q_ld(h, vp, vs, rho, qp, qs, p, gauss, nsamp, fsamp, tshift, nsv, waveno, nout):
+    """One model with its own Q per layer through the long-double oracle's synrf entry (rf_model_ld fixes Q at 500 and
+    225, as the batch entry of the fp64 oracle does); depths, Poisson's ratio and nsv as rf_model_ld forms them, in long
+    double.  Returns the first nout samples as np.longdouble."""
+    global _lib
+    if _lib is None:
+        _lib = _build()
+    ld = np.longdouble
+    a = [np.ascontiguousarray(x, dtype=ld) for x in (h, vp, vs, rho, qp, qs)]
+    z = np.ascontiguousarray(np.concatenate(([ld(0)], np.cumsum(a[0])[:-1])), dtype=ld)
+    vpvs = a[1][0] / a[2][0]
+    sigma = (ld(2) - vpvs * vpvs) / (ld(2) - ld(2) * (vpvs * vpvs))
+    out = np.zeros(int(nsamp), dtype=ld)
+    ptr = lambda x: x.ctypes.data_as(C.c_void_p)
+    f = _lib.bhol_synrf
+    f.restype = C.c_int
+    f.argtypes = [C.c_int] + [C.c_longdouble] * 6 + [C.c_int, C.c_int] + [C.c_void_p] * 9
+    f(int(nsamp), ld(fsamp), ld(tshift), ld(p), ld(gauss), a[2][0] if nsv is None else ld(nsv), sigma, int(waveno),
+      a[0].size, ptr(z), ptr(a[1]), ptr(a[2]), ptr(a[3]), ptr(a[4]), ptr(a[5]), None, None, ptr(out))
+    return out[:nout]
+
+
 def rf_model_ld(h, vp, vs, rho, p, gauss, nsamp, fsamp, tshift, nsv, waveno, nout):
     """One model through the long-double oracle; returns the first nout samples as np.longdouble."""
     global _lib
