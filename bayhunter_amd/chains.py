@@ -578,6 +578,22 @@ class ChainPool(object):
         from .moho import pool_moho
         return pool_moho(self, moho, mohovs, selection, dev, exclude_outliers, nbins, device)
 
+    def scalars(self, selection='weighted', dev=0.05, exclude_outliers=True, nbins=20, pairs=(), pair_bins=50, moho=None,
+                mohovs=4.2, by_chain=False, device=None):
+        """The posterior of the sampler's scalar parameters over the rows posterior() uses (scalars.summarize; the
+        reference's plot_posterior_likes / _misfits / _vpvs / _noise / _nlayers / _others, src/Plotting.py:552-710,
+        without the figures): per column of scalars.NAMES -- like, misfit:<ref>, misfit:joint, vpvs, corr:<ref>,
+        sigma:<ref>, nlayers -- median, mean, std, min, max, the histogram of `nbins` bins and its mode, each in the
+        dtype save() writes the column in; per pair of `pairs` (column names, e.g. ('nlayers', 'like')) the joint
+        histogram of pair_bins x pair_bins cells with its mode.  moho = (zlo, zhi) adds the column 'moho' (the Moho
+        depth of moho(), NaN for a model without one) for pairs such as ('moho', 'vpvs'), with nmodels_moho /
+        nexcluded_moho.  -> summarize()'s dict plus 'chains' (global indices used).  by_chain=True: one set per
+        chain in one pass -> a list with that dict per chain of the pool, None for a chain without rows (left out as an
+        outlier, or nothing accepted after the burn-in; `failed` {chain: message}), and `chains`; with
+        selection='saved' chain i's entry is what the reference computes from the files save() writes for it."""
+        from .scalars import pool_scalars
+        return pool_scalars(self, selection, dev, exclude_outliers, nbins, pairs, pair_bins, moho, mohovs, by_chain, device)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

@@ -101,24 +101,61 @@ def summarize(models, weights=None, moho=(0., 100.), mohovs=4.2, nbins=50, devic
     return res
 
 
-def summarize_sets(models, set_start, weights=None, moho=(0., 100.), mohovs=4.2, nbins=50, device=None):
+def _tradeoff_sets(D, w, set_start, vmin, vmax, nbins, stream):
+    """summarize()'s `tradeoff` of every set over D = derive()'s matrix: the x columns of TRADEOFF against the Moho
+    depth over each set's own outer_edges (vmin, vmax [sets, 4]: NaN for a set without a Moho), one bh_hist2d_sets
+    launch -> {name: dict(counts [sets, nbins, nbins], xedges, yedges [sets, nbins + 1], mode [sets, 2])}."""
+    S = set_start.size - 1
+    has = ~np.isnan(vmin[:, 0])
+    edges = np.zeros((S, 4, nbins + 1))
+    edges[:] = np.arange(nbins + 1)                     # (a set without a Moho adds nothing: anything ascending)
+    for z in np.nonzero(has)[0]:
+        edges[z] = [outer_edges(vmin[z, c], vmax[z, c], nbins) for c in range(4)]
+    pairs = np.array([(_COL[n], 0) for n in TRADEOFF], dtype=np.int32)
+    h2 = np.zeros((S, 3, nbins, nbins), dtype=np.int64)
+    _lib.check(_lib.load().bh_hist2d_sets(D.data_ptr(), D.shape[0], D.stride(0), 4, None if w is None else w.data_ptr(),
+                                          set_start.ctypes.data, S, pairs.ctypes.data, 3, edges.ctypes.data, nbins + 1,
+                                          h2.ctypes.data, stream))
+    edges[~has] = np.nan
+    yc = (edges[:, 0, :-1] + edges[:, 0, 1:]) / 2.
+    out = {}
+    for i, name in enumerate(TRADEOFF):
+        xe = edges[:, _COL[name]]
+        xc = (xe[:, :-1] + xe[:, 1:]) / 2.
+        xi, yi = np.unravel_index(h2[:, i].reshape(S, -1).argmax(axis=1), (nbins, nbins))
+        out[name] = dict(counts=h2[:, i].copy(), xedges=xe.copy(), yedges=edges[:, 0].copy(),
+                         mode=np.stack((xc[np.arange(S), xi], yc[np.arange(S), yi]), axis=1))
+    return out
+
+
+def summarize_sets(models, set_start, weights=None, moho=(0., 100.), mohovs=4.2, nbins=50, device=None, tradeoff=False):
     """summarize()'s numbers for every set of rows in one pass: set s is models[set_start[s]:set_start[s + 1]]
     (set_start [sets + 1], ascending from 0 to the number of rows; a set may be empty).  One derivation launch and one
     launch for the statistics of all sets.
 
     -> dict(nmodels, nexcluded [sets] (weighted rows with / without a Moho), fraction [sets] (nmodels over both; NaN for
             a set without weight), moho, vs_crust, vs_last, vs_jump = dict(median, mean, std, min, max [sets]) each,
-            hist [sets, nbins] of the Moho depth over the shared `edges` = linspace(zlo, zhi, nbins + 1)).
-    A set without a row that has a Moho is no error: nmodels 0, its statistics NaN, its histogram empty.  A negative
-    weight fails the call."""
+            hist [sets, nbins] of the Moho depth over the shared `edges` = linspace(zlo, zhi, nbins + 1));
+            with tradeoff=True also tradeoff = {vs_last, vs_crust, vs_jump: dict(counts [sets, nbins, nbins], xedges,
+            yedges [sets, nbins + 1], mode [sets, 2])}: summarize()'s three joint histograms of every set over the set's
+            own edges, from one more launch (bh_hist2d_sets, nbins <= 64).
+    A set without a row that has a Moho is no error: nmodels 0, its statistics NaN, its histogram empty (the edges and
+    modes of its trade-off NaN).  A negative weight fails the call."""
     import torch
     zlo, zhi, mohovs, nbins = _window(moho, mohovs, nbins)
+    if tradeoff and nbins > _lib.PAIRS_MAX_EDGES - 1:
+        raise ValueError("tradeoff: nbins <= %d" % (_lib.PAIRS_MAX_EDGES - 1))
     dev, rows, w, _ = _device.device_rows(models, weights, per_row="one weight per row", device=device)
     set_start, S = sel.check_set_start(set_start, rows.shape[0])
     edges = np.linspace(zlo, zhi, nbins + 1)
     cnt, nex = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int64)
     st = {k: np.full((S, 4), np.nan) for k in ('min', 'max', 'mean', 'std', 'lo', 'hi')}
     hist = np.zeros((S, nbins), dtype=np.int64)
+    trade = None
+    if tradeoff and not rows.shape[0]:
+        nan = lambda *shape: np.full(shape, np.nan)
+        trade = {n: dict(counts=np.zeros((S, nbins, nbins), dtype=np.int64), xedges=nan(S, nbins + 1),
+                         yedges=nan(S, nbins + 1), mode=nan(S, 2)) for n in TRADEOFF}
     if rows.shape[0]:
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
@@ -128,6 +165,8 @@ def summarize_sets(models, set_start, weights=None, moho=(0., 100.), mohovs=4.2,
                 edges.ctypes.data, nbins + 1, cnt.ctypes.data, nex.ctypes.data, st['min'].ctypes.data,
                 st['max'].ctypes.data, st['mean'].ctypes.data, st['std'].ctypes.data, st['lo'].ctypes.data,
                 st['hi'].ctypes.data, hist.ctypes.data, stream))
+            if tradeoff:
+                trade = _tradeoff_sets(D, w, set_start, st['min'], st['max'], nbins, stream)
     median = (st['lo'] + st['hi']) / 2.
     with np.errstate(invalid='ignore', divide='ignore'):
         fraction = np.where(cnt + nex > 0, cnt / (cnt + nex).astype(np.float64), np.nan)
@@ -135,6 +174,8 @@ def summarize_sets(models, set_start, weights=None, moho=(0., 100.), mohovs=4.2,
     for c, name in enumerate(NAMES):
         res[name] = dict(median=median[:, c].copy(), mean=st['mean'][:, c].copy(), std=st['std'][:, c].copy(),
                          min=st['min'][:, c].copy(), max=st['max'][:, c].copy())
+    if tradeoff:
+        res['tradeoff'] = trade
     return res
 
 
@@ -164,6 +205,8 @@ class StationMoho(sel.StationResult):
     nmodels, nexcluded [nstations]     weighted rows with / without a Moho
     fraction [nstations]               nmodels / (nmodels + nexcluded)
     hist [nstations, nbins], edges     the Moho depth over edges all stations share: linspace(zlo, zhi, nbins + 1)
+    tradeoff   with tradeoff=True only: {vs_last, vs_crust, vs_jump: dict(counts [nstations, nbins, nbins], xedges, yedges
+               [nstations, nbins + 1], mode [nstations, 2])}, every station over its own edges
     failed     {station name: message}, as StationPool.posterior reports it (such a station has no rows)"""
 
     def __init__(self, names, res, failed):
@@ -173,10 +216,10 @@ class StationMoho(sel.StationResult):
 
 
 def stations_moho(spool, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50,
-                  device=None):
+                  device=None, tradeoff=False):
     """StationPool.moho: summarize_sets() over every station's main-phase rows."""
     pool, c = spool.pool, spool.chains_per_station
     ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
     res = summarize_sets(_widened(pool.models[ci, ri], device), set_start, w.astype(np.int32),
-                         pool.priors['z'] if moho is None else moho, mohovs, nbins, device)
+                         pool.priors['z'] if moho is None else moho, mohovs, nbins, device, tradeoff)
     return StationMoho(spool.names, res, failed)

@@ -222,7 +222,7 @@ def _takes_station(fn):
 class StationView(ChainPool):
     """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
     noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
-    datafits(), moho(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
+    datafits(), moho(), scalars(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
 
     def __init__(self, pool, s):
         inner, c = pool.pool, pool.chains_per_station
@@ -439,15 +439,37 @@ class StationPool(object):
         from .datafits import stations_datafits
         return stations_datafits(self, selection, dev, exclude_outliers, q, nbins, device, strict, max_rows)
 
-    def moho(self, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50, device=None):
+    def moho(self, moho=None, mohovs=4.2, selection='weighted', dev=0.05, exclude_outliers=True, nbins=50, device=None,
+             tradeoff=False):
         """Moho depth +- std, crustal Vs and the share of models with a Moho of every station in one pass over the
         pool's rows (moho.summarize_sets: one launch derives every row, one reduces all stations): per station the
         numbers station(s).moho(...) reports.  -> moho.StationMoho: `names`, `moho / vs_crust / vs_last / vs_jump`
         = dict(median, mean, std, min, max [nstations]), `nmodels`, `nexcluded`, `fraction [nstations]`, `hist
         [nstations, nbins]` of the Moho depth over the shared `edges`, `failed` {name: message}.  A station without a
-        model that has a Moho is a hole of the map (NaN, nmodels 0), not an error."""
+        model that has a Moho is a hole of the map (NaN, nmodels 0), not an error.
+        tradeoff=True adds `tradeoff` = {vs_last, vs_crust, vs_jump: dict(counts [nstations, nbins, nbins], xedges,
+        yedges [nstations, nbins + 1], mode [nstations, 2])}: per station the three joint histograms against the Moho
+        depth that station(s).moho()['tradeoff'] holds, bit for bit, over the station's own edges, from one more
+        launch (bh_hist2d_sets; nbins <= 64); NaN edges and mode for a hole of the map."""
         from .moho import stations_moho
-        return stations_moho(self, moho, mohovs, selection, dev, exclude_outliers, nbins, device)
+        return stations_moho(self, moho, mohovs, selection, dev, exclude_outliers, nbins, device, tradeoff)
+
+    def scalars(self, selection='weighted', dev=0.05, exclude_outliers=True, nbins=20, pairs=(), pair_bins=50, moho=None,
+                mohovs=4.2, device=None, strict=False, max_rows=None):
+        """The posterior of the sampler's scalar parameters of every station in one pass over the pool's rows
+        (scalars.summarize_sets: one segmented reduction and one bh_hist2d_sets launch for all stations): "the sigma of
+        the receiver-function noise at every station", "the crustal Vp/Vs map".  Arguments as station(s).scalars(...);
+        per station every field is bit for bit what that returns ('chains' numbered within the station).
+        -> scalars.StationScalars: `names`, `stations[name]` those dicts, `failed` {name: message}, `columns`,
+        `nmodels / nexcluded [nstations]`, `stats[column]` = dict(median, mean, std, min, max, mode, constant
+        [nstations], hist [nstations, nbins], edges [nstations, nbins + 1]), `pairs[(x, y)]` = dict(counts [nstations,
+        pair_bins, pair_bins], xedges, yedges, mode [nstations, 2]); NaN for a failed station or one without rows.
+        strict=True: such a station is a ValueError naming the first one.  max_rows: the stations are taken in runs of
+        whole stations of at most that many rows (default: what half of the free device memory holds); no result
+        depends on it."""
+        from .scalars import stations_scalars
+        return stations_scalars(self, selection, dev, exclude_outliers, nbins, pairs, pair_bins, moho, mohovs, device,
+                                strict, max_rows)
 
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone

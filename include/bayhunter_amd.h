@@ -760,6 +760,35 @@ int  bh_moho_sets(const double *D, long long nrows, const int *weights, const lo
                   double *vmax, double *mean, double *stdev, double *medlo, double *medhi, long long *hist,
                   void *stream);
 
+/* ---- joint histograms of column pairs for many sets of rows ------------------------------- */
+/* The two-parameter views of a sampler's scalars (Moho depth against Vp/Vs, the sigma of one target against another's,
+ * layer count against likelihood), for every station of a network in one launch: what np.histogram2d(x, y,
+ * bins=(xedges, yedges)) counts per set and pair, over rows that each carry an integer weight.
+ *
+ * D          DEVICE float64 [nrows][stride], the first ncols columns used; 1 <= nrows <= 2^32
+ * weights    DEVICE int32 [nrows] >= 0, or NULL for all ones.  A negative weight anywhere is BH_ERR_ARG
+ * set_start  HOST [nsets + 1] as for bh_moho_sets: set s is rows set_start[s] .. set_start[s + 1], a set may be empty;
+ *            1 <= nsets <= BH_PAIRS_MAX_SETS
+ * pairs      HOST [npairs][2] = (x column, y column), 0 <= column < ncols, x == y allowed; 1 <= npairs <= BH_PAIRS_MAX
+ * edges      HOST [nsets][ncols][nedges], 2 <= nedges <= BH_PAIRS_MAX_EDGES: every set its own edges per column.  The
+ *            edges of every column a pair names must be ascending in every set; those of the other columns are not read
+ * hist       HOST [nsets][npairs][nb][nb], nb = nedges - 1, the x bin first, 64-bit counts
+ *
+ * A row of set s adds its weight to cell (bx, by) of pair (cx, cy): bx the bin of D[row][cx] in edges[s][cx], by
+ * that of D[row][cy] in edges[s][cy], by numpy's rule as in bh_datafits_finish (e[i] <= v < e[i+1], the last bin
+ * closed).  A row is skipped for a pair when either of the pair's two values is a NaN or outside its edges, or when
+ * its weight is 0: for that pair only.  Weights are accumulated in 64 bits everywhere.
+ * One block of the kernel covers all pairs of (a stretch of) one set; when the cell tables of all pairs do not fit
+ * its 64 KiB of LDS beside the edges it takes the pairs in groups and reads its rows once per group.  The counts are
+ * integer sums: two runs are bit-identical, and nothing depends on how pairs are grouped or sets are split over blocks.
+ * All arguments are checked before any device is touched; hist is there when the call returns. */
+#define BH_PAIRS_MAX       16
+#define BH_PAIRS_MAX_EDGES 65
+#define BH_PAIRS_MAX_SETS  65535
+int  bh_hist2d_sets(const double *D, long long nrows, long long stride, int ncols, const int *weights,
+                    const long long *set_start, int nsets, const int *pairs, int npairs, const double *edges,
+                    int nedges, long long *hist, void *stream);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);

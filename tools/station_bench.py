@@ -9,7 +9,8 @@ vp/vs and noise, like tools/chain_bench.py).  For S stations of c chains each, t
                the output: "scaled": true)
 
     python tools/station_bench.py [--modes stations,onepool,singles] [--repeats 5] [--sample 16] [--root DIR]
-                                  [--vary-p LO HI] [--gaps FRACTION] [--posterior | --datafits] [--out FILE.jsonl] [SxC ...]
+                                  [--vary-p LO HI] [--gaps FRACTION] [--posterior | --datafits | --scalars] [--out FILE.jsonl]
+                                  [SxC ...]
                                   (default 64x16 256x16 1024x16 1024x4)
 
 --vary-p LO HI: every station its own receiver-function ray parameter, spread evenly over [LO, HI] s/deg; the station
@@ -31,6 +32,11 @@ before a time is reported.  One JSON line per S x c.
 --datafits: the same for the statistics of the modelled data: the loop over pool.station(s).datafits() (one forward
 pass and one bh_datafits handle per station) against StationPool.datafits() (one forward pass and one bh_datafits_sets
 handle for all stations); with --vary-p the pool has per_station=('p',).
+
+--scalars: the same for the posterior of the sampler's scalar parameters: the loop over pool.station(s).scalars() (one
+bh_datafits handle and one bh_hist2d_sets call per station) against StationPool.scalars() (one bh_datafits_sets handle
+and one bh_hist2d_sets launch for all stations), both with the Moho column and the pairs (moho, vpvs), (sigma of the
+second target, sigma of the first) and (nlayers, like).
 
 A warm-up pool of every mode runs first; then `--repeats` rounds, each round running every mode once (alternating,
 so that a drift of the box hits all modes alike).  One JSON line per (S, c, mode) with every repeat's seconds,
@@ -61,11 +67,13 @@ def main():
                     help='time StationPool.posterior() against the loop over station views on one finished pool')
     ap.add_argument('--datafits', action='store_true',
                     help='time StationPool.datafits() against the loop over station views on one finished pool')
+    ap.add_argument('--scalars', action='store_true',
+                    help='time StationPool.scalars() against the loop over station views on one finished pool')
     ap.add_argument('--tag', default=None)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if not args.configs:
-        args.configs = ['64x16', '256x16', '1024x16'] + ([] if args.posterior or args.datafits else ['1024x4'])
+        args.configs = ['64x16', '256x16', '1024x16'] + ([] if args.posterior or args.datafits or args.scalars else ['1024x4'])
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     root = os.path.abspath(args.root) if args.root else here
     sys.path.insert(0, os.path.join(here, 'tests', 'scenarios'))
@@ -135,7 +143,7 @@ def main():
             assert np.array_equal(x, y, equal_nan=x.dtype.kind in 'fc'), path
 
     def readout_leg(what, S, c, iters, stations):
-        """what: 'posterior' or 'datafits' -- the method of the station views and of the pool"""
+        """what: 'posterior', 'datafits' or 'scalars' -- the method of the station views and of the pool"""
         import torch
         from bayhunter_amd.stations import StationPool
         per = dict(per_station=('p',)) if args.vary_p else {}
@@ -143,11 +151,17 @@ def main():
                          **per) as pool:
             pool.run()
 
+        kw = {}
+        if what == 'scalars':
+            refs = [t.ref for t in stations[0].targets]
+            kw = dict(moho=case['priors']['z'], pairs=[('moho', 'vpvs'), ('sigma:%s' % refs[1], 'sigma:%s' % refs[0]),
+                                                       ('nlayers', 'like')])
+
         def loop():
             out, failed = {}, {}
             for name in pool.names:
                 try:
-                    out[name] = getattr(pool.station(name), what)()
+                    out[name] = getattr(pool.station(name), what)(**kw)
                 except (ValueError, bayhunter_amd._lib.BayHunterAmdError) as e:
                     failed[name] = str(e)
             return out, failed
@@ -159,7 +173,7 @@ def main():
             torch.cuda.synchronize()
             return time.perf_counter() - t0, r
 
-        one = lambda: getattr(pool, what)(strict=False)
+        one = lambda: getattr(pool, what)(strict=False, **kw)
         (_, (want, wfailed)), (_, got) = timed(loop), timed(one)       # warm
         assert sorted(got.failed) == sorted(wfailed) and list(got.stations) == list(want), (got.failed, wfailed)
         same(got.stations, want)
@@ -182,8 +196,9 @@ def main():
         if args.vary_p:
             for joint, p in zip(stations, np.linspace(args.vary_p[0], args.vary_p[1], S)):
                 joint.targets[1].moddata.plugin.set_modelparams(p=float(p))
-        if args.posterior or args.datafits:
-            line = json.dumps(readout_leg('posterior' if args.posterior else 'datafits', S, c, iters, stations))
+        if args.posterior or args.datafits or args.scalars:
+            line = json.dumps(readout_leg('posterior' if args.posterior else 'datafits' if args.datafits else 'scalars',
+                                          S, c, iters, stations))
             print(line, flush=True)
             if args.out:
                 with open(args.out, 'a') as fh:
