@@ -594,6 +594,21 @@ class ChainPool(object):
         from .scalars import pool_scalars
         return pool_scalars(self, selection, dev, exclude_outliers, nbins, pairs, pair_bins, moho, mohovs, by_chain, device)
 
+    def convergence(self, nlags=1024, depths=(), dev=0.05, exclude_outliers=True, rhat_max=1.01, ess_min=None,
+                    device=None):
+        """Has the sample converged: split R-hat and the effective sample size of every scalar column (scalars.NAMES
+        without moho) and of Vs at each depth of `depths` (columns 'vs@<z>'), over the chains posterior() uses
+        (convergence.py).  The chains' common main-phase window -- from the latest first acceptance among them to
+        iter_main -- is split in two; every half chain is the series in which a row is repeated once per iteration it
+        stayed current.  -> dict(<column>: dict(rhat, ess, tau (integrated autocorrelation time, Geyer's initial monotone
+        sequence over `nlags` lags), truncated (no negative pair of autocorrelations within nlags: tau is a lower bound,
+        ess an upper one), constant, mean, W, B, var_plus, acf [nlags], tau_chain, ess_chain [chains], converged (rhat <=
+        rhat_max and ess >= ess_min and not truncated; ess_min defaults to 100 per chain)), n (samples of a half
+        chain), nseries, chains (global indices used), window (first, one past the last main-phase iteration),
+        first_iter [chains]).  ValueError when no chain is left or the window has fewer than 8 iterations."""
+        from .convergence import pool_convergence
+        return pool_convergence(self, nlags, depths, dev, exclude_outliers, rhat_max, ess_min, device)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

@@ -158,3 +158,68 @@ def station_rows(pool, chains_per_station, selection='weighted', dev=0.05, exclu
 def station_chains(ci, set_start, z, chains_per_station):
     """The chains station z's rows come from, as indices into the station's own view (station_rows' ci, set_start)."""
     return np.unique(ci[set_start[z]:set_start[z + 1]]) - z * chains_per_station
+
+
+# ---- the order of a chain's rows: half chains for the convergence diagnostics ------------------------------
+
+def half_chain_series(pool, chains_per_group, dev=0.05, exclude_outliers=True):
+    """The two half chains of every chain, group by group (a group: `chains_per_group` consecutive chains -- the whole
+    pool, or one station), as run-length coded series for split R-hat and the effective sample size.
+
+    Per group the chains are the ones station_rows takes with selection='weighted' (those of pool_rows for a group
+    that is the whole pool).  Their common window is [t0, iter_main), t0 the latest first main-phase iteration among
+    them: a chain that accepts late shortens its group's window.  With n = (iter_main - t0) // 2 the half windows are
+    [iter_main - 2n, iter_main - n) and [iter_main - n, iter_main); a row enters a half with the iterations it spends
+    inside it, so a row that straddles the boundary is in both halves with its share of the weight, and one that begins
+    before the window is clipped.  Every series then has exactly n samples.
+
+    -> dict(ci, ri, w [entries] (int64; the series one after the other: chain by chain, first half then second half),
+            series_start [series + 1] (entries), group_start [groups + 1] (series), chains [series / 2] (the chain of
+            each pair of series, a pool-local index), n [groups], window [groups, 2] = (iter_main - 2n, iter_main)
+            (-1 for a failed group), first_iter [nchains] (the first main-phase iteration of every chain that has series;
+            -1 for the others: no main-phase row, left out as an outlier, or of a group station_rows failed),
+            failed {group: message}).
+    A group in `failed` -- station_rows' reasons, no chain left, or n < 4 -- has no entries."""
+    c = int(chains_per_group)
+    G = pool.nchains // c
+    ci, ri, w, set_start, failed = station_rows(pool, c, 'weighted', dev, exclude_outliers)
+    failed = dict(failed)
+    iv = pool.iter[ci, ri].astype(np.int64)
+    first = np.r_[True, ci[1:] != ci[:-1]] if ci.size else np.zeros(0, dtype=bool)
+    first_iter = np.full(pool.nchains, -1, dtype=np.int64)
+    first_iter[ci[first]] = iv[first]
+    n = np.zeros(G, dtype=np.int64)
+    window = np.full((G, 2), -1, dtype=np.int64)
+    end = int(pool.iter_main)
+    for g in range(G):
+        if g in failed:
+            continue
+        used = np.unique(ci[set_start[g]:set_start[g + 1]])
+        if used.size == 0:
+            failed[g] = "empty selection: no main-phase rows"
+            continue
+        n[g] = (end - int(first_iter[used].max())) // 2
+        if n[g] < 4:
+            n[g] = 0
+            failed[g] = "the chains' common window has fewer than 8 iterations"
+            continue
+        window[g] = (end - 2 * n[g], end)
+    ng = n[ci // c] if ci.size else np.zeros(0, dtype=np.int64)
+    parts = []
+    for half in (0, 1):
+        lo, hi = end - (2 - half) * ng, end - (1 - half) * ng
+        wh = np.minimum(iv + w, hi) - np.maximum(iv, lo)
+        keep = np.nonzero((wh > 0) & (ng > 0))[0]
+        parts.append((keep, np.full(keep.size, half, dtype=np.int64), wh[keep]))
+    pos = np.concatenate([p[0] for p in parts])
+    half = np.concatenate([p[1] for p in parts])
+    wh = np.concatenate([p[2] for p in parts])
+    order = np.lexsort((pos, half, ci[pos]))
+    pos, half, wh = pos[order], half[order], wh[order]
+    key = 2 * ci[pos] + half                                   # ascending: one value per series
+    chains = np.unique(ci[pos])
+    series_start = np.searchsorted(key, np.repeat(2 * chains, 2) + np.tile([0, 1], chains.size)).astype(np.int64)
+    series_start = np.concatenate((series_start, [pos.size])).astype(np.int64)
+    group_start = (2 * np.searchsorted(chains // c, np.arange(G + 1))).astype(np.int64)
+    return dict(ci=ci[pos], ri=ri[pos], w=wh.astype(np.int64), series_start=series_start, group_start=group_start,
+                chains=chains, n=n, window=window, first_iter=first_iter, failed=failed)

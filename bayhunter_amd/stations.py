@@ -222,7 +222,7 @@ def _takes_station(fn):
 class StationView(ChainPool):
     """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
     noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
-    datafits(), moho(), scalars(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
+    datafits(), moho(), scalars(), convergence(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
 
     def __init__(self, pool, s):
         inner, c = pool.pool, pool.chains_per_station
@@ -470,6 +470,19 @@ class StationPool(object):
         from .scalars import stations_scalars
         return stations_scalars(self, selection, dev, exclude_outliers, nbins, pairs, pair_bins, moho, mohovs, device,
                                 strict, max_rows)
+
+    def convergence(self, nlags=1024, depths=(), dev=0.05, exclude_outliers=True, rhat_max=1.01, ess_min=None,
+                    device=None, strict=True, max_rows=None):
+        """Which stations have converged: split R-hat and the effective sample size of every station in one pass
+        (convergence.py): every station a group of half chains, one segmented reduction and one bh_autocov_sets launch
+        per run of whole stations.  Arguments as station(s).convergence(...); per station every field is bit for bit
+        what that returns.  -> convergence.StationConvergence: `names`, `stations[name]` those dicts, `failed` {name:
+        message}, `columns`, `rhat / ess / tau / truncated / converged` {column: [nstations]} (NaN for a failed station)
+        and `window [nstations, 2]`.  strict=True: a failed station is a ValueError naming the first one.  max_rows: runs
+        of whole stations of at most that many entries; no result depends on it."""
+        from .convergence import stations_convergence
+        return stations_convergence(self, nlags, depths, dev, exclude_outliers, rhat_max, ess_min, device, strict,
+                                    max_rows)
 
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone

@@ -789,6 +789,35 @@ int  bh_hist2d_sets(const double *D, long long nrows, long long stride, int ncol
                     const long long *set_start, int nsets, const int *pairs, int npairs, const double *edges,
                     int nedges, long long *hist, void *stream);
 
+/* ---- autocovariances of many run-length coded series --------------------------------------- */
+/* What the convergence diagnostics (split R-hat, effective sample size) need of a chain's ORDER: per series -- a half
+ * chain -- and column the autocovariance at lags 0 .. nlags - 1 of the series in which every row is repeated `weight`
+ * times (a row stays the chain's state for `weight` iterations).
+ *
+ * D             DEVICE float64 [nrows][stride], the first ncols columns used; 1 <= nrows <= 2^32
+ * weights       DEVICE int32 [nrows] >= 0, or NULL for all ones; 0: the row is absent.  A negative weight anywhere is
+ *               BH_ERR_ARG
+ * series_start  HOST [nseries + 1], ascending from 0 to nrows: series s is rows series_start[s] .. series_start[s + 1],
+ *               a series may be empty
+ * mean          HOST [nseries][ncols]: what is subtracted from every sample of the series' column
+ * nlags         1 .. BH_AUTOCOV_MAX_LAGS
+ * acov          HOST [nseries][ncols][nlags]
+ * length        HOST [nseries]: n_s, the sum of the series' weights
+ *
+ * With x_0 .. x_{n-1} the expanded column of a series and y_t = x_t - mean[s][c] (one rounded subtraction) the result
+ * is defined exactly:
+ *     acov[s][c][k] = acc / (double)n,  acc = 0.0; for t = 0 .. n-k-1 ascending: acc = fma(y_t, y_{t+k}, acc)
+ * one accumulator per (series, column, lag); 0 for k >= n and for n = 0.  A NaN in a column reaches the lags whose
+ * chain reads it (all of them when the mean is NaN) and no other column.  The value does not depend on the grid, the
+ * tile length or how lags and columns are dealt to threads: two runs are bit-identical, and so is the host build of
+ * csrc/autocov_core.h.  One workgroup per (series, column, 2048 lags) keeps a tile of 2048 samples and a halo of nlags
+ * in at most 48 KiB of LDS.  All arguments are checked before any device is touched; acov and length are there when the
+ * call returns. */
+#define BH_AUTOCOV_MAX_LAGS 4096
+int  bh_autocov_sets(const double *D, long long nrows, long long stride, int ncols, const int *weights,
+                     const long long *series_start, int nseries, const double *mean, int nlags, double *acov,
+                     long long *length, void *stream);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
