@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "swd_launch.hip", "rf_capi.hip", "like_capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
-           "posterior_sets.hip", "datafits.hip", "datafits_sets.hip", "moho.hip", "pairs.hip", "autocov.hip", "math_probe.hip", "rf_probe.hip"]
+           "datafits.hip", "moho.hip", "pairs.hip", "autocov.hip", "math_probe.hip", "rf_probe.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
            "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h"]

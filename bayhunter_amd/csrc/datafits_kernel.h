@@ -1,8 +1,8 @@
-// datafits_kernel.h -- what a block of the data-fit kernels does with a range of rows: the body of df_kernel
-// (datafits.hip: one set, all rows) and of df_sets_kernel (datafits_sets.hip: one set per block, its own range of
-// the rows), and the row test of their mask kernels.  Both kernels hand df_block the rows [r0, r1), the block's
-// place `bx` among the `G` blocks that share them, and arguments whose output pointers are the set's own; what a
-// set's block adds up, and in which order, therefore does not depend on which of the two kernels runs it.
+// datafits_kernel.h -- what a block of the data-fit kernels does with a range of rows: the body of df_sets_kernel
+// (datafits.hip: one set per block, its own range of the rows; a bh_datafits handle is the single set of all rows),
+// and the row test of the mask kernel.  The kernel hands df_block the rows [r0, r1), the block's place `bx` among the
+// `G` blocks that share them, and arguments whose output pointers are the set's own; what a set's block adds up, and
+// in which order, therefore depends on the set's rows alone.
 //
 // The part above BH_HOSTSIM's #ifndef needs no device (the launch geometry and the chunk plan of the sets):
 // tests/hostsim/datafits_sets_sim.cpp compiles it with g++ (test infrastructure only).

@@ -1,8 +1,8 @@
-// posterior_kernel.h -- what a block of the posterior kernels does with a range of rows: the body of post_kernel
-// (posterior.hip: one set, all rows) and of post_sets_kernel (posterior_sets.hip: one set per blockIdx.z, its own
-// range of the rows).  Both kernels hand it the rows [r0, r1), the block's place `bx` among the `G` blocks that
-// share them, and arguments whose output pointers are the set's own; what a set's block adds up, and in which order,
-// therefore does not depend on which of the two kernels runs it.
+// posterior_kernel.h -- what a block of the posterior kernels does with a range of rows: the body of post_sets_kernel
+// (posterior.hip: one set per blockIdx.z, its own range of the rows; a bh_posterior handle is the single set of all
+// rows).  The kernel hands it the rows [r0, r1), the block's place `bx` among the `G` blocks that share them, and
+// arguments whose output pointers are the set's own; what a set's block adds up, and in which order, therefore
+// depends on the set's rows alone.
 //
 // The part above BH_HOSTSIM's #ifndef needs no device (the launch geometry): tests/hostsim/datafits_sets_sim.cpp
 // compiles it with g++ (test infrastructure only).

@@ -91,7 +91,8 @@ struct RadixSelect {
         for (int i = 0; i < nranks; i++)
             for (int c = 0; c < ncols; c++) left[(size_t)i * ncols + c] = ranks[i];
     }
-    // ranks of its own for every column: ranks[nranks][ncols] (columns of sets with different weight totals)
+    // ranks of its own for every column: ranks[nranks][ncols] (columns of sets with different weight totals).  The
+    // library's handles all take this form, a single set included; both forms find the same exact order statistics.
     struct PerColumn {};
     RadixSelect(int ncols_, int nranks_, int keybits, const uint64_t *ranks, PerColumn)
         : RadixSelect(ncols_, nranks_, keybits, ranks)

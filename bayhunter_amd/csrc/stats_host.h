@@ -1,13 +1,13 @@
-// stats_host.h -- the host scaffolding of the weighted column reductions (posterior.hip, datafits.hip) and of their
-// segmented forms (posterior_sets.hip, datafits_sets.hip).
+// stats_host.h -- the host scaffolding of the weighted column reductions (posterior.hip, datafits.hip).
 //
 // Both reduce n columns (depths there, samples of the modelled data here) over rows with integer weights in a
 // scan pass and a finish pass: min / max over order-preserving keys, Σ through a per-block slab that one thread
 // per column adds in block order, histograms over host-made edges, order statistics by radix select
-// (stats_core.h).  Only the way a block reads a value differs, and that stays in the files; what surrounds
-// it is here: the owner of device buffers, the fill and slab kernels, the select's device side, and the part of
-// a handle that carries a scan over to its finish -- ColumnStats for one set of rows, SetStats for many sets
-// (one block = one set), with the set_start check every segmented entry point makes (bh_moho_sets too).
+// (stats_core.h).  The rows come in contiguous sets (one block = one set); a handle over one set of rows is the
+// same handle with a single set.  Only the way a block reads a value differs, and that stays in the files; what
+// surrounds it is here: the owner of device buffers, the fill and slab kernels, the select's device side, the part
+// of a handle that carries a scan over to its finish (SetStats), and the set_start check every segmented entry
+// point makes (bh_moho_sets too).
 // (Errors and the device check: host_common.h.)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,16 +50,6 @@ static __global__ void stats_fill_kernel(u64 *p, int n, u64 v)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
-}
-
-// Σ over blocks in block order: one thread per column
-static __global__ void stats_reduce_kernel(const double *slab, int G, int n, double *out)
-{
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    double s = 0.0;
-    for (int g = 0; g < G; g++) s = s + slab[(size_t)g * n + c];
-    out[c] = s;
 }
 
 inline bool ascending(const double *v, int n)
@@ -123,84 +113,17 @@ inline const char *scan_fault(u64 included, u64 negative)
            : included > (1ull << 53) ? "weight total above 2^53" : nullptr;
 }
 
-// The part of a handle both reductions share: n columns, G blocks along the rows (a function of the row count
-// only, so that the slab order is fixed), and what a successful scan leaves for the finish.
-struct ColumnStats {
-    int n = 0, G = 1, scanned = 0;
-    hipStream_t st = nullptr;
-    u64 total = 0;                     // weight total of the scan
-    DevBufs bufs;
-    double *slab = nullptr, *red = nullptr, *dmean = nullptr;    // [G][n], [n], [n]
-    u64 *kmin = nullptr, *kmax = nullptr;                        // [n]
+// an argument error of the entry point `who`: "<who>: <what>" (static: the library exports no symbol for it)
+static inline int fail_who(const char *who, const char *what)
+{
+    return bh::fail_arg_((std::string(who) + ": " + what).c_str());
+}
 
-    int alloc_columns()
-    {
-        BH_HIP(bufs.alloc(slab, (size_t)G * n));
-        BH_HIP(bufs.alloc(red, n));
-        BH_HIP(bufs.alloc(dmean, n));
-        BH_HIP(bufs.alloc(kmin, n));
-        BH_HIP(bufs.alloc(kmax, n));
-        return BH_OK;
-    }
-    // a scan starts: whatever an earlier one left is void until this one has succeeded
-    int begin_scan()
-    {
-        scanned = 0;
-        hipLaunchKernelGGL(stats_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kmin, n, ~0ull);
-        hipLaunchKernelGGL(stats_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, kmax, n, 0ull);
-        BH_HIP(hipGetLastError());
-        return BH_OK;
-    }
-    // the slab of the pass just launched, added up: synchronises
-    int reduce_slab(std::vector<double> &out)
-    {
-        hipLaunchKernelGGL(stats_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           (const double *)slab, G, n, red);
-        BH_HIP(hipGetLastError());
-        out.assign(n, 0.0);
-        BH_HIP(hipMemcpyAsync(out.data(), red, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-        BH_HIP(hipStreamSynchronize(st));
-        return BH_OK;
-    }
-    // a scan ends, with its counts and reduce_slab's Σ w·v on the host: the total or an error (`who` names the
-    // entry point), the mean to the device for the finish, min / max back from their keys
-    int end_scan(const char *who, u64 included, u64 negative, const std::vector<double> &sum, double *vmin,
-                 double *vmax, double *mean)
-    {
-        const char *bad = scan_fault(included, negative);
-        if (bad) return bh::fail_arg_((std::string(who) + ": " + bad).c_str());
-        total = included;
-        std::vector<double> mu(n);
-        std::vector<u64> kmn(n), kmx(n);
-        for (int c = 0; c < n; c++) mu[c] = sum[c] / (double)included;
-        BH_HIP(hipMemcpyAsync(dmean, mu.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
-        BH_HIP(hipMemcpyAsync(kmn.data(), kmin, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
-        BH_HIP(hipMemcpyAsync(kmx.data(), kmax, sizeof(u64) * n, hipMemcpyDeviceToHost, st));
-        BH_HIP(hipStreamSynchronize(st));
-        scanned = 1;
-        for (int c = 0; c < n; c++) {
-            if (vmin) vmin[c] = bh::post_unkey64(kmn[c]);
-            if (vmax) vmax[c] = bh::post_unkey64(kmx[c]);
-            if (mean) mean[c] = mu[c];
-        }
-        return BH_OK;
-    }
-    // the finish pass's slab of Σ w·(v - mean)² -> population std: synchronises
-    int read_stdev(double *stdev)
-    {
-        std::vector<double> sq;
-        int rc = reduce_slab(sq);
-        if (rc) return rc;
-        for (int c = 0; c < n; c++) stdev[c] = std::sqrt(sq[c] / (double)total);
-        return BH_OK;
-    }
-};
-
-// ---- many sets of rows at once: the rows come in contiguous segments, set z is rows start[z] .. start[z + 1] ------
+// ---- the rows come in contiguous segments: set z is rows start[z] .. start[z + 1] -----------------------------------
 
 // Σ over a set's blocks in block order: one thread per (set, column); set z owns slab rows goff[z] .. goff[z + 1]
 // (a template, and SetStats below one on the file's blocks_of: a plain kernel in a header is compiled into every file
-// that includes it, and posterior.hip, datafits.hip and moho.hip keep the device code they had)
+// that includes it, and moho.hip takes from here the buffers and the set_start check only)
 template <typename T>
 static __global__ void stats_sets_reduce_kernel(const T *slab, const long long *goff, int nsets, int n, T *out)
 {
@@ -218,10 +141,9 @@ static __global__ void stats_sets_reduce_kernel(const T *slab, const long long *
 inline int check_set_start(const char *who, const long long *set_start, int nsets, long long nrows)
 {
     if (!set_start || set_start[0] != 0 || set_start[nsets] != nrows)
-        return bh::fail_arg_((std::string(who) + ": set_start must begin at 0 and end at nrows").c_str());
+        return fail_who(who, "set_start must begin at 0 and end at nrows");
     for (int z = 0; z < nsets; z++)
-        if (set_start[z] > set_start[z + 1])
-            return bh::fail_arg_((std::string(who) + ": set_start must be ascending").c_str());
+        if (set_start[z] > set_start[z + 1]) return fail_who(who, "set_start must be ascending");
     return BH_OK;
 }
 
@@ -234,9 +156,10 @@ inline const char *set_status_text(int status)
            : status == BH_POSTERIOR_SET_OVERFLOW ? scan_fault(~0ull, 0) : "";
 }
 
-// The part of a handle both segmented reductions share: ColumnStats for nsets sets.  A block belongs to one set and
-// is block x of the G(z) blocks a single handle over the set's rows would launch (the file's own blocks_of); the
-// sets' slab rows lie one after the other, so a pass takes every set in one launch and one reduction.
+// The part of a handle both reductions share: n columns of nsets sets, and what a scan leaves for the finish.  A
+// block belongs to one set and is block x of the G(z) blocks of the set -- a function of the set's row count only (the
+// file's own blocks_of), so that the slab order of a set is fixed whatever its offset and its neighbours; the sets'
+// slab rows lie one after the other, so a pass takes every set in one launch and one reduction.
 enum { SET_SKIP = 1 };                 // skip[z] & SET_SKIP: the finish leaves set z out (the other bits are the file's)
 template <int (*BlocksOf)(long long)>
 struct SetStats {
@@ -310,8 +233,7 @@ struct SetStats {
                  const std::vector<double> &sum, long long *tot, int *stat, double *vmin, double *vmax, double *mean)
     {
         for (int z = 0; z < nsets; z++)
-            if (negative[z])
-                return bh::fail_arg_((std::string(who) + ": " + scan_fault(included[z], negative[z])).c_str());
+            if (negative[z]) return fail_who(who, scan_fault(included[z], negative[z]));
         std::vector<u64> kmn(cols()), kmx(cols());
         BH_HIP(hipMemcpyAsync(kmn.data(), kmin, sizeof(u64) * cols(), hipMemcpyDeviceToHost, st));
         BH_HIP(hipMemcpyAsync(kmx.data(), kmax, sizeof(u64) * cols(), hipMemcpyDeviceToHost, st));

@@ -138,42 +138,7 @@ def _pair_list(cols, pairs, pair_bins):
 
 # ---- one set or many, on the device -------------------------------------------------------------------------
 
-class _One(object):
-    """A bh_datafits handle over one set of rows behind the interface of the segmented one."""
-
-    def __init__(self, Y, ncols, w, stream):
-        self.f, self.ncols, self.args = df.Fits(Y, ncols, w, None, stream), ncols, (Y, w, stream)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.f.close()
-
-    def scan(self):
-        try:
-            s = self.f.scan()
-        except _lib.BayHunterAmdError as e:
-            if 'empty selection' not in str(e):              # scan_fault()'s words (csrc/stats_host.h)
-                raise
-            Y, w, stream = self.args                         # no included row: what the segmented scan says of such a set
-            self.f.close()
-            self.f = df._FitsSets(Y, self.ncols, w, None, [0, Y.shape[0]], stream)
-            return self.f.scan()
-        return dict(total=np.array([s['total']], dtype=np.int64), excluded=np.array([s['excluded']], dtype=np.int64),
-                    vmin=s['vmin'][None], vmax=s['vmax'][None], mean=s['mean'][None], status=np.zeros(1, dtype=np.int32))
-
-    def finish(self, ranks, edges, eset):
-        if isinstance(self.f, df._FitsSets):
-            return self.f.finish(ranks, edges, eset)
-        ost, hist, std = self.f.finish(ranks[0], edges[0], eset)
-        return ost[None], hist[None], std[None]
-
-    def status_text(self, status):
-        return self.f.lib.bh_datafits_sets_status_text(int(status)).decode()
-
-
-def _summarize(cols, set_start, weights, nbins, pairs, pair_bins, device, single):
+def _summarize(cols, set_start, weights, nbins, pairs, pair_bins, device):
     import torch
     if not isinstance(cols, Columns):
         raise ValueError("cols: a scalars.Columns")
@@ -197,7 +162,7 @@ def _summarize(cols, set_start, weights, nbins, pairs, pair_bins, device, single
         return sel.SetList(results, {z: "empty selection: no rows" for z in range(S)})
     lib = _lib.load()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    handle = (lambda Y, n: _One(Y, n, w, stream)) if single else (lambda Y, n: df._FitsSets(Y, n, w, None, set_start, stream))
+    handle = lambda Y, n: df._FitsSets(Y, n, w, None, set_start, stream)     # summarize(): the one set [0, R]
     with torch.cuda.device(dev):
         with handle(M, nstat) as f:
             s = f.scan()
@@ -270,7 +235,7 @@ def summarize(cols, weights=None, nbins=20, pairs=(), pair_bins=50, device=None)
             with a column that has no value at all: zero counts, NaN edges and mode).
     ValueError for an empty selection."""
     rows = cols.data.shape[0] if isinstance(cols, Columns) else 0
-    res = _summarize(cols, [0, rows], weights, nbins, pairs, pair_bins, device, True)
+    res = _summarize(cols, [0, rows], weights, nbins, pairs, pair_bins, device)
     if res[0] is None:
         raise ValueError(res.failed[0])
     return res[0]
@@ -281,7 +246,7 @@ def summarize_sets(cols, set_start, weights=None, nbins=20, pairs=(), pair_bins=
     ascending from 0 to the number of rows; a set may be empty).  One segmented reduction (bh_datafits_sets_*) and one
     bh_hist2d_sets launch for all sets.  -> a SetList: summarize()'s dict per set, bit for bit what summarize returns
     for the set's rows alone, or None for a set without an included row of positive weight (`failed` {set: message})."""
-    return _summarize(cols, set_start, weights, nbins, pairs, pair_bins, device, False)
+    return _summarize(cols, set_start, weights, nbins, pairs, pair_bins, device)
 
 
 # ---- chain pools ------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // posterior_sets_sim.cpp -- TEST INFRASTRUCTURE ONLY.
 // The host side of the radix select (bayhunter_amd/csrc/stats_core.h) with one list of ranks per column, as the
-// segmented posterior (posterior_sets.hip) constructs it, compiled with g++; the test feeds it numpy's digit
+// segmented posterior (posterior.hip) constructs it, compiled with g++; the test feeds it numpy's digit
 // histograms.  per_column = 0 is the constructor every column shares one list with.
 #define BH_HOSTSIM 1
 #include "../../bayhunter_amd/csrc/stats_core.h"

@@ -262,22 +262,29 @@ def test_internal_prototypes_live_in_host_common_only():
 
 def test_sets_scaffold_lives_in_stats_host_only():
     """What the segmented reductions share (csrc/stats_host.h: SetStats) exists once: the set_start check's words occur
-    in one source file, whichever entry point reports them, neither sets file defines a reduce kernel of its own, and
-    the one status text is behind both exported symbols."""
+    in one source file, whichever entry point reports them, neither file defines a reduce kernel of its own, and the one
+    status text is behind both exported symbols.  The one-set handles are the sets handles with a single set: their
+    scaffold, their kernels and their files are gone, and their create goes through the sets create."""
     csrc = os.path.join(ROOT, 'bayhunter_amd', 'csrc')
     srcs = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.h', '.hip', '.cpp'))}
     for words in ('set_start must begin at 0 and end at nrows', 'set_start must be ascending'):
         assert [f for f, src in srcs.items() if words in src] == ['stats_host.h'], words
     kernel = re.compile(r'__global__[^;{()]*?\b(\w*reduce\w*)\s*\(')
-    assert kernel.findall(srcs['stats_host.h']) == ['stats_reduce_kernel', 'stats_sets_reduce_kernel']
-    for f in ('posterior_sets.hip', 'datafits_sets.hip'):
+    assert kernel.findall(srcs['stats_host.h']) == ['stats_sets_reduce_kernel']
+    assert 'posterior_sets.hip' not in srcs and 'datafits_sets.hip' not in srcs
+    for f in ('posterior.hip', 'datafits.hip'):
         assert not kernel.findall(srcs[f]), f
-        assert 'struct bh_%s : bh::SetStats' % f[:-4] in srcs[f], f
-        assert re.search(r'bh_%s_status_text\(int status\)\s*\{\s*return bh::set_status_text\(status\);' % f[:-4], srcs[f]), f
+        assert 'struct bh_%s_sets : bh::SetStats' % f[:-4] in srcs[f], f
+        assert re.search(r'bh_%s_sets_status_text\(int status\)\s*\{\s*return bh::set_status_text\(status\);' % f[:-4], srcs[f]), f
         for mine in ('scan_fault', 'stats_fill_kernel', 'post_unkey64(km'):
             assert mine not in srcs[f], (mine, f)
-    for f in ('posterior_sets.hip', 'datafits_sets.hip', 'moho.hip'):
-        assert srcs[f].count('bh::check_set_start("bh_') == 1, f
+        assert srcs[f].count('bh::check_set_start(') == 1, f         # in the create both forms share (`who` reports it)
+        body = re.search(r'^int bh_%s_create\(.*?^\}' % f[:-4], srcs[f], flags=re.S | re.M).group(0)
+        assert 'hipMalloc' not in body and 'alloc(' not in body and re.search(r'\bcreate\("bh_%s_create"' % f[:-4], body), f
+    assert srcs['moho.hip'].count('bh::check_set_start("bh_') == 1
+    for f, src in srcs.items():
+        for gone in ('ColumnStats', 'post_kernel<', 'df_mask_kernel'):
+            assert gone not in src, (gone, f)
 
 
 def test_no_switches_beyond_the_kept_ones():

@@ -332,8 +332,9 @@ def test_capi_refuses_bad_arguments(lib):
 def test_posterior_kernels_use_no_scratch():
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     from kernel_resources import kernel_resources
-    r = kernel_resources('posterior.hip')
-    assert len([k for k in r if 'post_kernel' in k]) == 4, sorted(r)
+    r = kernel_resources('posterior.hip')                 # both forms of the handle: one kernel, float32 / float64 x scan / finish
+    assert len([k for k in r if 'post_sets_kernel' in k]) == 4, sorted(r)
+    assert any('sets_reduce_kernel' in k for k in r)
     assert all(v['scratch'] == 0 for v in r.values()), r
 
 
