@@ -609,6 +609,18 @@ class ChainPool(object):
         from .convergence import pool_convergence
         return pool_convergence(self, nlags, depths, dev, exclude_outliers, rhat_max, ess_min, device)
 
+    def depth_covariance(self, dep_int=None, extras=('vpvs',), selection='weighted', dev=0.05, exclude_outliers=True,
+                         device=None):
+        """How Vs at one depth moves with Vs at another: the posterior covariance and correlation matrix of the Vs(z)
+        profile over the rows posterior() uses (covariance.summarize; the reference has no counterpart).  dep_int
+        defaults to posterior.default_dep_int() (0.5 km steps to 100 km); `extras` names columns of scalars.NAMES that
+        join the depths as further rows and columns of the matrix ('vpvs': the Vs - Vp/Vs trade-off per depth).  The
+        means are the segmented scan's, the contraction runs on the FP64 matrix cores (bh_depthcov_sets).
+        -> dict(cov, corr [K, K], mean, std [K], names ('vs@<z>' per depth, then the extras), nmodels, dep, chains (global
+        indices used)); corr is NaN in the rows and columns of a variance of 0 (a depth every model agrees on)."""
+        from .covariance import pool_depth_covariance
+        return pool_depth_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

@@ -222,7 +222,7 @@ def _takes_station(fn):
 class StationView(ChainPool):
     """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
     noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
-    datafits(), moho(), scalars(), convergence(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
+    datafits(), moho(), scalars(), convergence(), depth_covariance(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
 
     def __init__(self, pool, s):
         inner, c = pool.pool, pool.chains_per_station
@@ -483,6 +483,21 @@ class StationPool(object):
         from .convergence import stations_convergence
         return stations_convergence(self, nlags, depths, dev, exclude_outliers, rhat_max, ess_min, device, strict,
                                     max_rows)
+
+    def depth_covariance(self, dep_int=None, extras=('vpvs',), selection='weighted', dev=0.05, exclude_outliers=True,
+                         device=None, strict=True, max_rows=None, budget_bytes=1 << 30):
+        """The posterior covariance and correlation matrix of the Vs(z) profile of every station in one pass
+        (covariance.summarize_sets: one segmented scan for the means and one bh_depthcov_sets call per run of stations).
+        Arguments as station(s).depth_covariance(...); per station every field is bit for bit what that returns ('chains'
+        numbered within the station).  -> covariance.StationDepthCovariance: `names`, `stations[name]` those dicts,
+        `failed` {name: message}, `columns` ('vs@<z>' per depth, then the extras), `dep`, the stacked `cov / corr
+        [nstations, K, K]`, `mean / std [nstations, K]`, `nmodels [nstations]`; NaN for a failed station.  strict=True: a
+        failed station is a ValueError naming the first one.  max_rows: runs of whole stations of at most that many rows
+        (default: what half of the free device memory holds); budget_bytes: bound on the S matrices of one call (1 GiB;
+        1 024 stations of 201 depths are 331 MB).  No result depends on either."""
+        from .covariance import stations_depth_covariance
+        return stations_depth_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device, strict, max_rows,
+                                         budget_bytes)
 
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone

@@ -818,6 +818,38 @@ int  bh_autocov_sets(const double *D, long long nrows, long long stride, int nco
                      const long long *series_start, int nseries, const double *mean, int nlags, double *acov,
                      long long *length, void *stream);
 
+/* ---- depth-to-depth second moment of Vs for many sets of rows ------------------------------- */
+/* What the posterior covariance and correlation matrix of the Vs(z) profile need beyond the per-depth means: how Vs at
+ * one depth moves with Vs at another, and with a few scalar columns beside it (Vp/Vs, noise amplitudes), for every
+ * station of a network in one call.  The one contraction of the statistics, X^T diag(w) X, on v_mfma_f64_16x16x4_f64.
+ *
+ * rows, fp64, nrows, stride, width   DEVICE rows in the reference's layout as for bh_posterior_sets_create;
+ *               1 <= nrows <= 2^32
+ * weights       DEVICE int32 [nrows] >= 0, or NULL for all ones.  A negative weight anywhere is BH_ERR_ARG
+ * extra         DEVICE float64 [nrows][extra_stride], the first nextra columns used; NULL with nextra = 0
+ * set_start     HOST [nsets + 1] as for bh_moho_sets: set s is rows set_start[s] .. set_start[s + 1], a set may be empty
+ * dep           HOST [ndep] ascending, ndep >= 1; K = ndep + nextra <= BH_DEPTHCOV_MAX_K
+ * center        HOST [nsets][K]: what is subtracted from every row of the set (its mean, as a scan rounded it)
+ * S             HOST [nsets][K][K];  r1 HOST [nsets][K];  total HOST [nsets]
+ *
+ * With x_r a row's Vs on dep (bh_posterior's walk) followed by its extra values, d_rk = fl(x_rk - center[s][k]) and
+ * e_rk = fl(w_r d_rk):
+ *     S[s][i][j] = sum_r e_ri d_rj  (i <= j, mirrored: S is exactly symmetric),  r1[s][i] = sum_r e_ri,  total[s] = sum_r w_r
+ * over the set's rows with w_r > 0 and a model (an all-NaN row is left out).  The caller forms
+ * cov = (S - r1 r1^T / W) / W with W = total: a centre off the exact mean costs nothing at first order.  A set without
+ * such a row has total 0 and zeros.  A NaN among a counted row's extra values reaches the cells of its column.
+ * The order of the sums is fixed (csrc/depthcov_core.h): blocks of BH_DEPTHCOV_BLOCK_ROWS rows counted from the set's
+ * first row, inside a block the rows ascending four per MFMA, the block partials added in ascending order by one thread
+ * per cell.  Two runs are bit-identical, and a set's result depends neither on the other sets of the call nor on where
+ * its rows lie.  All arguments but the weights' sign are checked before any device is touched; the outputs are there
+ * when the call returns. */
+#define BH_DEPTHCOV_MAX_K      256
+#define BH_DEPTHCOV_BLOCK_ROWS 1024
+int  bh_depthcov_sets(const void *rows, int fp64, long long nrows, long long stride, int width, const int *weights,
+                      const double *extra, long long extra_stride, int nextra, const long long *set_start, int nsets,
+                      const double *dep, int ndep, const double *center, double *S, double *r1, long long *total,
+                      void *stream);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
