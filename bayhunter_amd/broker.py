@@ -35,16 +35,17 @@ import numpy as np
 IDLE, REQUEST, DONE = 0, 1, 2
 
 
-def gpu_backend(swd, rf):
+def gpu_backend(swd, rf, ell=()):
     """Default back end, constructed in the server process: (H, VP, VS, RHO, nlay) -> (out, err)."""
     import torch
-    from .engine import ForwardEngine, RfSpec, SwdSpec
-    eng = ForwardEngine(swd=[SwdSpec(*s) for s in swd], rf=[RfSpec(*r) for r in rf])
+    from .engine import EllSpec, ForwardEngine, RfSpec, SwdSpec
+    eng = ForwardEngine(swd=[SwdSpec(*s) for s in swd], rf=[RfSpec(*r) for r in rf], ell=[EllSpec(*e) for e in ell])
+    nflags = max(1, len(eng.swd))          # the flags of the targets the clients know (hidden ones come behind them)
 
     def run(H, VP, VS, RHO, nlay):
         out, err = eng.run(H, VP, VS, RHO, nlay)
         torch.cuda.synchronize()
-        return out[:, :eng.ncols].cpu().numpy(), err.cpu().numpy()
+        return out[:, :eng.ncols].cpu().numpy(), err[:, :nflags].cpu().numpy()
     return run
 
 
@@ -71,14 +72,14 @@ def _server_alive(pid):
         return False
 
 
-def _serve(shared, backend_factory, swd, rf):
+def _serve(shared, backend_factory, swd, rf, ell=()):
     S = shared
     S['server_pid'].value = os.getpid()
     # A server that could not create its back end, or whose launch failed, ends with a non-zero exit
     # code (a supervisor / `_proc.exitcode` must not see a clean exit); KeyboardInterrupt and SystemExit
     # are reported to the waiting clients and then re-raised, not swallowed.
     try:
-        run = backend_factory(swd, rf)
+        run = backend_factory(swd, rf, ell) if ell else backend_factory(swd, rf)
     except Exception:
         _fail(S, 'broker back end could not be created:\n' + traceback.format_exc())
         sys.exit(1)
@@ -133,16 +134,18 @@ def _serve(shared, backend_factory, swd, rf):
 
 class ForwardBroker(object):
     """Server side.  swd: list of (ref, periods[, mode, flsph]); rf: list of
-    (ref, obsx[, gauss, p, nsv]) -- the argument tuples of engine.SwdSpec / engine.RfSpec."""
+    (ref, obsx[, gauss, p, nsv]); ell: list of (ref, periods[, flsph, absolute]) -- the argument tuples of
+    engine.SwdSpec / engine.RfSpec / engine.EllSpec.  A back end is called as factory(swd, rf), and as
+    factory(swd, rf, ell) when there are ellipticity targets."""
 
     def __init__(self, swd=(), rf=(), max_clients=64, Lmax=32, window=3e-4,
-                 backend_factory=gpu_backend):
+                 backend_factory=gpu_backend, ell=()):
         self.swd = [tuple(s) for s in swd]
         self.rf = [tuple(r) for r in rf]
-        self.sizes = [len(s[1]) for s in self.swd] + [len(r[1]) for r in self.rf]
-        self.refs = [s[0] for s in self.swd] + [r[0] for r in self.rf]
-        self.axes = [np.asarray(s[1], dtype=np.float64) for s in self.swd] + \
-                    [np.asarray(r[1], dtype=np.float64) for r in self.rf]
+        self.ell = [tuple(e) for e in ell]
+        self.sizes = [len(s[1]) for s in self.swd + self.rf + self.ell]
+        self.refs = [s[0] for s in self.swd + self.rf + self.ell]
+        self.axes = [np.asarray(s[1], dtype=np.float64) for s in self.swd + self.rf + self.ell]
         row = int(sum(self.sizes))
         n = int(max_clients)
         ctx = mp.get_context('fork')
@@ -166,7 +169,7 @@ class ForwardBroker(object):
         if self._factory is gpu_backend and torch is not None and torch.cuda.is_initialized():
             raise BrokerError("ForwardBroker.start() after this process initialised the GPU: start the "
                               "broker first (or from a fresh process), then create engines / chain pools")
-        self._proc = self._ctx.Process(target=_serve, args=(self.shared, self._factory, self.swd, self.rf),
+        self._proc = self._ctx.Process(target=_serve, args=(self.shared, self._factory, self.swd, self.rf, self.ell),
                                        daemon=True)
         self._proc.start()
         if not self.shared['ready'].acquire(timeout=300):
@@ -189,7 +192,7 @@ class ForwardBroker(object):
             if slot >= self.shared['n']:
                 raise RuntimeError("more sessions than max_clients")
             self.shared['next_slot'].value = slot + 1
-        return BrokerSession(self.shared, slot, self.refs, self.axes, self.sizes, len(self.swd))
+        return BrokerSession(self.shared, slot, self.refs, self.axes, self.sizes, len(self.swd), len(self.ell))
 
     def stats(self):
         launches, models, busy = np.frombuffer(self.shared['stats'], dtype=np.float64)
@@ -208,9 +211,10 @@ class ForwardBroker(object):
 class BrokerSession(object):
     """Client side, one per chain process."""
 
-    def __init__(self, shared, slot, refs, axes, sizes, nswd):
+    def __init__(self, shared, slot, refs, axes, sizes, nswd, nell=0):
         self.S, self.slot = shared, slot
         self.refs, self.axes, self.nswd = refs, axes, nswd
+        self.first_ell = len(refs) - nell    # the ellipticity targets are the last nell
         self.offsets = np.concatenate(([0], np.cumsum(sizes)))
         self._key = None
         self._row = None
@@ -281,7 +285,8 @@ class BrokerSession(object):
 
 class BrokerPlugin(object):
     """run_model(h, vp, vs, rho) -> (x, y) through the broker; (nan, nan) when the solver found no
-    root for this model -- the reference's failure convention (src/surf96_modsw.py:126)."""
+    root for this model -- the reference's failure convention (src/surf96_modsw.py:126) -- and for an ellipticity
+    target whose row is NaN (a failed search behind it, a water layer on top)."""
 
     def __init__(self, session, t):
         self.session, self.t = session, t
@@ -297,4 +302,6 @@ class BrokerPlugin(object):
         if self.t < self.session.nswd and flags[self.t] != 0:
             return np.nan, np.nan
         lo, hi = self.session.offsets[self.t], self.session.offsets[self.t + 1]
+        if self.t >= self.session.first_ell and np.isnan(row[lo:hi]).any():
+            return np.nan, np.nan
         return self.obsx, row[lo:hi].copy()

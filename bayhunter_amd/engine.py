@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .layout import ORDER_MIN, RF_REFS, SWD_REFS, RfSpec, RowLayout, SwdSpec, rf_obsparams  # noqa: F401 (re-exported)
+from .layout import ELL_REFS, ORDER_MIN, RF_REFS, SWD_REFS, EllSpec, RfSpec, RowLayout, SwdSpec, rf_obsparams  # noqa: F401 (re-exported)
 
 
 class DeviceModels(object):
@@ -37,20 +37,25 @@ class DeviceModels(object):
 class ForwardEngine(object):
     """All targets of a joint inversion for a batch of models in (at most) two launches.
 
-    Output row of model b: [swd target 0 | swd target 1 | ... | rf target 0 | ...], fp64, `ncols`
-    values; `slices[t]` is target t's column range.  Rows are `row` doubles apart: with a dispersion
+    Output row of model b: [swd target 0 | swd target 1 | ... | rf target 0 | ... | ellipticity target 0 | ...], fp64,
+    `ncols` values; `slices[t]` is target t's column range.  Rows are `row` doubles apart: with a dispersion
     target of more than 60 periods `row` > `ncols` (the 60 solved values live behind the visible
     columns and are interpolated into them after the kernel).
+
+    An ellipticity target (EllSpec) is one more launch, bh_ell_batch, behind the dispersion launch on the same stream:
+    it reads the phase velocities of an equal 'rdispph' target of `swd`, or of a hidden one the layout adds behind the
+    visible columns (layout.RowLayout).  `err` then has a column per solved dispersion target, the hidden ones last.
     """
 
-    def __init__(self, swd=(), rf=(), device=None):
+    def __init__(self, swd=(), rf=(), device=None, ell=()):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.BayHunterAmdError("no HIP device visible to torch; there is no CPU fallback")
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None \
             else torch.device(device)
-        self.layout = lay = RowLayout(swd, rf)
-        self.swd, self.rf = lay.swd, lay.rf
+        self.layout = lay = RowLayout(swd, rf, ell)
+        self.swd, self.rf, self.ell = lay.swd, lay.rf, lay.ell
+        self._nswd = len(lay.swd_all)        # dispersion targets the library solves: the visible and the hidden ones
         self.slices, self.ncols, self.row = lay.slices, lay.ncols, lay.row
         self._tg, self._rfp = lay.tg, lay.rfp
         with torch.cuda.device(self.device):
@@ -101,10 +106,10 @@ class ForwardEngine(object):
              profiles/r01_divergence_probe.txt).
         (`ragged` is accepted for compatibility.)"""
         order = None
-        if self.sort_ragged and self.swd and packed.shape[0] > ORDER_MIN:
+        if self.sort_ragged and self._nswd and packed.shape[0] > ORDER_MIN:
             B, L = packed.shape[0], packed.shape[2]
             keys = torch.empty(B, dtype=torch.int32, device=self.device)
-            tmax = max(float(sp.periods.max()) for sp in self.swd)
+            tmax = max(float(sp.periods.max()) for sp in self.layout.swd_all)
             st = torch.cuda.current_stream(self.device)
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.bh_swd_order_keys(
@@ -115,7 +120,7 @@ class ForwardEngine(object):
 
     def alloc_out(self, B):
         out = torch.empty((B, self.row), dtype=torch.float64, device=self.device)
-        err = torch.empty((B, max(1, len(self.swd))), dtype=torch.int32, device=self.device)
+        err = torch.empty((B, max(1, self._nswd)), dtype=torch.int32, device=self.device)
         return out, err
 
     def run(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, stream=None, rf_sets=None):
@@ -129,7 +134,7 @@ class ForwardEngine(object):
         models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
         if models.packed.device != self.device:
             raise ValueError("models live on %s, engine on %s" % (models.packed.device, self.device))
-        if models.order is None and self.sort_ragged and self.swd and models.B > ORDER_MIN:
+        if models.order is None and self.sort_ragged and self._nswd and models.B > ORDER_MIN:
             # resident models that came without a processing order (e.g. models.layers_from_voronoi):
             # computed once and kept with them
             models.order = self.reorder(models.packed, models.nlay).order
@@ -151,12 +156,12 @@ class ForwardEngine(object):
             # waves retire one by one; launched on a second stream, rf_kernel's workgroups take over
             # the freed SIMDs instead of waiting for the last search to finish.
             side = None
-            if self.swd and self.rf and self.overlap:
+            if self._nswd and self.rf and self.overlap:
                 side = self._side.get(st.cuda_stream)
                 if side is None:
                     side = self._side[st.cuda_stream] = torch.cuda.Stream(device=self.device)
                 side.wait_stream(st)
-            need, ws_ptr = self.lib.bh_swd_workspace_bytes(B, len(self.swd), self._tg), None
+            need, ws_ptr = self.lib.bh_swd_workspace_bytes(B, self._nswd, self._tg), None
             if need:
                 ws = self._ws.get(st.cuda_stream)
                 if ws is None or ws.numel() * 8 < need:
@@ -166,7 +171,7 @@ class ForwardEngine(object):
                 ws_ptr = ws.data_ptr()
             # row, descriptors and overlap are read at every call: a caller may move a target's columns (bench.py)
             args = (B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(), RHO.data_ptr(),
-                    len(self.swd), self._tg, self.periods.data_ptr(), len(self._obsx), self._interp, len(self.rf),
+                    self._nswd, self._tg, self.periods.data_ptr(), len(self._obsx), self._interp, len(self.rf),
                     self._rfp, models.order.data_ptr() if models.order is not None else None, models.mean_depth or 0.0, 1,
                     out.data_ptr(), self.row, err.data_ptr(), ws_ptr, need, sp,
                     sp if side is None else C.c_void_p(side.cuda_stream))
@@ -181,6 +186,12 @@ class ForwardEngine(object):
                         or set_id.device != self.device:
                     raise ValueError("rf_sets: set_id [B] int32, contiguous, on the engine's device")
                 _lib.check(self.lib.bh_forward_batch_sets(*(args + (set_p.shape[1], set_p.data_ptr(), set_id.data_ptr()))))
+            # the ellipticities, behind the dispersion launch on its stream (beside the receiver functions on theirs)
+            for e, (t, per_off, c_off), off in zip(self.ell, self.layout.ell_src, self.layout.ell_off):
+                _lib.check(self.lib.bh_ell_batch(
+                    B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(), RHO.data_ptr(),
+                    e.periods.size, self.periods.data_ptr() + 8 * per_off, e.flsph, out.data_ptr() + 8 * c_off, self.row,
+                    err.data_ptr() + 4 * t, max(1, self._nswd), 1 if e.absolute else 0, out.data_ptr() + 8 * off, self.row, sp))
             if side is not None:
                 st.wait_stream(side)
                 for t in (H, VP, VS, RHO, nlay, out) + (() if rf_sets is None else tuple(rf_sets)):

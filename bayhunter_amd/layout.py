@@ -16,6 +16,7 @@ ORDER_MIN = 1024
 
 SWD_REFS = {'rdispgr': (2, 1), 'ldispgr': (1, 1), 'rdispph': (2, 0), 'ldispph': (1, 0)}
 RF_REFS = {'prf': 0, 'seis': 0, 'srf': 1}
+ELL_REFS = ('rellip',)
 
 
 def rf_obsparams(obsx, ref='prf'):
@@ -59,18 +60,52 @@ class RfSpec(object):
         self.gauss, self.p, self.nsv = float(gauss), float(p), nsv
 
 
+class EllSpec(object):
+    """Ellipticity (H/V) of the fundamental Rayleigh mode at `periods` (at most 60: a ratio that changes sign is not
+    interpolated).  absolute: |H/V|, what most data are; else the signed ratio, positive for retrograde motion."""
+
+    def __init__(self, ref, periods, flsph=0, absolute=True):
+        if ref not in ELL_REFS:
+            raise ReferenceError("no ellipticity forward model for ref '%s'" % ref)
+        self.ref = ref
+        self.obsx = np.ascontiguousarray(periods, dtype=np.float64)
+        if self.obsx.size < 1 or self.obsx.size > _lib.MAX_PERIODS:
+            raise ValueError("ellipticity target '%s': 1 to %d periods, not %d" % (ref, _lib.MAX_PERIODS, self.obsx.size))
+        self.periods = self.obsx
+        self.flsph, self.absolute = int(flsph), bool(absolute)
+
+    def reads(self, sp):
+        """Does the dispersion target `sp` solve what this target needs: fundamental-mode Rayleigh phase velocities
+        on the same earth at bit-equal periods?"""
+        return (sp.ref == 'rdispph' and sp.mode == 1 and sp.flsph == self.flsph and not sp.resample
+                and sp.periods.tobytes() == self.periods.tobytes())
+
 
 class RowLayout(object):
-    """Output row of model b: [swd target 0 | swd target 1 | ... | rf target 0 | ...], fp64, `ncols`
-    values; `slices[t]` is target t's column range.  Rows are `row` doubles apart: with a dispersion
+    """Output row of model b: [swd target 0 | swd target 1 | ... | rf target 0 | ... | ellipticity target 0 | ...],
+    fp64, `ncols` values; `slices[t]` is target t's column range.  Rows are `row` doubles apart: with a dispersion
     target of more than 60 periods `row` > `ncols` (the 60 solved values live behind the visible
     columns and are interpolated into them after the kernel).  `tg` / `rfp` are the descriptor arrays
     bh_forward_batch takes (at least one element each), `periods` the concatenated solved periods, `resampled` the
-    (target index, visible slice, scratch offset, SwdSpec) of every target with more than 60 periods."""
+    (target index, visible slice, scratch offset, SwdSpec) of every target with more than 60 periods.
 
-    def __init__(self, swd=(), rf=()):
-        self.swd, self.rf = list(swd), list(rf)
-        if len(self.swd) > _lib.MAX_TARGETS:
+    An ellipticity target reads the phase velocities of a dispersion target (EllSpec.reads).  Where `swd` has none, the
+    layout adds a hidden 'rdispph' target whose columns lie behind the visible ones, like the solved values of a
+    resampled target: `swd_all` is `swd` followed by the hidden targets, `tg` describes all of them, and `ell_src[i]`
+    is (index into swd_all, period offset, column offset) of ellipticity target i's source.  Without ellipticity
+    targets nothing differs from a layout that does not know them."""
+
+    def __init__(self, swd=(), rf=(), ell=()):
+        self.swd, self.rf, self.ell = list(swd), list(rf), list(ell)
+        self.swd_all = list(self.swd)
+        src = []
+        for e in self.ell:
+            t = next((i for i, sp in enumerate(self.swd_all) if e.reads(sp)), None)
+            if t is None:
+                t = len(self.swd_all)
+                self.swd_all.append(SwdSpec('rdispph', e.periods, 1, e.flsph))
+            src.append(t)
+        if len(self.swd_all) > _lib.MAX_TARGETS:
             raise ValueError("too many SWD targets")
         off = 0
         self.slices = []
@@ -82,13 +117,22 @@ class RowLayout(object):
             rf_off.append(off)
             self.slices.append(slice(off, off + r.obsx.size))
             off += r.obsx.size
+        self.ell_off = []
+        for e in self.ell:
+            self.ell_off.append(off)
+            self.slices.append(slice(off, off + e.obsx.size))
+            off += e.obsx.size
         self.ncols = off
         per_off = 0
-        self.tg = (_lib.SwdTarget * max(1, len(self.swd)))()
+        self.tg = (_lib.SwdTarget * max(1, len(self.swd_all)))()
         pers = []
         self.resampled = []
-        for t, sp in enumerate(self.swd):
-            koff = self.slices[t].start
+        for t, sp in enumerate(self.swd_all):
+            if t >= len(self.swd):                         # hidden: solved behind the visible columns, shown nowhere
+                koff = off
+                off += sp.periods.size
+            else:
+                koff = self.slices[t].start
             if sp.resample:                                # the kernel writes behind the visible columns
                 koff = off
                 off += sp.periods.size
@@ -101,6 +145,7 @@ class RowLayout(object):
                           r.waveno, r.obsx.size, o) for r, o in zip(self.rf, rf_off)])
         self.row = off
         self.periods = np.ascontiguousarray(np.concatenate(pers) if pers else np.zeros(1), dtype=np.float64)
+        self.ell_src = [(t, self.tg[t].per_off, self.tg[t].out_off) for t in src]
 
     def interp(self, obsx):
         """The bh_eval_interp array of the targets in `resampled`, with their observed periods at addresses obsx[i]."""

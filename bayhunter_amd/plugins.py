@@ -6,14 +6,15 @@ Contract (reference: src/Targets.py:33-82,201-214, templates/myfwd.py): an objec
 an ndarray of the same length -- or ``(nan, nan)`` when no solution exists; it never raises for a
 model it cannot solve.  ``SurfDisp`` and ``RFminiModRF`` are stand-ins for the reference classes of
 the same names (src/surf96_modsw.py, src/rfmini_modrf.py) and accept the same parameters; both add
-``run_models`` for batches.  All numerics happen in libbayhunter_amd (no CPU fallback).
+``run_models`` for batches.  ``RayleighEllipticity`` has no counterpart in the reference, which leaves the datum to a
+user plugin (templates/myfwd.py).  All numerics happen in libbayhunter_amd (no CPU fallback).
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from .engine import RF_REFS, SWD_REFS, ForwardEngine, RfSpec, SwdSpec, rf_obsparams
+from .engine import ELL_REFS, RF_REFS, SWD_REFS, EllSpec, ForwardEngine, RfSpec, SwdSpec, rf_obsparams
 
 NP_MAX = _lib.MAX_PERIODS   # surfdisp96.f:62
 
@@ -172,3 +173,47 @@ class RFminiModRF(_Plugin):
                                                     wtype=self.modelparams['wtype'])])
         out, _ = self._engine.run(H, VP, VS, RHO, nlay)
         return self._time_axis(), out.cpu().numpy()
+
+
+class RayleighEllipticity(_Plugin):
+    """Ellipticity (H/V, ZH ratio) of the fundamental Rayleigh mode per period, for layered models.
+
+    ref            'rellip'
+    modelparams    flsph (0 = flat earth), absolute (True: |H/V|, what most data are; False: the signed ratio,
+                   positive for retrograde motion)
+    At most 60 periods (ValueError beyond: a ratio that changes sign is not interpolated).  A model whose dispersion
+    search fails, or whose top layer is water, has no ellipticity: (nan, nan).
+    """
+    defaults = {'flsph': 0, 'absolute': True}
+
+    def __init__(self, obsx, ref='rellip'):
+        if ref not in ELL_REFS:
+            raise ReferenceError("RayleighEllipticity has no forward model for ref '%s' (known: %s)."
+                                 % (ref, ', '.join(ELL_REFS)))
+        _Plugin.__init__(self, obsx, ref)
+        EllSpec(ref, obsx)                                     # the period limit, before anything is computed
+
+    def run_model(self, h, vp, vs, rho, **params):
+        """One model through bh_ellipticity."""
+        lib = _lib.load()
+        model32 = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32))
+                   for a in (h, vp, vs, rho)]                  # real*4 layers, like the dispersion drop-in's
+        pers = np.ascontiguousarray(self.obsx, dtype=np.float64)
+        ell = np.zeros(pers.size)
+        flag = C.c_int(0)
+        _lib.check(lib.bh_ellipticity(
+            model32[0].ctypes.data, model32[1].ctypes.data, model32[2].ctypes.data, model32[3].ctypes.data, len(h),
+            self.modelparams['flsph'], pers.size, pers.ctypes.data, 1 if self.modelparams['absolute'] else 0,
+            ell.ctypes.data, C.byref(flag)))
+        if flag.value != 0 or np.isnan(ell).any():
+            return np.nan, np.nan
+        return pers, ell
+
+    def run_models(self, H, VP, VS, RHO, nlay):
+        """Batch of models ([B, Lmax] arrays) -> (x, Y[B, nobs], err[B]); rows without an ellipticity are NaN."""
+        if self._engine is None:
+            self._engine = ForwardEngine(ell=[EllSpec(self.ref, self.obsx, self.modelparams['flsph'],
+                                                      self.modelparams['absolute'])])
+        out, err = self._engine.run(H, VP, VS, RHO, nlay)
+        return (np.ascontiguousarray(self.obsx, dtype=np.float64), out[:, self._engine.slices[0]].cpu().numpy(),
+                err.cpu().numpy()[:, 0])

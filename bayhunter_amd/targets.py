@@ -20,7 +20,8 @@ import logging
 import numpy as np
 
 from . import _lib
-from .engine import RF_REFS, SWD_REFS
+from .engine import ELL_REFS, RF_REFS, SWD_REFS
+from .plugins import RayleighEllipticity as _EllipticityPlugin
 from .plugins import RFminiModRF, SurfDisp
 
 logger = logging.getLogger()
@@ -47,6 +48,9 @@ class ModeledData(object):
             self.xlabel = 'Time in s'
         elif ref in SWD_REFS:
             self.plugin = SurfDisp(obsx, ref)
+            self.xlabel = 'Period in s'
+        elif ref in ELL_REFS:
+            self.plugin = _EllipticityPlugin(obsx, ref)
             self.xlabel = 'Period in s'
         else:
             logger.info("No built-in forward model for ref '%s': install one with "
@@ -204,6 +208,8 @@ LoveDispersionPhase = _typed('ldispph', 'swd', 'LoveDispersionPhase')
 LoveDispersionGroup = _typed('ldispgr', 'swd', 'LoveDispersionGroup')
 PReceiverFunction = _typed('prf', 'rf', 'PReceiverFunction')
 SReceiverFunction = _typed('srf', 'rf', 'SReceiverFunction')
+# no counterpart in the reference; valued with the noise models of the dispersion targets
+RayleighEllipticity = _typed('rellip', 'swd', 'RayleighEllipticity')
 
 
 class JointTarget(object):

@@ -185,6 +185,24 @@ int bh_rf_batch_sets(int B, int Lmax, int model_stride, const int *nlay, const d
                      const int *set_id, double *out, int out_stride,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- batched Rayleigh-wave ellipticity (device pointers) --------------------------------- */
+/* H/V of the fundamental Rayleigh mode: one pass of the period equation's layer recursion per (model, period) at
+ * the phase velocity a search found (csrc/ell_core.h).  Models as for bh_swd_batch; periods [nper], 1 <= nper <=
+ * BH_MAX_PERIODS; flsph as bh_swd_target.iflsph.
+ *   c, c_stride      row b: c + b * c_stride, the phase velocities of the nper periods as a fundamental-mode Rayleigh
+ *                    phase target (iwave 2, igr 0, mode 1, the same iflsph and periods) wrote them: usually
+ *                    out + out_off and out_stride of that bh_swd_batch call
+ *   c_err, err_stride  row b: c_err[b * err_stride], that target's err flag (err + t, ntargets)
+ *   absolute         != 0: |H/V|, what most data are; 0: the signed ratio, positive for retrograde motion
+ *   out, out_stride  row b: out + b * out_stride receives nper values; it may be other columns of c's matrix
+ * A row whose flag is set, whose nlay is outside 2 .. Lmax or whose top layer is water is NaN, as is a period whose c
+ * is not a positive finite number.  Asynchronous on `stream`, behind the call that writes c.  BH_ERR_ARG for nper out
+ * of range, a NULL pointer, c_stride or out_stride shorter than nper, err_stride < 1. */
+int bh_ell_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                 const double *vs, const double *rho, int nper, const double *periods, int flsph, const double *c,
+                 int c_stride, const int *c_err, int err_stride, int absolute, double *out, int out_stride,
+                 void *stream);
+
 /* ---- Voronoi nuclei -> layered models + prior checks (device pointers) ------------------- */
 /* The step in front of the forward path: Model.get_vp_vs_h (src/Models.py:26-52) and
  * SingleChain._validmodel (src/SingleChain.py:330-392) for a batch of proposals.  Input per model:
@@ -310,6 +328,11 @@ int bh_synrf(int nsamp, double fsamp, double tshift, double p, double a, double 
              int waveno, int nlay, const double *z, const double *vp, const double *vs,
              const double *rh, const double *qp, const double *qs,
              double *fz, double *fr, double *rf);
+/* Ellipticity of the fundamental Rayleigh mode of one model: bh_surfdisp96's search (iwave 2, mode 1, igr 0) for the
+ * phase velocities, then bh_ell_batch's pass.  Model arrays as for bh_surfdisp96, t/ell real*8 with at least kmax
+ * entries, 1 <= kmax <= BH_MAX_PERIODS.  *err is the search's flag; when it is set, ell is NaN throughout. */
+int bh_ellipticity(const float *thkm, const float *vpm, const float *vsm, const float *rhom,
+                   int nlayer, int iflsph, int kmax, const double *t, int absolute, double *ell, int *err);
 
 /* ---- the reference's literal FFI symbols ------------------------------------------------ */
 /* Thin aliases of the two drop-ins above under the names the reference's generated glue binds, so that
