@@ -13,7 +13,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "swd_launch.hip", "rf_capi.hip", "like_capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
            "datafits.hip", "moho.hip", "pairs.hip", "autocov.hip", "depthcov.hip", "math_probe.hip", "rf_probe.hip",
-           "ellipticity.hip", "ell_capi.hip"]
+           "ellipticity.hip", "ell_rows.hip", "ell_capi.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
            "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "depthcov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h",
@@ -57,6 +57,11 @@ class EvalInterp(C.Structure):
     """struct bh_eval_interp"""
     _fields_ = [("target", C.c_int), ("dst_off", C.c_int), ("n_dst", C.c_int), ("_pad", C.c_int),
                 ("obsx", C.c_void_p)]
+
+
+class EllTarget(C.Structure):
+    """struct bh_ell_target"""
+    _fields_ = [("src", C.c_int), ("nper", C.c_int), ("out_off", C.c_int), ("absolute", C.c_int)]
 
 
 class ModelPriors(C.Structure):
@@ -180,6 +185,7 @@ _SIGS = {
     "bh_eval_set_observations": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
     "bh_eval_set_rf_slowness": (C.c_int, [_vp, C.c_int, _vp]),
     "bh_eval_set_gaps": (C.c_int, [_vp, C.c_int, _vp]),
+    "bh_eval_set_ellipticity": (C.c_int, [_vp, C.c_int, C.POINTER(EllTarget)]),
     "bh_forward_batch": (C.c_int, [C.c_int] * 3 + [_vp] * 5 + [C.c_int, C.POINTER(SwdTarget), _vp, C.c_int,
                                    C.POINTER(EvalInterp), C.c_int, C.POINTER(RfParams), _vp, C.c_double, C.c_int, _vp,
                                    C.c_int, _vp, _vp, C.c_size_t, _vp, _vp]),
@@ -228,6 +234,8 @@ _SIGS = {
                                 C.c_int, _vp, _vp, C.POINTER(C.c_int)]),
     "bh_ell_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int,
                                _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "bh_ell_batch_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int,
+                                    _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp]),
     "bh_ellipticity": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.POINTER(C.c_int)]),
     "bh_synrf": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                            C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,5 +1,6 @@
-// ell_capi.hip -- the C ABI of the Rayleigh-wave ellipticity (include/bayhunter_amd.h): bh_ell_batch on device
-// pointers and the synchronous single-model drop-in bh_ellipticity.  Host code only; the kernel is in ellipticity.hip.
+// ell_capi.hip -- the C ABI of the Rayleigh-wave ellipticity (include/bayhunter_amd.h): bh_ell_batch and
+// bh_ell_batch_rows on device pointers and the synchronous single-model drop-in bh_ellipticity.  Host code only; the
+// kernels are in ellipticity.hip and ell_rows.hip.
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "ell_launch.h"
@@ -27,6 +28,31 @@ int bh_ell_batch(int B, int Lmax, int model_stride, const int *nlay, const doubl
     A.nlay = nlay; A.h = h; A.vp = vp; A.vs = vs; A.rho = rho;
     A.periods = periods; A.c = c; A.c_err = c_err; A.out = out;
     BH_HIP(bh::launch_ell(A, (hipStream_t)stream));
+    return BH_OK;
+}
+
+int bh_ell_batch_rows(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                      const double *vs, const double *rho, int nper, const double *periods, int flsph, const double *c,
+                      int c_stride, int *err, int err_stride, int absolute, double *out, int out_stride, const int *order,
+                      int raise_flag, void *stream)
+{
+    if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return bh::fail_arg_("B/Lmax out of range");
+    if (model_stride < Lmax) return bh::fail_arg_("model_stride < Lmax");
+    if (nper < 1 || nper > BH_MAX_PERIODS) return bh::fail_arg_("nper out of range (1 .. 60)");
+    if (c_stride < nper || out_stride < nper) return bh::fail_arg_("c_stride / out_stride shorter than nper");
+    if (err_stride < 1) return bh::fail_arg_("err_stride < 1");
+    if (!nlay || !h || !vp || !vs || !rho || !periods || !c || !err || !out) return bh::fail_arg_("NULL pointer");
+    if (B == 0) return BH_OK;
+    int rc = bh::require_device();
+    if (rc) return rc;
+    bh::EllRowsArgs A;
+    A.B = B; A.Lmax = Lmax; A.nper = nper; A.mstride = model_stride;
+    A.flsph = flsph == 1; A.absolute = absolute != 0;
+    A.c_stride = c_stride; A.err_stride = err_stride; A.out_stride = out_stride;
+    A.raise_flag = raise_flag != 0;
+    A.nlay = nlay; A.h = h; A.vp = vp; A.vs = vs; A.rho = rho;
+    A.periods = periods; A.c = c; A.order = order; A.err = err; A.out = out;
+    BH_HIP(bh::launch_ell_rows(A, (hipStream_t)stream));
     return BH_OK;
 }
 

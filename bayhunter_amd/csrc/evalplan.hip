@@ -90,6 +90,8 @@ struct bh_eval_plan {
     int *gaps = nullptr;          // [nsets][row] columns of the kept samples, then [nsets][T] their counts
                                   // (bh_eval_set_gaps; like_core.h), or null: no set has a gap
     bool gaps_set = false;        // bh_eval_set_gaps has been called (a table without a gap leaves `gaps` null)
+    std::vector<bh_ell_target> ell;   // ellipticity targets (bh_eval_set_ellipticity): one ell_rows_kernel each, behind
+                                      // the dispersion stage on `st`
     bool submitted = false;       // a batch has been submitted: the observations are fixed from then on
     int last_count = 0;           // models of the submission `done` belongs to (set once `done` is recorded)
     bool failed = false;          // the last submission returned an error: nothing to wait for, no results
@@ -396,6 +398,16 @@ static int submit_batch(bh_eval_plan *p, int count, bool *forked)
                             (double)layers / (double)count, p->concurrency, p->out, p->row, p->err, p->swd_ws,
                             p->swd_bytes, p->st, rst, p->nsets, p->rf_set_p, dset)))
         return rc;
+    // The ellipticities: behind the dispersion searches (and the interpolations) on their stream, in front of the
+    // join, so that the receiver functions on the side stream run beside them.  A model without a value gets
+    // BH_ELL_NO_VALUE in its source target's flag, which the likelihood behind the join reads.
+    for (const bh_ell_target &e : p->ell) {
+        const bh_swd_target &src = p->swd[e.src];
+        if ((rc = bh_ell_batch_rows(count, Leff, 4 * L, dnlay, h, vp, vs, rho, e.nper, p->periods + src.per_off, src.iflsph,
+                                    p->out + src.out_off, p->row, p->err + e.src, p->nflags, e.absolute, p->out + e.out_off,
+                                    p->row, order, 1, p->st)))
+            return rc;
+    }
     double *logL = p->dres, *mis = p->dres + count;
     // The dense Gaussian product of a receiver-function target needs that target's columns only: it follows
     // rf_kernel on the side stream, beside this batch's dispersion searches.  Behind the join it was on the critical
@@ -542,6 +554,33 @@ int bh_eval_set_gaps(bh_eval_plan *p, int nsets, const unsigned char *set_presen
         p->gaps = d;
     }
     p->gaps_set = true;
+    return BH_OK;
+}
+
+int bh_eval_set_ellipticity(bh_eval_plan *p, int nell, const bh_ell_target *ell)
+{
+    if (nell < 1 || nell > BH_MAX_TARGETS) return bh::fail_arg_("bh_eval_set_ellipticity: nell outside 1 .. BH_MAX_TARGETS");
+    if (!ell) return bh::fail_arg_("bh_eval_set_ellipticity: NULL pointer (ell)");
+    if (!p) return bh::fail_arg_("plan is NULL");
+    if (p->submitted) return bh::fail_arg_("bh_eval_set_ellipticity: called after bh_eval_submit");
+    if (!p->ell.empty()) return bh::fail_arg_("bh_eval_set_ellipticity: the plan has its ellipticity targets already");
+    for (int i = 0; i < nell; i++) {
+        const bh_ell_target &e = ell[i];
+        const std::string who = "bh_eval_set_ellipticity: ell[" + std::to_string(i) + "].";
+        if (e.src < 0 || e.src >= p->nswd)
+            return bh::fail_arg_((who + "src = " + std::to_string(e.src) + " is outside the plan's " + std::to_string(p->nswd) +
+                                  " dispersion targets").c_str());
+        const bh_swd_target &s = p->swd[e.src];
+        if (s.iwave != 2 || s.igr != 0 || s.mode != 1)
+            return bh::fail_arg_((who + "src names a target that is not the fundamental Rayleigh mode's phase velocity "
+                                  "(iwave 2, igr 0, mode 1)").c_str());
+        if (e.nper < 1 || e.nper > BH_MAX_PERIODS || e.nper != s.nper)
+            return bh::fail_arg_((who + "nper = " + std::to_string(e.nper) + ": 1 .. 60 and the source's (" +
+                                  std::to_string(s.nper) + ")").c_str());
+        if (e.out_off < 0 || e.out_off + e.nper > p->row)
+            return bh::fail_arg_((who + "out_off: the columns lie outside the row").c_str());
+    }
+    p->ell.assign(ell, ell + nell);
     return BH_OK;
 }
 

@@ -101,10 +101,11 @@ def forward_matrix(targets, models, vpvs, mantle=None, device=None, rf_p=None, s
     from .engine import ForwardEngine
     from .models import layers_from_voronoi
     dev = _device.torch_device(device)
-    bl = targets.batch_layout()
+    bl = targets.batch_layout(ell=True)
     lay = bl['layout']
     with torch.cuda.device(dev):
-        eng = ForwardEngine(swd=lay.swd, rf=lay.rf, device=dev)
+        # ell_flags: a row without an ellipticity is flagged, and left out, like a row whose search failed
+        eng = ForwardEngine(swd=lay.swd, rf=lay.rf, device=dev, ell=lay.ell, ell_flags=True)
         rows = _device.to_device(models, torch.float64, dev)
         vpvs = _device.to_device(np.broadcast_to(np.asarray(vpvs, dtype=np.float64), (rows.shape[0],))
                                  if not isinstance(vpvs, torch.Tensor) else vpvs, torch.float64, dev)
@@ -305,7 +306,7 @@ class _DeviceSets(object):
     def __init__(self, stations, mantle, device, rf_p, chunk_bytes=None):
         self.dev = _device.torch_device(device)
         self.joint, self.mantle, self.rf_p, self.chunk_bytes = stations[0], mantle, rf_p, chunk_bytes
-        bl = self.joint.batch_layout()
+        bl = self.joint.batch_layout(ell=True)
         desc, lay = bl['desc'], bl['layout']
         self.segs = [(desc[n].off, desc[n].off + desc[n].n) for n in range(self.joint.ntargets)]
         self.ncols = lay.ncols

@@ -45,9 +45,13 @@ class ForwardEngine(object):
     An ellipticity target (EllSpec) is one more launch, bh_ell_batch, behind the dispersion launch on the same stream:
     it reads the phase velocities of an equal 'rdispph' target of `swd`, or of a hidden one the layout adds behind the
     visible columns (layout.RowLayout).  `err` then has a column per solved dispersion target, the hidden ones last.
+    ell_flags=True launches bh_ell_batch_rows instead, in the run's processing order if it has one: the same values,
+    and a model without an ellipticity (water on top, a half-space alone, a period without a phase velocity) gets
+    BH_ELL_NO_VALUE in its source target's column of `err`, as in an evaluation plan -- the likelihood then refuses
+    the row.  The default leaves `err` as the dispersion launch wrote it.
     """
 
-    def __init__(self, swd=(), rf=(), device=None, ell=()):
+    def __init__(self, swd=(), rf=(), device=None, ell=(), ell_flags=False):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.BayHunterAmdError("no HIP device visible to torch; there is no CPU fallback")
@@ -55,6 +59,7 @@ class ForwardEngine(object):
             else torch.device(device)
         self.layout = lay = RowLayout(swd, rf, ell)
         self.swd, self.rf, self.ell = lay.swd, lay.rf, lay.ell
+        self.ell_flags = bool(ell_flags)
         self._nswd = len(lay.swd_all)        # dispersion targets the library solves: the visible and the hidden ones
         self.slices, self.ncols, self.row = lay.slices, lay.ncols, lay.row
         self._tg, self._rfp = lay.tg, lay.rfp
@@ -188,10 +193,14 @@ class ForwardEngine(object):
                 _lib.check(self.lib.bh_forward_batch_sets(*(args + (set_p.shape[1], set_p.data_ptr(), set_id.data_ptr()))))
             # the ellipticities, behind the dispersion launch on its stream (beside the receiver functions on theirs)
             for e, (t, per_off, c_off), off in zip(self.ell, self.layout.ell_src, self.layout.ell_off):
-                _lib.check(self.lib.bh_ell_batch(
-                    B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(), RHO.data_ptr(),
-                    e.periods.size, self.periods.data_ptr() + 8 * per_off, e.flsph, out.data_ptr() + 8 * c_off, self.row,
-                    err.data_ptr() + 4 * t, max(1, self._nswd), 1 if e.absolute else 0, out.data_ptr() + 8 * off, self.row, sp))
+                args = (B, Lmax, mstride, nlay.data_ptr(), H.data_ptr(), VP.data_ptr(), VS.data_ptr(), RHO.data_ptr(),
+                        e.periods.size, self.periods.data_ptr() + 8 * per_off, e.flsph, out.data_ptr() + 8 * c_off, self.row,
+                        err.data_ptr() + 4 * t, max(1, self._nswd), 1 if e.absolute else 0, out.data_ptr() + 8 * off, self.row)
+                if self.ell_flags:
+                    _lib.check(self.lib.bh_ell_batch_rows(
+                        *(args + (models.order.data_ptr() if models.order is not None else None, 1, sp))))
+                else:
+                    _lib.check(self.lib.bh_ell_batch(*(args + (sp,))))
             if side is not None:
                 st.wait_stream(side)
                 for t in (H, VP, VS, RHO, nlay, out) + (() if rf_sets is None else tuple(rf_sets)):

@@ -18,7 +18,9 @@ def _view(ptr, ctype, count):
 
 
 class EvalPlan(object):
-    """`layout` = JointTarget.batch_layout().  Host views of the plan's pinned staging block:
+    """`layout` = JointTarget.batch_layout(ell=True).  A layout with ellipticity targets gives the plan its hidden
+    dispersion sources and the targets themselves (bh_eval_set_ellipticity): a model without an ellipticity is then
+    refused by the likelihood like a model whose search failed.  Host views of the plan's pinned staging block:
     packed[rows, 4, Lmax], nlay[rows], noise[rows, 2*ntargets], chain[rows]; `submit(count)` evaluates
     the first `count` rows, `wait()` returns (logL[count], misfits[count, ntargets+1]) -- views that stay
     valid until the next submit.
@@ -37,9 +39,19 @@ class EvalPlan(object):
         interp = lay.interp([sp.obsx.ctypes.data for _, _, _, sp in lay.resampled])   # (copied by bh_eval_create)
         self.handle = C.c_void_p()
         _lib.check(self.lib.bh_eval_create(
-            self.rows, self.Lmax, lay.row, len(lay.swd), lay.tg, lay.periods.ctypes.data, lay.periods.size,
+            self.rows, self.Lmax, lay.row, len(lay.swd_all), lay.tg, lay.periods.ctypes.data, lay.periods.size,
             len(lay.rf), lay.rfp, self.T, desc, layout['nflags'], layout['yobs'].ctypes.data, layout['aux'].ctypes.data,
             layout['aux'].size, len(lay.resampled), interp, 1 if use_mfma else 0, C.byref(self.handle)))
+        if lay.ell:                                  # the hidden sources are among swd_all: lay.tg describes them
+            ell = (_lib.EllTarget * len(lay.ell))(*[
+                _lib.EllTarget(t, e.periods.size, off, 1 if e.absolute else 0)
+                for e, (t, _, _), off in zip(lay.ell, lay.ell_src, lay.ell_off)])
+            try:
+                _lib.check(self.lib.bh_eval_set_ellipticity(self.handle, len(lay.ell), ell))
+            except Exception:
+                self.lib.bh_eval_destroy(self.handle)
+                self.handle = None
+                raise
         p = [C.c_void_p() for _ in range(5)]
         _lib.check(self.lib.bh_eval_buffers(self.handle, *[C.byref(x) for x in p]))
         R, L, T = self.rows, self.Lmax, self.T

@@ -145,7 +145,7 @@ def observation_tables(joints, present=False):
     gap; present=True appends present[nsets, row] (uint8, 0 at a gap), or None when no station has one."""
     yobs, scale, logdet, have = [], [], [], []
     for joint in joints:                    # one layout at a time: each carries its dense R^-1 (323 KB at n = 201)
-        bl = joint.batch_layout()
+        bl = joint.batch_layout(ell=True)
         desc, row = bl['desc'], bl['layout'].row
         yobs.append(bl['yobs'])
         have.append(bl['present'])

@@ -269,14 +269,19 @@ class JointTarget(object):
         self.proposalmisfits = self.get_misfits()
 
     # ------------------------------------------------------------------ batched, on the GPU
-    def batch_layout(self):
+    def batch_layout(self, ell=False):
         """What a batched evaluation needs besides device memory (no torch, no device): the row layout of
         the forward kernels (layout.RowLayout), the likelihood descriptors, and the observed data / auxiliary
         arrays (scaled errors, dense R^-1) as host arrays.  Data gaps (SingleTarget.present): `present[row]` holds 0 at
         a missing sample, yobs a finite placeholder (0) and the scaled errors, taken over the kept samples, 1 -- the
-        table an evaluation plan takes in set_gaps.  Nothing non-finite goes to the device on account of a gap."""
-        from .layout import RfSpec, RowLayout, SwdSpec
-        swd, rf, order = [], [], []
+        table an evaluation plan takes in set_gaps.  Nothing non-finite goes to the device on account of a gap.
+
+        ell=True: ellipticity targets (plugins.RayleighEllipticity) are part of the layout -- their columns behind
+        the receiver functions', a hidden dispersion target where no 'rdispph' target solves their phase velocities,
+        and a flag column per solved dispersion target, the hidden ones included (`nflags`).  Every caller in the
+        package asks for them; the call without the argument refuses such a target as it always has."""
+        from .layout import EllSpec, RfSpec, RowLayout, SwdSpec
+        swd, rf, ells, order = [], [], [], []
         for t in self.targets:
             p = t.moddata.plugin
             if isinstance(p, SurfDisp):
@@ -287,10 +292,14 @@ class JointTarget(object):
                 order.append(('rf', len(rf)))
                 rf.append(RfSpec(t.ref, p.obsx, p.modelparams['gauss'], p.modelparams['p'],
                                  p.modelparams['nsv'], wtype=p.modelparams['wtype']))
+            elif ell and isinstance(p, _EllipticityPlugin):
+                order.append(('ell', len(ells)))
+                ells.append(EllSpec(t.ref, p.obsx, p.modelparams['flsph'], p.modelparams['absolute']))
             else:
                 raise TypeError("evaluate_batch supports the built-in SurfDisp / RFminiModRF plugins")
-        lay = RowLayout(swd, rf)
-        slices = [lay.slices[i if kind == 'swd' else len(swd) + i] for kind, i in order]
+        lay = RowLayout(swd, rf, ells)
+        first = {'swd': 0, 'rf': len(swd), 'ell': len(swd) + len(rf)}     # lay.slices: visible swd, then rf, then ell
+        slices = [lay.slices[first[kind] + i] for kind, i in order]
         yobs, present = np.zeros(lay.row), np.ones(lay.row, dtype=np.uint8)
         aux, desc = [], (_lib.LikeTarget * self.ntargets)()
         aux_off = 0
@@ -314,17 +323,18 @@ class JointTarget(object):
             if a is not None:
                 aux.append(np.asarray(a, dtype=np.float64))
                 aux_off += aux[-1].size
-        return dict(layout=lay, desc=desc, nflags=max(1, len(swd)), yobs=yobs, present=present,
+        return dict(layout=lay, desc=desc, nflags=max(1, len(lay.swd_all)), yobs=yobs, present=present,
                     aux=np.ascontiguousarray(np.concatenate(aux) if aux else np.zeros(1), dtype=np.float64))
 
     def _build_batch(self):
         import torch
         from .engine import ForwardEngine
-        bl = self.batch_layout()
+        bl = self.batch_layout(ell=True)
         if not bl['present'].all():
             raise ValueError("a target with data gaps is evaluated by a StationPool(missing='mask'), whose evaluation "
                              "plans carry the gaps (EvalPlan.set_gaps)")
-        eng = ForwardEngine(swd=bl['layout'].swd, rf=bl['layout'].rf)
+        # ell_flags: a model without an ellipticity is flagged, and refused by the likelihood, as an evaluation plan does
+        eng = ForwardEngine(swd=bl['layout'].swd, rf=bl['layout'].rf, ell=bl['layout'].ell, ell_flags=True)
         dev = eng.device
         self._batch = dict(eng=eng, desc=bl['desc'], nflags=bl['nflags'],
                            yobs=torch.from_numpy(bl['yobs']).to(dev), aux=torch.from_numpy(bl['aux']).to(dev))
@@ -334,7 +344,7 @@ class JointTarget(object):
         """An evaluation plan of the library for batches of up to `max_models` proposals of at most `Lmax`
         layers (evalplan.EvalPlan: proposals -> (logL, misfits) in one C call, no torch)."""
         from .evalplan import EvalPlan
-        return EvalPlan(self.batch_layout(), max_models, Lmax, use_mfma=self.use_mfma)
+        return EvalPlan(self.batch_layout(ell=True), max_models, Lmax, use_mfma=self.use_mfma)
 
     def evaluate_batch(self, H, VP=None, VS=None, nlay=None, noise=None, RHO=None, stream=None):
         """Many models at once: `evaluate_batch(models, noise=...)` with resident

@@ -202,6 +202,22 @@ int bh_ell_batch(int B, int Lmax, int model_stride, const int *nlay, const doubl
                  const double *vs, const double *rho, int nper, const double *periods, int flsph, const double *c,
                  int c_stride, const int *c_err, int err_stride, int absolute, double *out, int out_stride,
                  void *stream);
+/* The same values, bit for bit, from a kernel that holds whole models per workgroup (csrc/ell_rows.hip) -- and can
+ * therefore say in the source target's own flag that a model has no ellipticity:
+ *   err, err_stride  row b: err[b * err_stride], read as c_err above.  With raise_flag != 0 the word of a model whose
+ *                    flag was 0 and whose row holds a NaN (water on top, nlay < 2, a period whose c is not a positive
+ *                    finite number) becomes BH_ELL_NO_VALUE; every other word is left unwritten.  raise_flag == 0:
+ *                    err is only read.  The likelihood (bh_likelihood_*) refuses a row with a non-zero flag.
+ *   order            DEVICE int[B], a permutation of 0..B-1, or NULL: slot i of the launch works on model order[i] (the
+ *                    order of the dispersion launch: models of like depth share a workgroup); results land in the
+ *                    model's own row.  Trusted, as in bh_swd_batch_ordered.
+ * Two calls on one source flag: the second reads the first's flag and returns NaN for that model.
+ * BH_ERR_ARG as for bh_ell_batch. */
+#define BH_ELL_NO_VALUE 4
+int bh_ell_batch_rows(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                      const double *vs, const double *rho, int nper, const double *periods, int flsph, const double *c,
+                      int c_stride, int *err, int err_stride, int absolute, double *out, int out_stride,
+                      const int *order, int raise_flag, void *stream);
 
 /* ---- Voronoi nuclei -> layered models + prior checks (device pointers) ------------------- */
 /* The step in front of the forward path: Model.get_vp_vs_h (src/Models.py:26-52) and
@@ -585,6 +601,25 @@ int  bh_eval_set_rf_slowness(bh_eval_plan *plan, int nsets, const double *p);
  * call: a BH_COV_GAUSS target with a gap and a target without a kept sample in some set.  The derived tables belong
  * to the plan and go with it in bh_eval_destroy; a set_present without a gap leaves the plan as it was. */
 int  bh_eval_set_gaps(bh_eval_plan *plan, int nsets, const unsigned char *set_present);
+/* Ellipticity targets for a plan (bh_ell_batch_rows): HOST array, copied.  Target i reads the phase velocities of the
+ * plan's dispersion target `src` -- an index into bh_eval_create's swd[], in which a source that is no datum of its
+ * own is one more target whose columns lie behind the visible ones and that no likelihood target covers -- and writes
+ * nper values at columns out_off ..; periods and iflsph are the source's.  Callable once, between bh_eval_create and
+ * the first bh_eval_submit.  Refused with BH_ERR_ARG and a message naming the field: src out of range; a source that
+ * is not Rayleigh (iwave 2), phase (igr 0), mode 1; nper different from the source's or outside 1 .. BH_MAX_PERIODS;
+ * columns outside the row; nell outside 1 .. BH_MAX_TARGETS.
+ * bh_eval_submit then launches one ell_rows_kernel per target behind the dispersion stage, in the batch's processing
+ * order, beside the receiver functions; a model without an ellipticity (bh_ell_batch_rows) gets BH_ELL_NO_VALUE in the
+ * source's column of the plan's flags, so the likelihood gives the row logL = -1e15 and misfits of 1e15 as it does
+ * for a failed search.  Two targets on one source are allowed: the second sees the first's flag and returns NaN for
+ * that model; the row is refused either way.  A plan without this call queues exactly what it queued before. */
+typedef struct bh_ell_target {
+    int src;       /* index into the plan's dispersion targets                              */
+    int nper;      /* number of periods: the source's                                       */
+    int out_off;   /* first column of the nper ellipticities in the output row              */
+    int absolute;  /* != 0: |H/V|; 0: the signed ratio                                      */
+} bh_ell_target;
+int  bh_eval_set_ellipticity(bh_eval_plan *plan, int nell, const bh_ell_target *ell);
 /* How many plans take turns on the device (a pool's chain groups; default 1): passed on as bh_swd_hint's second
  * argument with every submission. */
 int  bh_eval_set_concurrency(bh_eval_plan *plan, int plans_in_flight);
