@@ -12,11 +12,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "swd_launch.hip", "rf_capi.hip", "like_capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
-           "datafits.hip", "moho.hip", "pairs.hip", "autocov.hip", "depthcov.hip", "math_probe.hip", "rf_probe.hip",
+           "datafits.hip", "moho.hip", "pairs.hip", "autocov.hip", "depthcov.hip", "datacov.hip", "math_probe.hip", "rf_probe.hip",
            "ellipticity.hip", "ell_rows.hip", "ell_capi.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
-           "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "depthcov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h",
+           "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "depthcov_core.h", "datacov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h",
            "ell_core.h", "ell_launch.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
@@ -32,6 +32,7 @@ MAX_DATAFITS_RANKS = 16           # BH_DATAFITS_MAX_RANKS
 PAIRS_MAX, PAIRS_MAX_EDGES, PAIRS_MAX_SETS = 16, 65, 65535      # BH_PAIRS_MAX, BH_PAIRS_MAX_EDGES, BH_PAIRS_MAX_SETS
 AUTOCOV_MAX_LAGS = 4096           # BH_AUTOCOV_MAX_LAGS
 DEPTHCOV_MAX_K, DEPTHCOV_BLOCK_ROWS = 256, 1024     # BH_DEPTHCOV_MAX_K, BH_DEPTHCOV_BLOCK_ROWS
+DATACOV_MAX_S = 1024              # BH_DATACOV_MAX_S
 
 
 class SwdTarget(C.Structure):
@@ -286,6 +287,9 @@ _SIGS = {
                                   _vp]),
     "bh_depthcov_sets": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, C.c_longlong, C.c_int, _vp,
                                    C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "bh_datacov_sets": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, C.c_longlong, C.c_int, _vp,
+                                  C.c_longlong, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, _vp, C.c_int, _vp, C.c_int]
+                        + [_vp] * 10),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -621,6 +621,19 @@ class ChainPool(object):
         from .covariance import pool_depth_covariance
         return pool_depth_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device)
 
+    def data_covariance(self, dep_int=None, extras=('vpvs',), selection='weighted', dev=0.05, exclude_outliers=True,
+                        device=None):
+        """Which depth range a datum constrained in this inversion: the posterior cross-covariance and correlation of the
+        Vs(z) profile and the modelled data over the rows posterior() and datafits() use (datacov.summarize; the
+        reference has no counterpart).  One forward pass as in datafits(); dep_int and `extras` as in depth_covariance().
+        The centres are the two segmented scans' means, the contraction runs on the FP64 matrix cores (bh_datacov_sets).
+        -> dict(cov, corr [K, S], mean_x, std_x [K], mean_y, std_y [S], names ('vs@<z>' per depth, then the extras),
+        targets {ref: the slice of the S data columns that is the target's}, x {ref: obsdata.x}, dep, nmodels, nexcluded
+        (weighted rows left out: failed forward pass or NaN), chains (global indices used)); corr is NaN in the row of a
+        depth and in the column of a datum every model agrees on."""
+        from .datacov import pool_data_covariance
+        return pool_data_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

@@ -222,7 +222,8 @@ def _takes_station(fn):
 class StationView(ChainPool):
     """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
     noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
-    datafits(), moho(), scalars(), convergence(), depth_covariance(), save()`, `targets`, `priors`, `initparams`): views of the pool's arrays, chains numbered from 0."""
+    datafits(), moho(), scalars(), convergence(), depth_covariance(), data_covariance(), save()`, `targets`, `priors`,
+    `initparams`): views of the pool's arrays, chains numbered from 0."""
 
     def __init__(self, pool, s):
         inner, c = pool.pool, pool.chains_per_station
@@ -498,6 +499,21 @@ class StationPool(object):
         from .covariance import stations_depth_covariance
         return stations_depth_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device, strict, max_rows,
                                          budget_bytes)
+
+    def data_covariance(self, dep_int=None, extras=('vpvs',), selection='weighted', dev=0.05, exclude_outliers=True,
+                        device=None, strict=True, max_rows=None):
+        """The posterior cross-covariance and correlation of the Vs(z) profile and the modelled data of every station in
+        one pass (datacov.summarize_sets: one forward pass -- every row at its own station's ray parameter with
+        per_station=('p',) -- two segmented scans for the centres and one bh_datacov_sets call per run of stations).
+        Arguments as station(s).data_covariance(...); per station every field is bit for bit what that returns ('chains'
+        numbered within the station).  -> datacov.StationDataCovariance: `names`, `stations[name]` those dicts, `failed`
+        {name: message}, `columns` ('vs@<z>' per depth, then the extras), `dep`, `targets`, `x`, the stacked `cov / corr
+        [nstations, K, S]`, `mean_x / std_x [nstations, K]`, `mean_y / std_y [nstations, S]`, `nmodels / nexcluded
+        [nstations]`; NaN for a failed station.  strict=True: a failed station is a ValueError naming the first one.
+        max_rows: runs of whole stations of at most that many rows (default: what half of the free device memory holds);
+        no result depends on it."""
+        from .datacov import stations_data_covariance
+        return stations_data_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device, strict, max_rows)
 
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone

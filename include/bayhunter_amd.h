@@ -908,6 +908,43 @@ int  bh_depthcov_sets(const void *rows, int fp64, long long nrows, long long str
                       const double *dep, int ndep, const double *center, double *S, double *r1, long long *total,
                       void *stream);
 
+/* ---- cross moment of Vs(z) and the modelled data for many sets of rows ----------------------- */
+/* What the posterior cross-covariance between the Vs(z) profile and the modelled data needs beyond the two segmented
+ * scans' means: which depth range a datum -- one period of a dispersion curve, one H/V value, one sample of a receiver
+ * function -- moves with across the ensemble.  The rectangular contraction X^T diag(w) Y on v_mfma_f64_16x16x4_f64.
+ *
+ * rows .. nextra   the model side, exactly as for bh_depthcov_sets: K = ndep + nextra <= BH_DEPTHCOV_MAX_K columns
+ * Y             DEVICE float64 [nrows][y_stride], the modelled data (bh_forward_batch's out); the S data columns are
+ *               col0 .. col0 + S - 1; 1 <= S <= BH_DATACOV_MAX_S, col0 >= 0, y_stride >= col0 + S
+ * err           DEVICE int32 [nrows][err_stride], the first nflags flags used (bh_forward_batch's err); NULL with nflags = 0
+ * set_start, dep   as for bh_depthcov_sets
+ * cx, cy        HOST [nsets][K], [nsets][S]: what is subtracted from every row of the set (the means, as the scans
+ *               rounded them; any centres)
+ * C             HOST [nsets][K][S];  r1x, qx HOST [nsets][K];  r1y, qy HOST [nsets][S];  total, excluded HOST [nsets]
+ *
+ * A row counts when its weight is above 0, it has a model, all its nflags flags are 0 and none of its S data values is
+ * NaN (the rows bh_datafits keeps); that is decided once per row, from all S columns, before the contraction.  Over
+ * the rows that count, with dx = fl(x - cx), ex = fl(w dx), dy = fl(y - cy), ey = fl(w dy):
+ *     C[s][k][j] = sum_r ex_rk dy_rj,  r1x = sum_r ex,  r1y = sum_r ey,  qx = sum_r ex dx,  qy = sum_r ey dy,
+ *     total = sum_r w_r;   excluded = the weight of the rows with w_r > 0 that do not count.
+ * The caller forms cov = (C - r1x r1y^T / W) / W and the two variances (q - r1^2 / W) / W with W = total.  A set without
+ * a row that counts has total 0 and zeros.  The order of the sums is bh_depthcov_sets' (csrc/datacov_core.h): blocks of
+ * BH_DEPTHCOV_BLOCK_ROWS rows counted from the set's first row, the rows ascending four per MFMA, the block partials
+ * added in ascending order by one thread per cell.  Two runs are bit-identical; a set's result depends neither on the
+ * other sets of the call nor on where its rows lie; a cell of data column j depends on that column's values and on
+ * which rows count, not on the other columns' values.
+ * BH_DATACOV_MAX_S: a workgroup's LDS holds the data columns of one group of tiles only, so S is not bounded by the
+ * LDS but by the slab of block partials: one block's tiles are Kp x Sp doubles, 2 MiB at K = 256 and S = 1024, of which
+ * the slab of 256 MiB still holds 128 blocks a launch.
+ * All arguments but the weights' sign are checked before any device is touched; the outputs are there when the call
+ * returns. */
+#define BH_DATACOV_MAX_S 1024
+int  bh_datacov_sets(const void *rows, int fp64, long long nrows, long long stride, int width, const int *weights,
+                     const double *extra, long long extra_stride, int nextra, const double *Y, long long y_stride,
+                     int col0, int S, const int *err, long long err_stride, int nflags, const long long *set_start,
+                     int nsets, const double *dep, int ndep, const double *cx, const double *cy, double *C, double *r1x,
+                     double *r1y, double *qx, double *qy, long long *total, long long *excluded, void *stream);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
