@@ -13,11 +13,11 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libbayhunter_amd.so")
 SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "swd_launch.hip", "rf_capi.hip", "like_capi.hip", "evalplan.hip", "chains.cpp", "posterior.hip",
            "datafits.hip", "moho.hip", "pairs.hip", "autocov.hip", "depthcov.hip", "datacov.hip", "math_probe.hip", "rf_probe.hip",
-           "ellipticity.hip", "ell_rows.hip", "ell_capi.hip"]
+           "ellipticity.hip", "ell_rows.hip", "ell_capi.hip", "interfaces.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
            "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "depthcov_core.h", "datacov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h",
-           "ell_core.h", "ell_launch.h"]
+           "ell_core.h", "ell_launch.h", "interfaces_core.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->
@@ -33,6 +33,7 @@ PAIRS_MAX, PAIRS_MAX_EDGES, PAIRS_MAX_SETS = 16, 65, 65535      # BH_PAIRS_MAX, 
 AUTOCOV_MAX_LAGS = 4096           # BH_AUTOCOV_MAX_LAGS
 DEPTHCOV_MAX_K, DEPTHCOV_BLOCK_ROWS = 256, 1024     # BH_DEPTHCOV_MAX_K, BH_DEPTHCOV_BLOCK_ROWS
 DATACOV_MAX_S = 1024              # BH_DATACOV_MAX_S
+INTERFACES_MAX_DEPTH_BINS, INTERFACES_MAX_JUMP_BINS = 1024, 256     # BH_INTERFACES_MAX_DEPTH_BINS, BH_INTERFACES_MAX_JUMP_BINS
 
 
 class SwdTarget(C.Structure):
@@ -290,6 +291,8 @@ _SIGS = {
     "bh_datacov_sets": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, C.c_longlong, C.c_int, _vp,
                                   C.c_longlong, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, _vp, C.c_int, _vp, C.c_int]
                         + [_vp] * 10),
+    "bh_interfaces_sets": (C.c_int, [_vp, C.c_int, C.c_longlong, C.c_longlong, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp,
+                                     C.c_int] + [_vp] * 11),
 }
 EXPORTS = sorted(_SIGS)
 

@@ -578,6 +578,16 @@ class ChainPool(object):
         from .moho import pool_moho
         return pool_moho(self, moho, mohovs, selection, dev, exclude_outliers, nbins, device)
 
+    def interfaces(self, dep_edges=None, jump_edges=None, selection='weighted', dev=0.05, exclude_outliers=True,
+                   device=None):
+        """Discontinuity statistics over the rows posterior() uses (interfaces.summarize): per depth bin of
+        `dep_edges` (default the posterior's own interface edges) the probability that a model has an interface there,
+        a negative one and a positive one (p_interface, p_neg, p_pos), the interface counts, the joint histogram of
+        interface depth and Vs jump over `jump_edges` (default linspace(-2, 2, 41)) and the mean and standard deviation
+        of the jump.  -> summarize()'s dict plus 'chains' (global indices used)."""
+        from .interfaces import pool_interfaces
+        return pool_interfaces(self, dep_edges, jump_edges, selection, dev, exclude_outliers, device)
+
     def scalars(self, selection='weighted', dev=0.05, exclude_outliers=True, nbins=20, pairs=(), pair_bins=50, moho=None,
                 mohovs=4.2, by_chain=False, device=None):
         """The posterior of the sampler's scalar parameters over the rows posterior() uses (scalars.summarize; the

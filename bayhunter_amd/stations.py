@@ -222,7 +222,7 @@ def _takes_station(fn):
 class StationView(ChainPool):
     """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
     noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
-    datafits(), moho(), scalars(), convergence(), depth_covariance(), data_covariance(), save()`, `targets`, `priors`,
+    datafits(), moho(), interfaces(), scalars(), convergence(), depth_covariance(), data_covariance(), save()`, `targets`, `priors`,
     `initparams`): views of the pool's arrays, chains numbered from 0."""
 
     def __init__(self, pool, s):
@@ -454,6 +454,17 @@ class StationPool(object):
         launch (bh_hist2d_sets; nbins <= 64); NaN edges and mode for a hole of the map."""
         from .moho import stations_moho
         return stations_moho(self, moho, mohovs, selection, dev, exclude_outliers, nbins, device, tradeoff)
+
+    def interfaces(self, dep_edges=None, jump_edges=None, selection='weighted', dev=0.05, exclude_outliers=True,
+                   device=None):
+        """The discontinuity section of the network in one pass over the pool's rows (interfaces.summarize_sets): per
+        station and depth bin the probability of an interface, of a negative and of a positive one, and the Vs jump,
+        over edges all stations share.  -> interfaces.StationInterfaces: `names`, `stations` {name: the dict
+        station(s).interfaces(...) returns, field for field}, `p_interface / p_neg / p_pos / jump_mean / count
+        [nstations, depth bins]` (a station without a model is a row of NaN), `dep_edges`, `jump_edges`, `failed`
+        {name: message}."""
+        from .interfaces import stations_interfaces
+        return stations_interfaces(self, dep_edges, jump_edges, selection, dev, exclude_outliers, device)
 
     def scalars(self, selection='weighted', dev=0.05, exclude_outliers=True, nbins=20, pairs=(), pair_bins=50, moho=None,
                 mohovs=4.2, device=None, strict=False, max_rows=None):

@@ -945,6 +945,45 @@ int  bh_datacov_sets(const void *rows, int fp64, long long nrows, long long stri
                      int nsets, const double *dep, int ndep, const double *cx, const double *cy, double *C, double *r1x,
                      double *r1y, double *qx, double *qy, long long *total, long long *excluded, void *stream);
 
+/* ---- discontinuity statistics: interface probability and Vs jump per depth ------------------- */
+/* Where a transdimensional posterior puts its interfaces, and which way Vs steps across them, for every station of a
+ * network in one call.
+ *
+ * rows, fp64, nrows, stride, width   DEVICE rows in the reference's layout as for bh_posterior_sets_create;
+ *               1 <= nrows <= 2^32
+ * weights       DEVICE int32 [nrows] >= 0, or NULL for all ones.  A negative weight anywhere is BH_ERR_ARG
+ * set_start     HOST [nsets + 1] as for bh_moho_sets: set s is rows set_start[s] .. set_start[s + 1], a set may be
+ *               empty; 1 <= nsets <= BH_PAIRS_MAX_SETS
+ * dedges        HOST [ndedges] depth edges, finite and ascending, shared by all sets; nbd = ndedges - 1 depth bins,
+ *               1 <= nbd <= BH_INTERFACES_MAX_DEPTH_BINS
+ * jedges        HOST [njedges] jump edges, finite and ascending, nbj = njedges - 1 <= BH_INTERFACES_MAX_JUMP_BINS; or
+ *               NULL: no joint histogram (hist must then be NULL)
+ *
+ * A row with n nuclei has the interfaces k = 0 .. n-2 at the depths D_k of bh_posterior's walk (z_disc midpoints, the
+ * sequential fp64 cumsum) with the jumps J_k = (double)vs[k+1] - (double)vs[k].  Bins follow numpy's rule as in
+ * bh_datafits_finish (e[i] <= v < e[i+1], the last bin closed); an interface outside dedges adds nothing anywhere.
+ * HOST outputs, each optional, 64-bit counts:
+ *   total [nsets]                      the weight of the set's rows, rows without an interface and all-NaN rows included
+ *   count, neg, pos [nsets][nbd]       the weight of the interfaces in the depth bin; of those with J < 0; with J > 0
+ *   models, models_neg, models_pos     [nsets][nbd] the same, a row counted once per run of consecutive interfaces in
+ *                                      the bin: for depth-sorted rows the weight of the MODELS with such an interface
+ *   hist [nsets][nbd][nbj]             depth bin x jump bin; a jump outside jedges is left out of hist only
+ *   jsum, jsq [nsets][nbd]             sum w J and sum w (J - jsum / count)^2 in fp64: the caller's mean and population
+ *                                      variance of the jump (0 for a bin without an interface)
+ * An empty set, or one of weight 0, is no error: its counts are 0, its jsum and jsq NaN.
+ * The counts are integer sums (privatised in a workgroup's LDS, the depth bins taken in groups when their cells do not
+ * fit it), the two fp64 sums use no floating-point atomic: their order is fixed by the set's rows alone
+ * (csrc/interfaces_core.h).  Two runs are bit-identical, and a set's result is bit for bit that of its rows passed
+ * alone.  All arguments but the weights' sign are checked before any device is touched; the outputs are there when
+ * the call returns. */
+#define BH_INTERFACES_MAX_DEPTH_BINS 1024
+#define BH_INTERFACES_MAX_JUMP_BINS  256
+int  bh_interfaces_sets(const void *rows, int fp64, long long nrows, long long stride, int width, const int *weights,
+                        const long long *set_start, int nsets, const double *dedges, int ndedges, const double *jedges,
+                        int njedges, long long *total, long long *count, long long *models, long long *neg,
+                        long long *pos, long long *models_neg, long long *models_pos, long long *hist, double *jsum,
+                        double *jsq, void *stream);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
