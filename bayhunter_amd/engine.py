@@ -206,3 +206,40 @@ class ForwardEngine(object):
                 for t in (H, VP, VS, RHO, nlay, out) + (() if rf_sets is None else tuple(rf_sets)):
                     t.record_stream(side)
         return out, err
+
+    def sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, target=0, stream=None):
+        """Depth sensitivity kernels of dispersion target `target` for the batch (bh_sens_batch, asynchronous): the
+        polished phase velocity c [B, nper], dc/dT [B, nper] and K [B, nper, 4, Lmax] = dc/dh, dc/dvp, dc/dvs, dc/drho
+        per layer, device tensors in a dict.  `out`, `err`: what run() returned for these models -- the pass reads the
+        engine's own phase velocities -- or None: run() is called first.  Fundamental-mode phase targets on a flat earth
+        with at most 60 periods only; a (model, period) without a value is NaN (include/bayhunter_amd.h)."""
+        models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
+        if not 0 <= target < len(self.layout.swd_all):
+            raise ValueError("target %r: the engine solves %d dispersion targets" % (target, len(self.layout.swd_all)))
+        spec = self.layout.swd_all[target]
+        if spec.igr != 0:
+            raise ValueError("sensitivity: target '%s' has igr = %d; group-velocity targets are not served" % (spec.ref, spec.igr))
+        if spec.mode != 1:
+            raise ValueError("sensitivity: target '%s' has mode = %d; only the fundamental mode is served" % (spec.ref, spec.mode))
+        if spec.flsph != 0:
+            raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (spec.ref, spec.flsph))
+        if spec.resample:
+            raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
+        if out is None or err is None:
+            out, err = self.run(models, stream=stream)
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        B, Lmax, nper = models.B, models.Lmax, spec.periods.size
+        tg = self._tg[target]
+        need = self.lib.bh_sens_workspace_bytes(B, nper)
+        with torch.cuda.stream(st):
+            K = torch.empty((B, nper, 4, Lmax), dtype=torch.float64, device=self.device)
+            c = torch.empty((B, nper), dtype=torch.float64, device=self.device)
+            dc_dT = torch.empty((B, nper), dtype=torch.float64, device=self.device)
+            ws = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.bh_sens_batch(
+                B, Lmax, 4 * Lmax, models.nlay.data_ptr(), models.H.data_ptr(), models.VP.data_ptr(), models.VS.data_ptr(),
+                models.RHO.data_ptr(), spec.iwave, nper, self.periods.data_ptr() + 8 * tg.per_off, 0,
+                out.data_ptr() + 8 * tg.out_off, self.row, err.data_ptr() + 4 * target, max(1, self._nswd), K.data_ptr(),
+                c.data_ptr(), dc_dT.data_ptr(), ws.data_ptr(), ws.numel() * 8, C.c_void_p(st.cuda_stream)))
+        return {'c': c, 'dc_dT': dc_dT, 'K': K}

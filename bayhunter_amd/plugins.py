@@ -96,6 +96,31 @@ class SurfDisp(_Plugin):
             return np.nan, np.nan                               # surf96_modsw.py:126
         return self._to_observed_axis(pers, vel)
 
+    def sensitivity(self, h, vp, vs, rho):
+        """Depth sensitivity kernels of one model through bh_sensitivity: dict c [nper] (the phase velocity as a
+        double-precision root), dc_dT [nper], K [nper, 4, nlayer] = dc/dh, dc/dvp, dc/dvs, dc/drho per layer.  For the
+        fundamental-mode phase targets 'rdispph' and 'ldispph' on a flat earth with at most 60 periods; NaN throughout
+        for a model the search cannot solve (bayhunter_amd.sensitivity has vs_total, group_velocity, to_depth)."""
+        if self.veltype != 0:
+            raise ReferenceError("SurfDisp.sensitivity: ref '%s' is a group-velocity target (igr = %d); kernels are "
+                                 "formed for 'rdispph' and 'ldispph'" % (self.ref, self.veltype))
+        if self.modelparams['mode'] != 1:
+            raise ValueError("SurfDisp.sensitivity: mode = %d; only the fundamental mode is served" % self.modelparams['mode'])
+        if self.modelparams['flsph'] != 0:
+            raise ValueError("SurfDisp.sensitivity: flsph = %d; only a flat earth is served" % self.modelparams['flsph'])
+        if self.kmax > NP_MAX:
+            raise ValueError("SurfDisp.sensitivity: %d periods exceed the solver limit of %d" % (self.kmax, NP_MAX))
+        lib = _lib.load()
+        model32 = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32)) for a in (h, vp, vs, rho)]
+        pers = self._solver_periods()
+        n = len(model32[0])
+        K, c, dc_dT = np.zeros((pers.size, 4, n)), np.zeros(pers.size), np.zeros(pers.size)
+        flag = C.c_int(0)
+        _lib.check(lib.bh_sensitivity(
+            model32[0].ctypes.data, model32[1].ctypes.data, model32[2].ctypes.data, model32[3].ctypes.data, n, 0,
+            self.wavetype, pers.size, pers.ctypes.data, K.ctypes.data, c.ctypes.data, dc_dT.ctypes.data, C.byref(flag)))
+        return {'c': c, 'dc_dT': dc_dT, 'K': K}
+
     def run_models(self, H, VP, VS, RHO, nlay):
         """Batch of models ([B, Lmax] arrays) -> (x, Y[B, nobs], err[B]); unsolved rows are NaN.  More than
         60 periods are interpolated on the device, with run_model's numpy.interp bits."""

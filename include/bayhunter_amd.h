@@ -219,6 +219,29 @@ int bh_ell_batch_rows(int B, int Lmax, int model_stride, const int *nlay, const 
                       int c_stride, int *err, int err_stride, int absolute, double *out, int out_stride,
                       const int *order, int raise_flag, void *stream);
 
+/* ---- batched phase-velocity sensitivity kernels (device pointers) -------------------------- */
+/* dc/dm of the fundamental-mode phase velocity with respect to every layer parameter, by the implicit-function theorem
+ * on the period equation (csrc/sens_core.h): the stored root is polished to a double-precision root of the real*4 model
+ * the search saw, then K = -F_m / F_c and dc/dT = -F_T / F_c from central differences.  Models as for bh_swd_batch;
+ * iwave 1 Love, 2 Rayleigh; periods [nper], 1 <= nper <= BH_MAX_PERIODS.  Fundamental-mode phase targets only.
+ *   c, c_stride, c_err, err_stride   as for bh_ell_batch: what a phase target (igr 0, mode 1, iflsph 0, the same iwave and
+ *                    periods) wrote
+ *   K                [B][nper][4][Lmax]: dc/dh, dc/dvp, dc/dvs, dc/drho per layer (km/s per km, per km/s, per g/cm^3).
+ *                    0 behind a model's last layer, for the half-space's thickness and, for Love waves, for vp
+ *   c_out, dc_dT     [B][nper]: the polished root and its derivative with respect to the period
+ *   workspace        bh_sens_workspace_bytes(B, nper) bytes
+ * A (model, period) without a value is NaN in K (all 4 Lmax entries), c_out and dc_dT: the row's flag is set, nlay is
+ * outside 2 .. Lmax, the top layer is water, c is not a positive finite number, the polished root lies further than
+ * 2e-6 c from c (another root), or F_c vanishes.  Asynchronous on `stream`, behind the call that writes c.
+ * BH_ERR_ARG for flsph != 0 (no derivative is formed through the flattening transformation), iwave, nper out of range,
+ * a NULL pointer, c_stride shorter than nper, err_stride < 1; BH_ERR_WORKSPACE for a workspace that is too small. */
+size_t bh_sens_workspace_bytes(int B, int nper);
+int bh_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                  const double *vs, const double *rho, int iwave /*1 Love, 2 Rayleigh*/, int nper,
+                  const double *periods, int flsph, const double *c, int c_stride, const int *c_err,
+                  int err_stride, double *K /*[B][nper][4][Lmax]: h, vp, vs, rho*/, double *c_out /*[B][nper]*/,
+                  double *dc_dT /*[B][nper]*/, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Voronoi nuclei -> layered models + prior checks (device pointers) ------------------- */
 /* The step in front of the forward path: Model.get_vp_vs_h (src/Models.py:26-52) and
  * SingleChain._validmodel (src/SingleChain.py:330-392) for a batch of proposals.  Input per model:
@@ -349,6 +372,12 @@ int bh_synrf(int nsamp, double fsamp, double tshift, double p, double a, double 
  * entries, 1 <= kmax <= BH_MAX_PERIODS.  *err is the search's flag; when it is set, ell is NaN throughout. */
 int bh_ellipticity(const float *thkm, const float *vpm, const float *vsm, const float *rhom,
                    int nlayer, int iflsph, int kmax, const double *t, int absolute, double *ell, int *err);
+/* Sensitivity kernels of one model: bh_surfdisp96's search (mode 1, igr 0) for the phase velocities, then
+ * bh_sens_batch's pass.  K [kmax][4][nlayer], c_out and dc_dT [kmax].  *err is the search's flag; when it is set,
+ * everything is NaN.  iflsph != 0 is refused (BH_ERR_ARG). */
+int bh_sensitivity(const float *thkm, const float *vpm, const float *vsm, const float *rhom, int nlayer,
+                   int iflsph, int iwave, int kmax, const double *t, double *K /*[kmax][4][nlayer]*/,
+                   double *c_out, double *dc_dT, int *err);
 
 /* ---- the reference's literal FFI symbols ------------------------------------------------ */
 /* Thin aliases of the two drop-ins above under the names the reference's generated glue binds, so that
