@@ -16,6 +16,12 @@
 // central difference, at most SENS_NEWTON steps, until |dc| <= 2^-50 c.  The bracket held the root, so a polished
 // root further than SENS_ACCEPT c0 from the stored c0 is another root and the (model, period) has no value.
 //
+// Where c lies next to the vs of a finite layer the accuracy of all this drops: on the hyperbolic side swd_var and
+// swd_love_layer form (1 - exp(-2q)) / 2 with an absolute error of 2^-54 whatever q is, and q vanishes at the crossing.
+// With c on that vs the polished root is within 1e-11 of the exact one instead of 5e-16; with c, or c one step of the
+// differences over c and the velocities away from it, every value loses three digits and the crossed layer's own
+// dc/dvs up to five.  From |c / vs - 1| = 2^-16 outward nothing of it is left (tests/sensitivity_tolerances.py).
+//
 // One whole recursion per evaluation: 3 per Newton step, 4 for F_c and F_T, 2 per slot; O(L^2) per (model, period).
 // The prefix / suffix form that makes it O(L) is not attempted here.
 //

@@ -42,6 +42,117 @@ CASES = [(name, wave) for name in MODELS for wave in ('rayleigh', 'love')]
 NO_VALUE = ('water', 'flag', 'c_zero', 'c_moved')
 
 
+# ---- models outside the list the tolerances were tuned on --------------------------------------------------------------------
+def deepen(model, n, spread=0.01):
+    """`model` cut to n layers: the thickest finite layer (the first of equals) is halved until there are n, then the
+    pieces of one original layer get its vs times 1 + spread * (position - 1/2), position (k + 1/2) / pieces from the
+    top, so that the result is another model and, for spread below the smallest relative vs step, still increasing
+    wherever `model` is.  vp and rho follow vs as in _model."""
+    h, owner = list(np.asarray(model[0], dtype=np.float64)), list(range(len(model[0])))
+    assert n >= len(h)
+    while len(h) < n:
+        j = int(np.argmax(h[:-1]))
+        h[j:j + 1] = [h[j] / 2, h[j] / 2]
+        owner[j:j + 1] = [owner[j], owner[j]]
+    owner = np.array(owner)
+    vs = np.asarray(model[2], dtype=np.float64)[owner]
+    for o in set(owner):
+        at = np.nonzero(owner == o)[0]
+        vs[at] *= 1.0 + spread * ((np.arange(at.size) + 0.5) / at.size - 0.5)
+    return _model(vs, h)
+
+
+def halve_layer(model, i):
+    """Layer i cut into two layers of half its thickness (exact in real*4) with the same vp, vs and rho."""
+    out = []
+    for k, x in enumerate(model):
+        x = list(np.asarray(x, dtype=np.float64).astype(np.float32).astype(np.float64))
+        x[i:i + 1] = [x[i] / 2, x[i] / 2] if k == 0 else [x[i], x[i]]
+        out.append(np.array(x))
+    return tuple(out)
+
+
+def _drawn(row):
+    from bayhunter_amd.synthetic import draw_models
+    H, VP, VS, RHO, nlay = draw_models(4, (10, 10), seed=5, sorted_vs=True)
+    return tuple(x[row, :nlay[row]].copy() for x in (H, VP, VS, RHO))
+
+
+def _lvz_fixture(case, row):
+    z = np.load(os.path.join(ROOT, 'tests', 'golden', 'lvz_worst_cases.npz'))
+    n = int(z['c%d_nl' % case][row])
+    return tuple(z['c%d_%s' % (case, k)][row, :n].astype(np.float64) for k in ('H', 'VP', 'VS', 'RHO'))
+
+
+# The second list, on which no step and no tolerance was tuned: two seeded 10-layer draws (the depth of
+# tools/sensitivity_bench.py), L8 cut to 18 layers, and the 23-layer model of tests/golden/lvz_worst_cases.npz (case 2,
+# row 0: vs jumps between 2.1 and 5.0 km/s from layer to layer over a half-space of 4.80 km/s, which only one 3 km layer
+# of 4.97 km/s exceeds -- none of the fixture's 13 models has a half-space faster than every layer; three have water on
+# top).  Two periods each.
+OFFLIST = {
+    'draw0': _drawn(0),
+    'draw1': _drawn(1),
+    'L8x18': deepen(MODELS['L8'], 18),
+    'lvz23': _lvz_fixture(2, 0),
+}
+OFFLIST_PERIODS = np.array([2., 20.])
+OFFLIST_CASES = [(name, wave) for name in OFFLIST for wave in ('rayleigh', 'love')]
+
+
+# ---- branch crossings ---------------------------------------------------------------------------------------------------------
+def period_at(twin, model, wave, target, lo=0.3, hi=150.0):
+    """The period at which the twin's polished c is `target`, by bisection in [lo, hi] (c rises with T there: the caller
+    checks the ends).  None when target is not between the ends."""
+    def c_of(T):
+        r = twin.sensitivity(*model, np.array([T]), wave)
+        return r['c'][0] if r['err'] == 0 else np.nan
+    clo, chi = c_of(lo), c_of(hi)
+    if not (clo < target < chi):
+        return None
+    for _ in range(80):
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            break
+        if c_of(mid) < target:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+# Periods at which the twin's polished c equals the real*4 vs of layer i of the model: (model, wave, i) -> T, found with
+# period_at and, since the polished c scatters by 1e-12 there, the closest of T (1 + j 2e-14), |j| <= 60, around its
+# result (test_sensitivity checks that they still land there).  Every finite layer of L3, L8 and lvz whose vs a
+# fundamental mode of 0.3 .. 150 s reaches.
+CROSSINGS = {                                               # c / vs - 1 of the twin's polished c
+    ('L3', 'rayleigh', 0): 3.106365031876115,               # 1.9e-14
+    ('L3', 'rayleigh', 1): 15.856311632649065,              # 4.1e-14
+    ('L3', 'love', 1): 11.176906739659756,                  # 0
+    ('L8', 'rayleigh', 0): 1.1298063783413355,              # 3.0e-14
+    ('L8', 'rayleigh', 1): 3.8000739329604443,              # 4.4e-16
+    ('L8', 'rayleigh', 2): 7.636639430141306,               # 1.6e-15
+    ('L8', 'rayleigh', 3): 14.035143812324192,              # 1.5e-14
+    ('L8', 'rayleigh', 4): 20.15693409653462,               # 7.5e-15
+    ('L8', 'rayleigh', 5): 26.442624149820386,              # 2.7e-14
+    ('L8', 'rayleigh', 6): 89.88506292908889,               # 2.3e-15
+    ('L8', 'love', 1): 2.8434721641243734,                  # 5.6e-15
+    ('L8', 'love', 2): 6.209414292554386,                   # 0
+    ('L8', 'love', 3): 11.44802595181374,                   # 2.2e-15
+    ('L8', 'love', 4): 17.090495870608706,                  # 2.9e-15
+    ('L8', 'love', 5): 21.69399449903746,                   # 6.7e-16
+    ('L8', 'love', 6): 30.910808278834722,                  # 0
+    ('lvz', 'rayleigh', 0): 2.407837374390026,              # 2.5e-14
+    ('lvz', 'rayleigh', 1): 18.57665705407409,              # 8.9e-16
+    ('lvz', 'rayleigh', 2): 9.691488869320105,              # 6.3e-15
+    ('lvz', 'rayleigh', 3): 26.84235627779169,              # 1.6e-15
+    ('lvz', 'love', 1): 12.535927041933116,                 # 1.3e-15
+    ('lvz', 'love', 2): 2.045798250330698,                  # 6.7e-16
+    ('lvz', 'love', 3): 20.848236841826353,                 # 7.1e-15
+}
+# the distances c / vs - 1 at which the comparison is repeated on either side
+CROSSING_DISTANCES = (2.0 ** -24, 2.0 ** -20, 2.0 ** -16, 2.0 ** -12)
+
+
 def load_sim():
     so = os.path.join(HOSTSIM, 'libsens_sim.so')
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in SIM_SRCS):

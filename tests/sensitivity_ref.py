@@ -56,8 +56,8 @@ def love_secular(h, vp, vs, rho, period, c):
         nu2 = k * k - (om / vs[i]) ** 2
         if nu2 > 0:
             nu = np.sqrt(nu2)
-            e = np.exp(-2 * nu * h[i])
-            C, S = (1 + e) / 2, (1 - e) / (2 * nu)         # cosh, sinh / nu, both times exp(-nu d) > 0
+            e1 = np.expm1(-2 * nu * h[i])                  # (1 - e needs it where c has just fallen below this layer's vs)
+            C, S = (2 + e1) / 2, -e1 / (2 * nu)            # cosh, sinh / nu, both times exp(-nu d) > 0
         elif nu2 < 0:
             q = np.sqrt(-nu2)
             C, S = np.cos(q * h[i]), np.sin(q * h[i]) / q
