@@ -644,6 +644,20 @@ class ChainPool(object):
         from .datacov import pool_data_covariance
         return pool_data_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device)
 
+    def sensitivity(self, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                    exclude_outliers=True, device=None, max_rows=None):
+        """Where in depth the dispersion data look across the ensemble: the phase-velocity sensitivity kernel of every
+        row posterior() uses, spread over the depth bins `dep_edges` (default interfaces()'s, 1 km to 100 km), and per
+        period and bin its mean, standard deviation, minimum and maximum over the weighted rows
+        (sensitivity.summarize: the search, the pass and the reduction bh_sens_sets_* on the device).  `ref` picks the
+        dispersion target (default: the pool's only fundamental-mode phase target); kind 'vs_total' (vp and rho moving
+        with vs, as the sampler moves them), 'vp', 'vs' or 'rho'.  data_covariance() answers the same question
+        statistically.  -> dict(mean, std, min, max [nper, bins], halfspace_mean, halfspace_std, nmodels, nexcluded
+        [nper], periods, edges, kind, ref, chains (global indices used)).  ValueError for a pool without a dispersion
+        target and for a group-velocity, higher-mode, flattened-earth or more-than-60-period target."""
+        from .sensitivity import pool_sensitivity
+        return pool_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

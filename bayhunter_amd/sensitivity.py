@@ -7,8 +7,20 @@ period, for Rayleigh and Love waves (csrc/sens_core.h).
     to_depth(K, h, edges)                        a layer kernel spread over depth bins
 
 Per model: plugins.SurfDisp.sensitivity; on an engine's own phase velocities: ForwardEngine.sensitivity.
+
+Over an ensemble -- where in depth the data look across all sampled models, and how much that varies between them:
+
+    summarize(periods, wave, models, vpvs, ...)          mean, spread, minimum and maximum of the depth-binned kernel
+    summarize_sets(periods, wave, models, set_start, ..) the same for every set of rows (a station) in one pass
+    from_sums(total, s1, s2, vmin, vmax)                 the rules, without a device
+    ChainPool.sensitivity / StationPool.sensitivity      over a pool's rows (pool_sensitivity, stations_sensitivity)
+
+Per row the device runs the search, the pass (bh_sens_batch) and the reduction bh_sens_sets_* (csrc/sens_sets_core.h);
+K never leaves the device.
 """
 import numpy as np
+
+from . import _lib, selection as sel
 
 KINDS = ('h', 'vp', 'vs', 'rho')          # K's kind axis
 REFS = {'rayleigh': 'rdispph', 'love': 'ldispph'}
@@ -62,3 +74,303 @@ def to_depth(K, h, edges):
     with np.errstate(divide='ignore', invalid='ignore'):
         w = np.where(h[:n - 1, None] > 0, np.clip(hi - lo, 0.0, None) / h[:n - 1, None], 0.0)      # [L-1, nbins]
     return K[..., :n - 1] @ w, K[..., n - 1]
+
+
+# ---- over an ensemble: the depth-binned kernel's moments per set of rows ---------------------------------------------
+
+_EMPTY = "empty selection (no row with a value at any period)"
+
+
+def from_sums(total, s1, s2, vmin, vmax):
+    """Mean and population standard deviation from bh_sens_sets_finish's sums: total [..., nper] = sum w, s1 = sum w x,
+    s2 = sum w x^2, vmin, vmax [..., nper, cells] -> (mean, std) [..., nper, cells]:
+
+        mean = s1 / W,  std = sqrt(max(0, s2 / W - mean^2))
+
+    The variance is exactly 0 where vmin == vmax (every row agrees), whatever the rounding left in s2.  A period with
+    W == 0 is NaN."""
+    W = np.asarray(total, dtype=np.float64)[..., None]
+    s1, s2 = np.asarray(s1, dtype=np.float64), np.asarray(s2, dtype=np.float64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        mean = np.where(W > 0, s1 / W, np.nan)
+        var = np.maximum(0.0, s2 / W - mean * mean)
+    var = np.where(np.asarray(vmin) == np.asarray(vmax), 0.0, var)
+    return mean, np.where(W > 0, np.sqrt(var), np.nan)
+
+
+def default_edges():
+    """The depth edges interfaces.summarize uses by default: 1 km bins to 100 km."""
+    from .posterior import hist_grids
+    return hist_grids(None)[1]
+
+
+def _check_edges(dep_edges):
+    e = np.ascontiguousarray(default_edges() if dep_edges is None else dep_edges, dtype=np.float64)
+    if e.ndim != 1 or e.size < 2 or e.size > _lib.SENS_SETS_MAX_BINS + 1:
+        raise ValueError("dep_edges: 2 to %d edges" % (_lib.SENS_SETS_MAX_BINS + 1))
+    if not np.all(np.isfinite(e)) or np.any(np.diff(e) <= 0):
+        raise ValueError("dep_edges: finite and ascending")
+    return e
+
+
+def _check_kind(kind):
+    if kind not in _lib.SENS_KINDS:
+        raise ValueError("kind %r: 'vp', 'vs', 'rho' or 'vs_total' (dc/dh is an interface derivative, not a depth density)"
+                         % (kind,))
+    return _lib.SENS_KINDS[kind]
+
+
+def split_runs(set_start, max_rows):
+    """The rows of set_start cut into runs (lo, hi) of at most max_rows rows that bh_sens_sets_add accepts one after the
+    other: whole sets as long as they fit; a set larger than max_rows is split at multiples of the block
+    (_lib.SENS_SETS_BLOCK_ROWS rows from its first row; one block at least)."""
+    set_start = np.asarray(set_start, dtype=np.int64)
+    blk, R, max_rows = _lib.SENS_SETS_BLOCK_ROWS, int(set_start[-1]), max(1, int(max_rows))
+    runs, lo = [], 0
+    while lo < R:
+        fits = set_start[(set_start > lo) & (set_start <= lo + max_rows)]
+        if fits.size:
+            hi = int(fits[-1])
+        else:                                   # the set lo lies in does not fit: whole blocks of it
+            z = int(np.searchsorted(set_start, lo, side='right')) - 1
+            first, end = int(set_start[z]), int(set_start[z + 1])
+            hi = min(end, first + max(blk, (lo + max_rows - first) // blk * blk))
+            if hi <= lo:
+                hi = min(end, lo + blk)
+        runs.append((lo, hi))
+        lo = hi
+    return runs
+
+
+class SensSets(object):
+    """One bh_sens_sets handle: add(row0, models, K, c, q, weights) run after run, then finish()."""
+
+    def __init__(self, set_start, nper, edges, kind, drho_dvp, stream):
+        import ctypes as C
+        self.lib = _lib.load()
+        self.set_start = np.ascontiguousarray(set_start, dtype=np.int64)
+        self.nsets, self.nper, self.edges = self.set_start.size - 1, int(nper), np.ascontiguousarray(edges, dtype=np.float64)
+        self.h = C.c_void_p()
+        _lib.check(self.lib.bh_sens_sets_create(C.byref(self.h), self.set_start.ctypes.data, self.nsets, self.nper,
+                                                self.edges.ctypes.data, self.edges.size, int(kind), float(drho_dvp), stream))
+
+    def add(self, row0, models, K, c, q=None, weights=None):
+        """Rows row0 .. of the numbering: models an engine.DeviceModels, K and c what ForwardEngine.sensitivity returned
+        for them, q [B, Lmax] float64 or None, weights int32 [B] or None -- device tensors."""
+        _lib.check(self.lib.bh_sens_sets_add(
+            self.h, int(row0), models.B, models.Lmax, 4 * models.Lmax, models.nlay.data_ptr(), models.H.data_ptr(),
+            None if q is None else q.data_ptr(), 0 if q is None else q.stride(0), K.data_ptr(), c.data_ptr(),
+            None if weights is None else weights.data_ptr()))
+
+    def finish(self):
+        """-> dict(total, excluded [sets, nper] int64, s1, s2, vmin, vmax [sets, nper, bins + 1])"""
+        Z, P, C1 = self.nsets, self.nper, self.edges.size
+        out = dict(total=np.zeros((Z, P), dtype=np.int64), excluded=np.zeros((Z, P), dtype=np.int64))
+        for k in ('s1', 's2', 'vmin', 'vmax'):
+            out[k] = np.zeros((Z, P, C1))
+        _lib.check(self.lib.bh_sens_sets_finish(self.h, *[out[k].ctypes.data for k in
+                                                          ('total', 'excluded', 's1', 's2', 'vmin', 'vmax')]))
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.bh_sens_sets_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _result(sums, z, periods, edges, kind):
+    """summarize()'s dict of set z, or None for a set without a counting row at any period."""
+    total = sums['total'][z]
+    if not total.any():
+        return None
+    mean, std = from_sums(total, sums['s1'][z], sums['s2'][z], sums['vmin'][z], sums['vmax'][z])
+    return {'mean': mean[:, :-1], 'std': std[:, :-1], 'min': sums['vmin'][z][:, :-1].copy(),
+            'max': sums['vmax'][z][:, :-1].copy(), 'halfspace_mean': mean[:, -1], 'halfspace_std': std[:, -1],
+            'nmodels': total.copy(), 'nexcluded': sums['excluded'][z].copy(), 'periods': periods, 'edges': edges,
+            'kind': kind}
+
+
+def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None,
+                   device=None, max_rows=None, strict=True, drho_dvp=0.32):
+    """summarize() of every set of rows in one pass: set s is models[set_start[s]:set_start[s + 1]] (set_start
+    [sets + 1], ascending from 0 to the number of rows; a set may be empty) with its vpvs and weights.
+
+    periods, wave   up to 60 periods of the fundamental-mode phase velocity; 'rayleigh' or 'love'
+    models          [rows, 2*maxlayers], the reference's layout (float32 or float64; numpy or a torch tensor)
+    vpvs, mantle    one vp/vs per row, or a scalar; the prior's (vs, vpvs) mantle rule, as for datacov.summarize
+    weights         integers >= 0, default 1 each
+    dep_edges       depth bin edges shared by all sets (default: interfaces.summarize's, 1 km bins to 100 km)
+    kind            'vs_total' (dc/dvs with vp = vpvs vs and rho = 0.77 + drho_dvp vp moving along), 'vp', 'vs' or 'rho'
+    max_rows        the rows are taken in runs of whole sets that fit max_rows, a larger set in whole blocks (default:
+                    what half of the free device memory holds); per run the layers, the search, the pass
+                    (ForwardEngine.sensitivity), q = vp / vs and bh_sens_sets_add; no result depends on it
+
+    -> a selection.SetList of dicts(mean, std, min, max [nper, bins]: km/s per km/s (per g/cm^3 for 'rho') of the layer
+    kernel that falls into the bin; halfspace_mean, halfspace_std [nper]; nmodels, nexcluded [nper] (weighted rows that
+    count; left out: no model, a failed search, no root); periods, edges, kind), every field bit for bit what summarize
+    returns for the set's rows alone.  A set without a row that counts at any period raises a ValueError naming the
+    first such set -- or, with strict=False, has the entry None and its message in the list's `failed`."""
+    import torch
+    from . import _device, datafits as df
+    from .engine import ForwardEngine, SwdSpec
+    from .models import layers_from_voronoi
+    if wave not in REFS:
+        raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
+    code, edges = _check_kind(kind), _check_edges(dep_edges)
+    periods = np.ascontiguousarray(periods, dtype=np.float64)
+    shape = getattr(models, 'shape', None) or np.asarray(models).shape
+    if len(shape) != 2:
+        raise ValueError("models: [rows, 2*maxlayers]")
+    R = shape[0]
+    set_start, Z = sel.check_set_start(set_start, R)
+    vp = None if np.ndim(vpvs) == 0 else vpvs
+    if vp is not None and len(vp) != R:
+        raise ValueError("vpvs: one per row, or a scalar")
+    if weights is not None and len(weights) != R:
+        raise ValueError("one weight per row")
+    if weights is not None and not hasattr(weights, 'is_cuda') and np.any(np.asarray(weights) < 0):
+        raise ValueError("negative weight")
+    if max_rows is not None and int(max_rows) < 1:
+        raise ValueError("max_rows >= 1")
+    if periods.ndim != 1 or periods.size < 1:
+        raise ValueError("periods: one at least")
+    spec = SwdSpec(REFS[wave], periods)
+    if spec.resample:
+        raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
+    results, failed = [None] * Z, {}
+    if R == 0:
+        failed = {z: "empty selection: no models" for z in range(Z)}
+        sel.raise_first_failed(failed, strict, "set")
+        return sel.SetList(results, failed)
+    dev = _device.torch_device(device)
+    with torch.cuda.device(dev):
+        eng = ForwardEngine(swd=[spec], device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        Lmax, nper = shape[1] // 2, periods.size
+        if max_rows is None:       # half of the free device memory: K, c, dc/dT and the workspace, the row, its layers
+            per_row = 8 * (4 * nper * Lmax + 3 * nper + eng.row + shape[1] + 8 * Lmax) + 16      # (packed, nuclei, q)
+            max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
+        with SensSets(set_start, nper, edges, code, drho_dvp, stream) as handle:
+            for lo, hi in split_runs(set_start, max_rows):
+                rows = _device.to_device(models[lo:hi], torch.float64, dev)
+                v = vpvs if vp is None else vp[lo:hi]
+                v = _device.to_device(np.broadcast_to(np.asarray(v, dtype=np.float64), (hi - lo,)).copy()
+                                      if not isinstance(v, torch.Tensor) else v, torch.float64, dev)
+                w = None if weights is None else _device.to_device(weights[lo:hi], torch.int32, dev)
+                vsn, zv, nl = df._layers(rows, dev)
+                dm, _ = layers_from_voronoi(vsn, zv, nl, v, df._OPEN_PRIORS, mantle=mantle, device=dev)
+                out, err = eng.run(dm)
+                res = eng.sensitivity(dm, out=out, err=err)
+                q = (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None
+                handle.add(lo, dm, res['K'], res['c'], q, w)
+            sums = handle.finish()
+    for z in range(Z):
+        results[z] = _result(sums, z, periods, edges, kind)
+        if results[z] is None:
+            failed[z] = "empty selection: no models" if set_start[z] == set_start[z + 1] else _EMPTY
+    sel.raise_first_failed(failed, strict, "set")
+    return sel.SetList(results, failed)
+
+
+def summarize(periods, wave, models, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None, device=None,
+              max_rows=None, drho_dvp=0.32):
+    """The depth-binned sensitivity kernel over one set of sampled models: summarize_sets' dict for all rows (see there).
+    ValueError for an empty selection."""
+    shape = getattr(models, 'shape', None) or np.asarray(models).shape
+    res = summarize_sets(periods, wave, models, [0, shape[0] if len(shape) == 2 else 0], vpvs, weights, dep_edges, kind,
+                         mantle, device, max_rows, strict=False, drho_dvp=drho_dvp)
+    if res[0] is None:
+        raise ValueError(res.failed[0])
+    return res[0]
+
+
+# ---- chain pools ----------------------------------------------------------------------------------------------------------
+
+def pool_target(targets, ref=None):
+    """The dispersion target of a JointTarget the kernels are formed for -> (wave, periods).  ref None: its only
+    fundamental-mode phase target.  ValueError for a pool without a dispersion target, an ambiguous choice, and -- in
+    ForwardEngine.sensitivity's words -- a target the pass does not serve."""
+    from .layout import SWD_REFS
+    specs = targets.batch_layout(ell=True)['layout'].swd
+    if not specs:
+        raise ValueError("sensitivity: the pool has no dispersion target")
+    if ref is None:
+        served = [sp for sp in specs if sp.igr == 0 and sp.mode == 1]
+        if len(served) > 1:
+            raise ValueError("sensitivity: ref is one of %s" % ', '.join(repr(sp.ref) for sp in served))
+        spec = served[0] if served else specs[0]
+    else:
+        if ref not in SWD_REFS or not any(sp.ref == ref for sp in specs):
+            raise ValueError("sensitivity: no dispersion target %r (there are %s)" % (ref, ', '.join(sp.ref for sp in specs)))
+        spec = next(sp for sp in specs if sp.ref == ref)
+    if spec.igr != 0:
+        raise ValueError("sensitivity: target '%s' has igr = %d; group-velocity targets are not served" % (spec.ref, spec.igr))
+    if spec.mode != 1:
+        raise ValueError("sensitivity: target '%s' has mode = %d; only the fundamental mode is served" % (spec.ref, spec.mode))
+    if spec.flsph != 0:
+        raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (spec.ref, spec.flsph))
+    if spec.resample:
+        raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
+    return {v: k for k, v in REFS.items()}[spec.ref], spec.periods
+
+
+def pool_sensitivity(pool, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                     exclude_outliers=True, device=None, max_rows=None):
+    """ChainPool.sensitivity: summarize() over the rows ChainPool.posterior uses, plus 'ref' and 'chains' (global
+    indices used)."""
+    wave, periods = pool_target(pool.targets, ref)
+    ci, ri, w = sel.pool_rows(pool, selection, dev, exclude_outliers)
+    res = summarize(periods, wave, pool.models[ci, ri], pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32),
+                    dep_edges, kind, pool.priors.get('mantle'), device, max_rows)
+    res['ref'] = REFS[wave]
+    res['chains'] = np.unique(ci) + pool.first
+    return res
+
+
+class StationSensitivity(sel.StationResult):
+    """StationPool.sensitivity's result, every array in the pool's station order.
+
+    names, failed    the stations; {station name: message} (such a station is NaN throughout)
+    stations         {station name: the dict pool.station(name).sensitivity(...) returns}, failed stations left out
+    ref, periods, edges, kind   the target, its periods and the depth edges all stations share
+    mean, std, min, max [nstations, nper, bins], halfspace_mean, halfspace_std [nstations, nper] (float64, NaN for a
+    failed station), nmodels, nexcluded [nstations, nper] (0 for a failed station)"""
+
+    def __init__(self, names, results, failed, ref, periods, edges, kind):
+        sel.StationResult.__init__(self, names, failed)
+        self.stations = {n: r for n, r in zip(names, results) if r is not None}
+        self.ref, self.periods, self.edges, self.kind = ref, periods, edges, kind
+        Z, P, nb = len(results), periods.size, edges.size - 1
+        for k in ('mean', 'std', 'min', 'max'):
+            setattr(self, k, np.full((Z, P, nb), np.nan))
+        self.halfspace_mean, self.halfspace_std = np.full((Z, P), np.nan), np.full((Z, P), np.nan)
+        self.nmodels, self.nexcluded = np.zeros((Z, P), dtype=np.int64), np.zeros((Z, P), dtype=np.int64)
+        for z, r in enumerate(results):
+            if r is not None:
+                for k in ('mean', 'std', 'min', 'max', 'halfspace_mean', 'halfspace_std', 'nmodels', 'nexcluded'):
+                    getattr(self, k)[z] = r[k]
+
+
+def stations_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                         exclude_outliers=True, device=None, max_rows=None, strict=False):
+    """StationPool.sensitivity: summarize_sets() over every station's main-phase rows."""
+    pool, c = spool.pool, spool.chains_per_station
+    wave, periods = pool_target(spool.stations[0], ref)
+    edges = _check_edges(dep_edges)
+    ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
+    res = summarize_sets(periods, wave, pool.models[ci, ri], set_start, pool.vpvs[ci, ri].astype(np.float64),
+                         w.astype(np.int32), edges, kind, pool.priors.get('mantle'), device, max_rows, strict=False)
+    for z, msg in res.failed.items():
+        failed.setdefault(z, msg)
+    sel.raise_first_failed(failed, strict, "station", spool.names)
+    for z, r in enumerate(res):
+        if r is not None:
+            r['ref'] = REFS[wave]
+            r['chains'] = sel.station_chains(ci, set_start, z, c)
+    return StationSensitivity(spool.names, res, failed, REFS[wave], periods, edges, kind)

@@ -222,7 +222,7 @@ def _takes_station(fn):
 class StationView(ChainPool):
     """The chains of one station of a StationPool behind the interface of a ChainPool (`models, misfits, likes,
     noise, vpvs, iter, nchains, first, counters(), chain(i), weighted(i), final(), outliers(), posterior(),
-    datafits(), moho(), interfaces(), scalars(), convergence(), depth_covariance(), data_covariance(), save()`, `targets`, `priors`,
+    datafits(), moho(), interfaces(), scalars(), convergence(), depth_covariance(), data_covariance(), sensitivity(), save()`, `targets`, `priors`,
     `initparams`): views of the pool's arrays, chains numbered from 0."""
 
     def __init__(self, pool, s):
@@ -525,6 +525,20 @@ class StationPool(object):
         no result depends on it."""
         from .datacov import stations_data_covariance
         return stations_data_covariance(self, dep_int, extras, selection, dev, exclude_outliers, device, strict, max_rows)
+
+    def sensitivity(self, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                    exclude_outliers=True, device=None, max_rows=None, strict=False):
+        """The posterior mean and spread of the depth-binned phase-velocity sensitivity kernel of every station in one
+        pass (sensitivity.summarize_sets: per run of rows the search, the pass and bh_sens_sets_add on one handle).
+        Arguments as station(s).sensitivity(...); per station every field is bit for bit what that returns ('chains'
+        numbered within the station).  -> sensitivity.StationSensitivity: `names`, `stations[name]` those dicts,
+        `failed` {name: message}, `ref`, `periods`, `edges`, `kind`, the stacked `mean / std / min / max [nstations,
+        nper, bins]`, `halfspace_mean / halfspace_std / nmodels / nexcluded [nstations, nper]`; NaN for a failed
+        station.  strict=True: a failed station is a ValueError naming the first one.  max_rows: runs of whole stations
+        of at most that many rows, a larger station in whole blocks (default: what half of the free device memory
+        holds); no result depends on it."""
+        from .sensitivity import stations_sensitivity
+        return stations_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, strict)
 
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone

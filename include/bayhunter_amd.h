@@ -1013,6 +1013,61 @@ int  bh_interfaces_sets(const void *rows, int fp64, long long nrows, long long s
                         long long *pos, long long *models_neg, long long *models_pos, long long *hist, double *jsum,
                         double *jsq, void *stream);
 
+/* ---- posterior sensitivity kernels: depth-binned dc/dm per set, period and depth cell ------------------- */
+/* Where in depth the data look across an ensemble, and how much that varies between the sampled models: the layer kernel
+ * bh_sens_batch wrote for every row, spread over depth bins all rows share, and its moments per set of rows (a station).
+ * The rows may not fit the device together with their K, so they arrive in several calls on a handle.
+ *
+ * create  set_start     HOST [nsets + 1] as for bh_moho_sets, in a global row numbering: set s is rows set_start[s] ..
+ *                       set_start[s + 1], a set may be empty; 1 <= nsets <= BH_PAIRS_MAX_SETS
+ *         nper          periods of every row's K and c_out, 1 .. BH_MAX_PERIODS
+ *         edges         HOST [nedges] depth edges in km, finite and ascending, shared by all sets: nb = nedges - 1 bins,
+ *                       1 <= nb <= BH_SENS_SETS_MAX_BINS
+ *         kind          the layer value G_l: BH_SENS_KIND_VP / _VS / _RHO are K[1][l], K[2][l], K[3][l];
+ *                       BH_SENS_KIND_VS_TOTAL is fma(q_l, fma(drho_dvp, K_rho, K_vp), K_vs), dc/dvs with vp = q vs and
+ *                       rho = const + drho_dvp vp moving along (BayHunter's parameters; drho_dvp 0.32 there).  dc/dh is
+ *                       an interface derivative, not a depth density, and is not offered
+ * add     rows row0 .. row0 + B - 1 of the numbering.  The calls must arrive in ascending order without a gap; a call may
+ *         begin or end inside a set only at a multiple of BH_SENS_SETS_BLOCK_ROWS rows from the set's first row.
+ *         nlay, hthk, model_stride   DEVICE, the models as bh_sens_batch read them (row b: hthk + b * model_stride)
+ *         q, q_stride   DEVICE [B][q_stride] the layers' vp / vs, read for l < nlay only; needed by
+ *                       BH_SENS_KIND_VS_TOTAL, else it may be NULL
+ *         K, c_out      DEVICE [B][nper][4][Lmax], [B][nper]: what bh_sens_batch wrote
+ *         weights       DEVICE int32 [B] >= 0, or NULL for all ones
+ *         Synchronises the handle's stream: the arrays are free when it returns.
+ * finish  HOST outputs, each optional: total, excluded [nsets][nper]; s1, s2, vmin, vmax [nsets][nper][nb + 1].
+ *
+ * Per row and period, with the layer tops the sequential fp64 cumsum of hthk, cell j < nb is
+ *     x_j = sum over l = 0 .. nlay - 2, ascending, by fma, of (max(0, min(bot_l, e[j+1]) - max(top_l, e[j])) / h_l) G_l
+ * (a layer with h_l <= 0 adds nothing; what lies outside e[0] .. e[nb] is dropped) and cell nb is the half-space's
+ * G_{nlay-1}.  A (row, period) counts when its weight is positive, 2 <= nlay <= Lmax and c_out is not NaN (bh_sens_batch
+ * sets c_out and all of K of a (model, period) to NaN together); a row of positive weight that does not count adds its
+ * weight to excluded[s][p].  Over the rows that count: total = sum w, s1 = sum w x, s2 = sum (w x) x (both by fma, no
+ * centre), vmin, vmax.  The caller's mean is s1 / total, the population variance s2 / total - mean^2.
+ * The order of the sums is fixed by the set's rows alone (csrc/sens_sets_core.h): blocks of BH_SENS_SETS_BLOCK_ROWS rows
+ * counted from the set's first row, the rows of a block ascending in one fma chain per cell, the block partials added in
+ * ascending block order by one thread per cell; no floating-point atomic.  Two runs are bit-identical, and a set's result
+ * depends neither on the other sets, nor on where its rows lie, nor on how the rows were split into calls.
+ * An empty set, or a period of a set without a row that counts, is no error: total 0, sums 0, vmin and vmax NaN.
+ * BH_ERR_ARG: rows out of order or past set_start's end, a cut that is no block multiple, BH_SENS_KIND_VS_TOTAL without
+ * q, q_stride or model_stride below Lmax, a NULL pointer, finish before all rows were added, a negative weight (reported
+ * by the add that brought it, and by finish).  All arguments but the weights' sign are checked before any device is
+ * touched. */
+#define BH_SENS_KIND_VP       1
+#define BH_SENS_KIND_VS       2
+#define BH_SENS_KIND_RHO      3
+#define BH_SENS_KIND_VS_TOTAL 4
+#define BH_SENS_SETS_BLOCK_ROWS 256
+#define BH_SENS_SETS_MAX_BINS   1024
+int  bh_sens_sets_create(void **handle, const long long *set_start, int nsets, int nper, const double *edges,
+                         int nedges, int kind, double drho_dvp, void *stream);
+int  bh_sens_sets_add(void *handle, long long row0, int B, int Lmax, int model_stride, const int *nlay,
+                      const double *hthk, const double *q, int q_stride, const double *K, const double *c_out,
+                      const int *weights);
+int  bh_sens_sets_finish(void *handle, long long *total, long long *excluded, double *s1, double *s2, double *vmin,
+                         double *vmax);
+void bh_sens_sets_destroy(void *handle);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
