@@ -658,6 +658,17 @@ class ChainPool(object):
         from .sensitivity import pool_sensitivity
         return pool_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows)
 
+    def group_sensitivity(self, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                          exclude_outliers=True, device=None, max_rows=None):
+        """sensitivity() for the group velocity: the depth-binned dU/dm of every row posterior() uses, U the analytic
+        group velocity of the polished phase-velocity root (csrc/sens_group_core.h) -- not the finite difference of two
+        real*4 solves the sampler fits.  `ref` defaults to the pool's only fundamental-mode group target; a phase or a
+        group ref may be named: the kernels are formed at the target's periods for its wave type.  Arguments and the
+        dict as for sensitivity(), plus 'velocity': 'group'.  ValueError for a pool without a dispersion target and for
+        a higher-mode, flattened-earth or more-than-60-period target."""
+        from .sensitivity import pool_sensitivity
+        return pool_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, velocity='group')
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

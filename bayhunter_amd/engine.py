@@ -243,3 +243,56 @@ class ForwardEngine(object):
                 out.data_ptr() + 8 * tg.out_off, self.row, err.data_ptr() + 4 * target, max(1, self._nswd), K.data_ptr(),
                 c.data_ptr(), dc_dT.data_ptr(), ws.data_ptr(), ws.numel() * 8, C.c_void_p(st.cuda_stream)))
         return {'c': c, 'dc_dT': dc_dT, 'K': K}
+
+    def group_sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, target=0, stream=None):
+        """Depth sensitivity kernels of the GROUP velocity at the periods of dispersion target `target` for the batch
+        (bh_sens_group_batch, asynchronous): U [B, nper] (the analytic group velocity of the polished root, not what a
+        group target's columns hold), dU_dT, c [B, nper], K [B, nper, 4, Lmax] = dU/dh, dU/dvp, dU/dvs, dU/drho per layer
+        and K_phase, what sensitivity() returns as K -- device tensors in a dict.  The pass reads phase velocities: a
+        phase target's own columns; for a group target the columns of an equal phase target of this engine (the same
+        wave type and periods) if there is one, else of a companion engine with that one target, kept with this engine
+        and run on the same DeviceModels.  `out`, `err`: what run() returned for these models, or None: run() is called
+        first.  Fundamental mode, flat earth, at most 60 periods; a (model, period) without a value is NaN."""
+        models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
+        if not 0 <= target < len(self.layout.swd_all):
+            raise ValueError("target %r: the engine solves %d dispersion targets" % (target, len(self.layout.swd_all)))
+        spec = self.layout.swd_all[target]
+        if spec.mode != 1:
+            raise ValueError("sensitivity: target '%s' has mode = %d; only the fundamental mode is served" % (spec.ref, spec.mode))
+        if spec.flsph != 0:
+            raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (spec.ref, spec.flsph))
+        if spec.resample:
+            raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        src, source = self, target
+        if spec.igr != 0:
+            equal = [t for t, sp in enumerate(self.layout.swd_all)
+                     if sp.igr == 0 and sp.iwave == spec.iwave and sp.mode == 1 and sp.flsph == 0 and not sp.resample
+                     and np.array_equal(sp.periods, spec.periods)]
+            if equal:
+                source = equal[0]
+            else:
+                if not hasattr(self, '_phase_companions'):
+                    self._phase_companions = {}
+                src = self._phase_companions.get(target)
+                if src is None:
+                    src = self._phase_companions[target] = ForwardEngine(
+                        swd=[SwdSpec('rdispph' if spec.iwave == 2 else 'ldispph', spec.periods)], device=self.device)
+                source, out, err = 0, None, None
+        if out is None or err is None:
+            out, err = src.run(models, stream=stream)
+        B, Lmax, nper = models.B, models.Lmax, spec.periods.size
+        tg = src._tg[source]
+        need = self.lib.bh_sens_group_workspace_bytes(B, nper)
+        with torch.cuda.stream(st):
+            K, Kp = (torch.empty((B, nper, 4, Lmax), dtype=torch.float64, device=self.device) for _ in range(2))
+            U, dU_dT, c = (torch.empty((B, nper), dtype=torch.float64, device=self.device) for _ in range(3))
+            ws = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.bh_sens_group_batch(
+                B, Lmax, 4 * Lmax, models.nlay.data_ptr(), models.H.data_ptr(), models.VP.data_ptr(), models.VS.data_ptr(),
+                models.RHO.data_ptr(), spec.iwave, nper, src.periods.data_ptr() + 8 * tg.per_off, 0,
+                out.data_ptr() + 8 * tg.out_off, src.row, err.data_ptr() + 4 * source, max(1, src._nswd), K.data_ptr(),
+                U.data_ptr(), dU_dT.data_ptr(), c.data_ptr(), Kp.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                C.c_void_p(st.cuda_stream)))
+        return {'K': K, 'U': U, 'dU_dT': dU_dT, 'c': c, 'K_phase': Kp}

@@ -121,6 +121,32 @@ class SurfDisp(_Plugin):
             self.wavetype, pers.size, pers.ctypes.data, K.ctypes.data, c.ctypes.data, dc_dT.ctypes.data, C.byref(flag)))
         return {'c': c, 'dc_dT': dc_dT, 'K': K}
 
+    def group_sensitivity(self, h, vp, vs, rho):
+        """Depth sensitivity kernels of the group velocity of one model through bh_group_sensitivity: dict U [nper] (the
+        analytic group velocity c / (1 + (T / c) dc/dT) of the double-precision root -- not the finite difference of two
+        real*4 solves that run_model returns for a group ref), dU_dT [nper], c [nper], K [nper, 4, nlayer] = dU/dh,
+        dU/dvp, dU/dvs, dU/drho per layer and K_phase, the phase kernel sensitivity() returns.  For any of the four
+        dispersion refs -- the wave type and the periods matter, the phase search is the pass's own -- in the fundamental
+        mode on a flat earth with at most 60 periods; NaN throughout for a model the search cannot solve."""
+        if self.modelparams['mode'] != 1:
+            raise ValueError("SurfDisp.group_sensitivity: mode = %d; only the fundamental mode is served" % self.modelparams['mode'])
+        if self.modelparams['flsph'] != 0:
+            raise ValueError("SurfDisp.group_sensitivity: flsph = %d; only a flat earth is served" % self.modelparams['flsph'])
+        if self.kmax > NP_MAX:
+            raise ValueError("SurfDisp.group_sensitivity: %d periods exceed the solver limit of %d" % (self.kmax, NP_MAX))
+        lib = _lib.load()
+        model32 = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32)) for a in (h, vp, vs, rho)]
+        pers = self._solver_periods()
+        n = len(model32[0])
+        K, Kp = np.zeros((pers.size, 4, n)), np.zeros((pers.size, 4, n))
+        U, dU_dT, c = np.zeros(pers.size), np.zeros(pers.size), np.zeros(pers.size)
+        flag = C.c_int(0)
+        _lib.check(lib.bh_group_sensitivity(
+            model32[0].ctypes.data, model32[1].ctypes.data, model32[2].ctypes.data, model32[3].ctypes.data, n, 0,
+            self.wavetype, pers.size, pers.ctypes.data, K.ctypes.data, U.ctypes.data, dU_dT.ctypes.data, c.ctypes.data,
+            Kp.ctypes.data, C.byref(flag)))
+        return {'K': K, 'U': U, 'dU_dT': dU_dT, 'c': c, 'K_phase': Kp}
+
     def run_models(self, H, VP, VS, RHO, nlay):
         """Batch of models ([B, Lmax] arrays) -> (x, Y[B, nobs], err[B]); unsolved rows are NaN.  More than
         60 periods are interpolated on the device, with run_model's numpy.interp bits."""

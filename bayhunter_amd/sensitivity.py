@@ -17,6 +17,14 @@ Over an ensemble -- where in depth the data look across all sampled models, and 
 
 Per row the device runs the search, the pass (bh_sens_batch) and the reduction bh_sens_sets_* (csrc/sens_sets_core.h);
 K never leaves the device.
+
+The same for the group velocity (csrc/sens_group_core.h): U = c / (1 + (T / c) dc/dT) is the
+analytic group velocity of the polished root, not the finite difference of two real*4 solves a group target returns, and
+K^U = dU/dm follows from the phase kernels at T and at two neighbouring periods.
+
+    group_batch(periods, H, VP, VS, RHO, nlay, wave)     the device search and the group pass for a batch of models
+    summarize / summarize_sets (velocity='group')        the depth-binned dU/dm over an ensemble
+    ChainPool.group_sensitivity / StationPool.group_sensitivity      (pool_sensitivity, stations_sensitivity)
 """
 import numpy as np
 
@@ -24,6 +32,8 @@ from . import _lib, selection as sel
 
 KINDS = ('h', 'vp', 'vs', 'rho')          # K's kind axis
 REFS = {'rayleigh': 'rdispph', 'love': 'ldispph'}
+GROUP_REFS = {'rayleigh': 'rdispgr', 'love': 'ldispgr'}
+VELOCITIES = ('phase', 'group')
 
 
 def batch(periods, H, VP, VS, RHO, nlay, wave='rayleigh'):
@@ -38,6 +48,24 @@ def batch(periods, H, VP, VS, RHO, nlay, wave='rayleigh'):
     models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
     out, err = eng.run(models)
     res = eng.sensitivity(models, out=out, err=err)
+    torch.cuda.synchronize(eng.device)
+    res = {k: v.cpu().numpy() for k, v in res.items()}
+    res['err'] = err.cpu().numpy()[:, 0]
+    return res
+
+
+def group_batch(periods, H, VP, VS, RHO, nlay, wave='rayleigh'):
+    """batch() for the group velocity: dict of numpy arrays U [B, nper] (the analytic group velocity), dU_dT, c [B, nper],
+    K [B, nper, 4, Lmax] = dU/dm (KINDS), K_phase (batch()'s K), err [B] (the phase search's flag).  A (model, period)
+    without a value is NaN in all of them."""
+    import torch
+    from .engine import ForwardEngine, SwdSpec
+    if wave not in REFS:
+        raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
+    eng = ForwardEngine(swd=[SwdSpec(REFS[wave], periods)])
+    models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
+    out, err = eng.run(models)
+    res = eng.group_sensitivity(models, out=out, err=err)
     torch.cuda.synchronize(eng.device)
     res = {k: v.cpu().numpy() for k, v in res.items()}
     res['err'] = err.cpu().numpy()[:, 0]
@@ -184,20 +212,23 @@ class SensSets(object):
         self.close()
 
 
-def _result(sums, z, periods, edges, kind):
+def _result(sums, z, periods, edges, kind, velocity='phase'):
     """summarize()'s dict of set z, or None for a set without a counting row at any period."""
     total = sums['total'][z]
     if not total.any():
         return None
     mean, std = from_sums(total, sums['s1'][z], sums['s2'][z], sums['vmin'][z], sums['vmax'][z])
-    return {'mean': mean[:, :-1], 'std': std[:, :-1], 'min': sums['vmin'][z][:, :-1].copy(),
-            'max': sums['vmax'][z][:, :-1].copy(), 'halfspace_mean': mean[:, -1], 'halfspace_std': std[:, -1],
-            'nmodels': total.copy(), 'nexcluded': sums['excluded'][z].copy(), 'periods': periods, 'edges': edges,
-            'kind': kind}
+    res = {'mean': mean[:, :-1], 'std': std[:, :-1], 'min': sums['vmin'][z][:, :-1].copy(),
+           'max': sums['vmax'][z][:, :-1].copy(), 'halfspace_mean': mean[:, -1], 'halfspace_std': std[:, -1],
+           'nmodels': total.copy(), 'nexcluded': sums['excluded'][z].copy(), 'periods': periods, 'edges': edges,
+           'kind': kind}
+    if velocity != 'phase':                     # (the phase result keeps the keys it had)
+        res['velocity'] = velocity
+    return res
 
 
 def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None,
-                   device=None, max_rows=None, strict=True, drho_dvp=0.32):
+                   device=None, max_rows=None, strict=True, drho_dvp=0.32, velocity='phase'):
     """summarize() of every set of rows in one pass: set s is models[set_start[s]:set_start[s + 1]] (set_start
     [sets + 1], ascending from 0 to the number of rows; a set may be empty) with its vpvs and weights.
 
@@ -210,6 +241,8 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
     max_rows        the rows are taken in runs of whole sets that fit max_rows, a larger set in whole blocks (default:
                     what half of the free device memory holds); per run the layers, the search, the pass
                     (ForwardEngine.sensitivity), q = vp / vs and bh_sens_sets_add; no result depends on it
+    velocity        'phase' (dc/dm), or 'group': the pass is ForwardEngine.group_sensitivity, the reduction receives dU/dm
+                    and counts a (row, period) by its U, and the dicts carry 'velocity': 'group'
 
     -> a selection.SetList of dicts(mean, std, min, max [nper, bins]: km/s per km/s (per g/cm^3 for 'rho') of the layer
     kernel that falls into the bin; halfspace_mean, halfspace_std [nper]; nmodels, nexcluded [nper] (weighted rows that
@@ -222,6 +255,8 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
     from .models import layers_from_voronoi
     if wave not in REFS:
         raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
+    if velocity not in VELOCITIES:
+        raise ValueError("velocity %r: 'phase' or 'group'" % (velocity,))
     code, edges = _check_kind(kind), _check_edges(dep_edges)
     periods = np.ascontiguousarray(periods, dtype=np.float64)
     shape = getattr(models, 'shape', None) or np.asarray(models).shape
@@ -255,6 +290,8 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
         Lmax, nper = shape[1] // 2, periods.size
         if max_rows is None:       # half of the free device memory: K, c, dc/dT and the workspace, the row, its layers
             per_row = 8 * (4 * nper * Lmax + 3 * nper + eng.row + shape[1] + 8 * Lmax) + 16      # (packed, nuclei, q)
+            if velocity == 'group':             # K_phase, U and the five further doubles of workspace per period
+                per_row += 8 * (4 * nper * Lmax + 6 * nper)
             max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
         with SensSets(set_start, nper, edges, code, drho_dvp, stream) as handle:
             for lo, hi in split_runs(set_start, max_rows):
@@ -266,12 +303,17 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
                 vsn, zv, nl = df._layers(rows, dev)
                 dm, _ = layers_from_voronoi(vsn, zv, nl, v, df._OPEN_PRIORS, mantle=mantle, device=dev)
                 out, err = eng.run(dm)
-                res = eng.sensitivity(dm, out=out, err=err)
+                if velocity == 'group':
+                    res = eng.group_sensitivity(dm, out=out, err=err)
+                    K, c = res['K'], res['U']
+                else:
+                    res = eng.sensitivity(dm, out=out, err=err)
+                    K, c = res['K'], res['c']
                 q = (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None
-                handle.add(lo, dm, res['K'], res['c'], q, w)
+                handle.add(lo, dm, K, c, q, w)
             sums = handle.finish()
     for z in range(Z):
-        results[z] = _result(sums, z, periods, edges, kind)
+        results[z] = _result(sums, z, periods, edges, kind, velocity)
         if results[z] is None:
             failed[z] = "empty selection: no models" if set_start[z] == set_start[z + 1] else _EMPTY
     sel.raise_first_failed(failed, strict, "set")
@@ -279,12 +321,12 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
 
 
 def summarize(periods, wave, models, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None, device=None,
-              max_rows=None, drho_dvp=0.32):
+              max_rows=None, drho_dvp=0.32, velocity='phase'):
     """The depth-binned sensitivity kernel over one set of sampled models: summarize_sets' dict for all rows (see there).
     ValueError for an empty selection."""
     shape = getattr(models, 'shape', None) or np.asarray(models).shape
     res = summarize_sets(periods, wave, models, [0, shape[0] if len(shape) == 2 else 0], vpvs, weights, dep_edges, kind,
-                         mantle, device, max_rows, strict=False, drho_dvp=drho_dvp)
+                         mantle, device, max_rows, strict=False, drho_dvp=drho_dvp, velocity=velocity)
     if res[0] is None:
         raise ValueError(res.failed[0])
     return res[0]
@@ -292,24 +334,29 @@ def summarize(periods, wave, models, vpvs, weights=None, dep_edges=None, kind='v
 
 # ---- chain pools ----------------------------------------------------------------------------------------------------------
 
-def pool_target(targets, ref=None):
-    """The dispersion target of a JointTarget the kernels are formed for -> (wave, periods).  ref None: its only
-    fundamental-mode phase target.  ValueError for a pool without a dispersion target, an ambiguous choice, and -- in
-    ForwardEngine.sensitivity's words -- a target the pass does not serve."""
+def pool_target(targets, ref=None, velocity='phase'):
+    """The dispersion target of a JointTarget the kernels are formed for -> (wave, periods, ref).  ref None: its only
+    fundamental-mode phase target -- for velocity 'group' its only fundamental-mode group target, and a ValueError when
+    there is none (a phase target is served when it is named).  ValueError for a pool
+    without a dispersion target, an ambiguous choice, and -- in ForwardEngine.sensitivity's words -- a target the pass
+    does not serve.  The group pass serves phase and group targets alike: the wave type and the periods matter."""
     from .layout import SWD_REFS
     specs = targets.batch_layout(ell=True)['layout'].swd
     if not specs:
         raise ValueError("sensitivity: the pool has no dispersion target")
     if ref is None:
-        served = [sp for sp in specs if sp.igr == 0 and sp.mode == 1]
+        served = [sp for sp in specs if sp.igr == (1 if velocity == 'group' else 0) and sp.mode == 1]
         if len(served) > 1:
             raise ValueError("sensitivity: ref is one of %s" % ', '.join(repr(sp.ref) for sp in served))
+        if velocity == 'group' and not served:
+            raise ValueError("sensitivity: the pool has no fundamental-mode group target; name one of %s as ref"
+                             % ', '.join(repr(sp.ref) for sp in specs))
         spec = served[0] if served else specs[0]
     else:
         if ref not in SWD_REFS or not any(sp.ref == ref for sp in specs):
             raise ValueError("sensitivity: no dispersion target %r (there are %s)" % (ref, ', '.join(sp.ref for sp in specs)))
         spec = next(sp for sp in specs if sp.ref == ref)
-    if spec.igr != 0:
+    if spec.igr != 0 and velocity != 'group':
         raise ValueError("sensitivity: target '%s' has igr = %d; group-velocity targets are not served" % (spec.ref, spec.igr))
     if spec.mode != 1:
         raise ValueError("sensitivity: target '%s' has mode = %d; only the fundamental mode is served" % (spec.ref, spec.mode))
@@ -317,18 +364,18 @@ def pool_target(targets, ref=None):
         raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (spec.ref, spec.flsph))
     if spec.resample:
         raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
-    return {v: k for k, v in REFS.items()}[spec.ref], spec.periods
+    return {1: 'love', 2: 'rayleigh'}[spec.iwave], spec.periods, spec.ref
 
 
 def pool_sensitivity(pool, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
-                     exclude_outliers=True, device=None, max_rows=None):
-    """ChainPool.sensitivity: summarize() over the rows ChainPool.posterior uses, plus 'ref' and 'chains' (global
-    indices used)."""
-    wave, periods = pool_target(pool.targets, ref)
+                     exclude_outliers=True, device=None, max_rows=None, velocity='phase'):
+    """ChainPool.sensitivity (velocity 'group': ChainPool.group_sensitivity): summarize() over the rows
+    ChainPool.posterior uses, plus 'ref' and 'chains' (global indices used)."""
+    wave, periods, tref = pool_target(pool.targets, ref, velocity)
     ci, ri, w = sel.pool_rows(pool, selection, dev, exclude_outliers)
     res = summarize(periods, wave, pool.models[ci, ri], pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32),
-                    dep_edges, kind, pool.priors.get('mantle'), device, max_rows)
-    res['ref'] = REFS[wave]
+                    dep_edges, kind, pool.priors.get('mantle'), device, max_rows, velocity=velocity)
+    res['ref'] = tref
     res['chains'] = np.unique(ci) + pool.first
     return res
 
@@ -341,6 +388,8 @@ class StationSensitivity(sel.StationResult):
     ref, periods, edges, kind   the target, its periods and the depth edges all stations share
     mean, std, min, max [nstations, nper, bins], halfspace_mean, halfspace_std [nstations, nper] (float64, NaN for a
     failed station), nmodels, nexcluded [nstations, nper] (0 for a failed station)"""
+
+    velocity = 'phase'      # 'group' on StationPool.group_sensitivity's result
 
     def __init__(self, names, results, failed, ref, periods, edges, kind):
         sel.StationResult.__init__(self, names, failed)
@@ -358,19 +407,24 @@ class StationSensitivity(sel.StationResult):
 
 
 def stations_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
-                         exclude_outliers=True, device=None, max_rows=None, strict=False):
-    """StationPool.sensitivity: summarize_sets() over every station's main-phase rows."""
+                         exclude_outliers=True, device=None, max_rows=None, strict=False, velocity='phase'):
+    """StationPool.sensitivity (velocity 'group': StationPool.group_sensitivity): summarize_sets() over every station's
+    main-phase rows."""
     pool, c = spool.pool, spool.chains_per_station
-    wave, periods = pool_target(spool.stations[0], ref)
+    wave, periods, tref = pool_target(spool.stations[0], ref, velocity)
     edges = _check_edges(dep_edges)
     ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
     res = summarize_sets(periods, wave, pool.models[ci, ri], set_start, pool.vpvs[ci, ri].astype(np.float64),
-                         w.astype(np.int32), edges, kind, pool.priors.get('mantle'), device, max_rows, strict=False)
+                         w.astype(np.int32), edges, kind, pool.priors.get('mantle'), device, max_rows, strict=False,
+                         velocity=velocity)
     for z, msg in res.failed.items():
         failed.setdefault(z, msg)
     sel.raise_first_failed(failed, strict, "station", spool.names)
     for z, r in enumerate(res):
         if r is not None:
-            r['ref'] = REFS[wave]
+            r['ref'] = tref
             r['chains'] = sel.station_chains(ci, set_start, z, c)
-    return StationSensitivity(spool.names, res, failed, REFS[wave], periods, edges, kind)
+    out = StationSensitivity(spool.names, res, failed, tref, periods, edges, kind)
+    if velocity != 'phase':
+        out.velocity = velocity
+    return out

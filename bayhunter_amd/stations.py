@@ -540,6 +540,15 @@ class StationPool(object):
         from .sensitivity import stations_sensitivity
         return stations_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, strict)
 
+    def group_sensitivity(self, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                          exclude_outliers=True, device=None, max_rows=None, strict=False):
+        """sensitivity() for the group velocity (ChainPool.group_sensitivity): every station's depth-binned dU/dm in one
+        pass; per station every field is bit for bit what station(s).group_sensitivity(...) returns.  `ref` defaults to
+        the stations' only fundamental-mode group target.  -> sensitivity.StationSensitivity with `velocity` 'group'."""
+        from .sensitivity import stations_sensitivity
+        return stations_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, strict,
+                                    velocity='group')
+
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone
         writes (data/c%03d_... numbered from 0, data/<station name>_config.pkl with the station's targets).

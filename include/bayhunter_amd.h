@@ -242,6 +242,30 @@ int bh_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const doub
                   int err_stride, double *K /*[B][nper][4][Lmax]: h, vp, vs, rho*/, double *c_out /*[B][nper]*/,
                   double *dc_dT /*[B][nper]*/, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- batched group-velocity sensitivity kernels (device pointers) -------------------------- */
+/* dU/dm of the fundamental-mode group velocity (csrc/sens_group_core.h).  U is the analytic group velocity of the
+ * polished phase-velocity root, U = c / (1 + (T / c) dc/dT) -- not the finite difference of two real*4 solves that a
+ * group target (igr 1) of bh_swd_batch returns.  With g = U / c and K^c = dc/dm (bh_sens_batch's K),
+ *     K^U = g (2 - g) K^c(T) - g^2 T dK^c/dT,
+ * the last factor a central difference of K^c between T (1 + r_g) and T (1 - r_g), r_g = 2^-12; each of the two periods
+ * has its own polished root, found from the tangent of c(T) and accepted within 32 r_g^2 of it.  Arguments as for
+ * bh_sens_batch; c is still what a PHASE target (igr 0, mode 1, iflsph 0, the same iwave and periods) wrote.
+ *   K                [B][nper][4][Lmax]: dU/dh, dU/dvp, dU/dvs, dU/drho per layer; the zeros of bh_sens_batch's K
+ *   U_out, dU_dT     [B][nper]: the group velocity and its derivative with respect to the period (from the three roots)
+ *   c_out            [B][nper]: the polished phase velocity, bit for bit bh_sens_batch's
+ *   K_phase          [B][nper][4][Lmax] or NULL: dc/dm at T, bit for bit bh_sens_batch's K
+ *   workspace        bh_sens_group_workspace_bytes(B, nper) bytes
+ * A (model, period) without a value is NaN in K, K_phase, U_out, dU_dT and c_out together: bh_sens_batch's conditions,
+ * or one of the two neighbouring roots has no value.  Asynchronous on `stream`.  The same refusals with the same codes
+ * as bh_sens_batch. */
+size_t bh_sens_group_workspace_bytes(int B, int nper);
+int bh_sens_group_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                        const double *vs, const double *rho, int iwave /*1 Love, 2 Rayleigh*/, int nper,
+                        const double *periods, int flsph, const double *c, int c_stride, const int *c_err,
+                        int err_stride, double *K /*[B][nper][4][Lmax]: h, vp, vs, rho*/, double *U_out /*[B][nper]*/,
+                        double *dU_dT /*[B][nper]*/, double *c_out /*[B][nper]*/, double *K_phase /*as K, or NULL*/,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Voronoi nuclei -> layered models + prior checks (device pointers) ------------------- */
 /* The step in front of the forward path: Model.get_vp_vs_h (src/Models.py:26-52) and
  * SingleChain._validmodel (src/SingleChain.py:330-392) for a batch of proposals.  Input per model:
@@ -378,6 +402,12 @@ int bh_ellipticity(const float *thkm, const float *vpm, const float *vsm, const 
 int bh_sensitivity(const float *thkm, const float *vpm, const float *vsm, const float *rhom, int nlayer,
                    int iflsph, int iwave, int kmax, const double *t, double *K /*[kmax][4][nlayer]*/,
                    double *c_out, double *dc_dT, int *err);
+/* Group-velocity sensitivity kernels of one model: the same phase search (mode 1, igr 0), then bh_sens_group_batch's
+ * pass.  K and K_phase (or NULL) [kmax][4][nlayer], U_out, dU_dT and c_out [kmax].  *err is the search's flag; when it
+ * is set, everything is NaN.  iflsph != 0 is refused (BH_ERR_ARG). */
+int bh_group_sensitivity(const float *thkm, const float *vpm, const float *vsm, const float *rhom, int nlayer,
+                         int iflsph, int iwave, int kmax, const double *t, double *K /*[kmax][4][nlayer]*/,
+                         double *U_out, double *dU_dT, double *c_out, double *K_phase /*as K, or NULL*/, int *err);
 
 /* ---- the reference's literal FFI symbols ------------------------------------------------ */
 /* Thin aliases of the two drop-ins above under the names the reference's generated glue binds, so that
