@@ -669,6 +669,18 @@ class ChainPool(object):
         from .sensitivity import pool_sensitivity
         return pool_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, velocity='group')
 
+    def ell_sensitivity(self, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                        exclude_outliers=True, device=None, max_rows=None):
+        """sensitivity() for the Rayleigh-wave ellipticity: which layers the H/V data look at.  The depth-binned dE/dm of
+        every row posterior() uses, E the ratio at the polished phase-velocity root (csrc/ell_sens_core.h), of |H/V| or
+        of the signed ratio as the target's `absolute` says; the values are changes of H/V per km/s of the layer (per
+        g/cm^3 for kind 'rho').  `ref` defaults to the pool's only ellipticity target.  Arguments and the dict as for
+        sensitivity(), plus 'velocity': 'ellipticity'.  ValueError for a pool without an ellipticity target and for a
+        flattened-earth target."""
+        from .sensitivity import pool_sensitivity
+        return pool_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows,
+                                velocity='ellipticity')
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

@@ -296,3 +296,38 @@ class ForwardEngine(object):
                 U.data_ptr(), dU_dT.data_ptr(), c.data_ptr(), Kp.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                 C.c_void_p(st.cuda_stream)))
         return {'K': K, 'U': U, 'dU_dT': dU_dT, 'c': c, 'K_phase': Kp}
+
+    def ell_sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, target=0, absolute=None,
+                        stream=None):
+        """Depth sensitivity kernels of ELLIPTICITY target `target` (an index into the engine's ellipticity targets) for the
+        batch (bh_ell_sens_batch, asynchronous): E [B, nper] (H/V at the polished double-precision root -- not the
+        target's columns, which hold H/V at the stored real*4 phase velocity), dE_dT, c [B, nper], K [B, nper, 4, Lmax] =
+        dE/dh, dE/dvp, dE/dvs, dE/drho per layer (change of H/V per km, per km/s, per g/cm^3) and K_phase, what
+        sensitivity() returns as K for the Rayleigh phase velocity -- device tensors in a dict.  The pass reads the phase
+        velocities bh_ell_batch is given for that target: the columns of an equal 'rdispph' target, or of the hidden one.
+        absolute: None for the target's; True: E, dE_dT and K are those of |H/V|.  `out`, `err`: what run() returned for
+        these models, or None: run() is called first.  Flat earth only; a (model, period) without a value is NaN."""
+        models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
+        if not 0 <= target < len(self.ell):
+            raise ValueError("target %r: the engine has %d ellipticity targets" % (target, len(self.ell)))
+        e = self.ell[target]
+        if e.flsph != 0:
+            raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (e.ref, e.flsph))
+        if out is None or err is None:
+            out, err = self.run(models, stream=stream)
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        t, per_off, c_off = self.layout.ell_src[target]
+        B, Lmax, nper = models.B, models.Lmax, e.periods.size
+        absolute = e.absolute if absolute is None else bool(absolute)
+        need = self.lib.bh_ell_sens_workspace_bytes(B, nper)
+        with torch.cuda.stream(st):
+            K, Kp = (torch.empty((B, nper, 4, Lmax), dtype=torch.float64, device=self.device) for _ in range(2))
+            E, dE_dT, c = (torch.empty((B, nper), dtype=torch.float64, device=self.device) for _ in range(3))
+            ws = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.bh_ell_sens_batch(
+                B, Lmax, 4 * Lmax, models.nlay.data_ptr(), models.H.data_ptr(), models.VP.data_ptr(), models.VS.data_ptr(),
+                models.RHO.data_ptr(), nper, self.periods.data_ptr() + 8 * per_off, 0, 1 if absolute else 0,
+                out.data_ptr() + 8 * c_off, self.row, err.data_ptr() + 4 * t, max(1, self._nswd), K.data_ptr(), E.data_ptr(),
+                dE_dT.data_ptr(), c.data_ptr(), Kp.data_ptr(), ws.data_ptr(), ws.numel() * 8, C.c_void_p(st.cuda_stream)))
+        return {'K': K, 'E': E, 'dE_dT': dE_dT, 'c': c, 'K_phase': Kp}

@@ -268,3 +268,25 @@ class RayleighEllipticity(_Plugin):
         out, err = self._engine.run(H, VP, VS, RHO, nlay)
         return (np.ascontiguousarray(self.obsx, dtype=np.float64), out[:, self._engine.slices[0]].cpu().numpy(),
                 err.cpu().numpy()[:, 0])
+
+    def sensitivity(self, h, vp, vs, rho):
+        """Depth sensitivity kernels of the ellipticity of one model through bh_ellipticity_sensitivity: dict E [nper] (H/V at
+        the double-precision root of the period equation -- run_model evaluates it at the search's real*4 phase
+        velocity), dE_dT [nper], c [nper], K [nper, 4, nlayer] = dE/dh, dE/dvp, dE/dvs, dE/drho per layer (change of H/V
+        per km, per km/s of the layer, per g/cm^3 for rho) and K_phase, the phase-velocity kernel SurfDisp.sensitivity
+        returns for 'rdispph'.  With modelparams['absolute'] E, dE_dT and K are those of |H/V|.  Flat earth only
+        (ValueError for flsph = 1); NaN throughout for a model the search cannot solve or without an ellipticity."""
+        if self.modelparams['flsph'] != 0:
+            raise ValueError("RayleighEllipticity.sensitivity: flsph = %d; only a flat earth is served" % self.modelparams['flsph'])
+        lib = _lib.load()
+        model32 = [np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32)) for a in (h, vp, vs, rho)]
+        pers = np.ascontiguousarray(self.obsx, dtype=np.float64)
+        n = len(model32[0])
+        K, Kp = np.zeros((pers.size, 4, n)), np.zeros((pers.size, 4, n))
+        E, dE_dT, c = np.zeros(pers.size), np.zeros(pers.size), np.zeros(pers.size)
+        flag = C.c_int(0)
+        _lib.check(lib.bh_ellipticity_sensitivity(
+            model32[0].ctypes.data, model32[1].ctypes.data, model32[2].ctypes.data, model32[3].ctypes.data, n, 0,
+            1 if self.modelparams['absolute'] else 0, pers.size, pers.ctypes.data, K.ctypes.data, E.ctypes.data,
+            dE_dT.ctypes.data, c.ctypes.data, Kp.ctypes.data, C.byref(flag)))
+        return {'K': K, 'E': E, 'dE_dT': dE_dT, 'c': c, 'K_phase': Kp}

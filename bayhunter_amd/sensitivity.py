@@ -25,6 +25,13 @@ K^U = dU/dm follows from the phase kernels at T and at two neighbouring periods.
     group_batch(periods, H, VP, VS, RHO, nlay, wave)     the device search and the group pass for a batch of models
     summarize / summarize_sets (velocity='group')        the depth-binned dU/dm over an ensemble
     ChainPool.group_sensitivity / StationPool.group_sensitivity      (pool_sensitivity, stations_sensitivity)
+
+And for the Rayleigh-wave ellipticity (csrc/ell_sens_core.h): E is H/V at the polished root and
+K^E = dE/dm = G_m + G_c dc/dm, the change of H/V per km/s of the layer (per g/cm^3 for 'rho').
+
+    ell_batch(periods, H, VP, VS, RHO, nlay, absolute)   the device search and the ellipticity pass for a batch of models
+    summarize / summarize_sets (velocity='ellipticity')  the depth-binned dE/dm over an ensemble
+    ChainPool.ell_sensitivity / StationPool.ell_sensitivity          (pool_sensitivity, stations_sensitivity)
 """
 import numpy as np
 
@@ -33,7 +40,7 @@ from . import _lib, selection as sel
 KINDS = ('h', 'vp', 'vs', 'rho')          # K's kind axis
 REFS = {'rayleigh': 'rdispph', 'love': 'ldispph'}
 GROUP_REFS = {'rayleigh': 'rdispgr', 'love': 'ldispgr'}
-VELOCITIES = ('phase', 'group')
+VELOCITIES = ('phase', 'group', 'ellipticity')
 
 
 def batch(periods, H, VP, VS, RHO, nlay, wave='rayleigh'):
@@ -66,6 +73,22 @@ def group_batch(periods, H, VP, VS, RHO, nlay, wave='rayleigh'):
     models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
     out, err = eng.run(models)
     res = eng.group_sensitivity(models, out=out, err=err)
+    torch.cuda.synchronize(eng.device)
+    res = {k: v.cpu().numpy() for k, v in res.items()}
+    res['err'] = err.cpu().numpy()[:, 0]
+    return res
+
+
+def ell_batch(periods, H, VP, VS, RHO, nlay, absolute=True):
+    """batch() for the Rayleigh-wave ellipticity: dict of numpy arrays E [B, nper] (H/V at the polished root; |H/V| with
+    absolute), dE_dT, c [B, nper], K [B, nper, 4, Lmax] = dE/dm (KINDS), K_phase (batch()'s K for Rayleigh waves), err [B]
+    (the phase search's flag).  A (model, period) without a value is NaN in all of them."""
+    import torch
+    from .engine import EllSpec, ForwardEngine
+    eng = ForwardEngine(ell=[EllSpec('rellip', periods, 0, absolute)])
+    models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
+    out, err = eng.run(models)
+    res = eng.ell_sensitivity(models, out=out, err=err)
     torch.cuda.synchronize(eng.device)
     res = {k: v.cpu().numpy() for k, v in res.items()}
     res['err'] = err.cpu().numpy()[:, 0]
@@ -228,7 +251,7 @@ def _result(sums, z, periods, edges, kind, velocity='phase'):
 
 
 def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None,
-                   device=None, max_rows=None, strict=True, drho_dvp=0.32, velocity='phase'):
+                   device=None, max_rows=None, strict=True, drho_dvp=0.32, velocity='phase', absolute=True):
     """summarize() of every set of rows in one pass: set s is models[set_start[s]:set_start[s + 1]] (set_start
     [sets + 1], ascending from 0 to the number of rows; a set may be empty) with its vpvs and weights.
 
@@ -242,7 +265,12 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
                     what half of the free device memory holds); per run the layers, the search, the pass
                     (ForwardEngine.sensitivity), q = vp / vs and bh_sens_sets_add; no result depends on it
     velocity        'phase' (dc/dm), or 'group': the pass is ForwardEngine.group_sensitivity, the reduction receives dU/dm
-                    and counts a (row, period) by its U, and the dicts carry 'velocity': 'group'
+                    and counts a (row, period) by its U, and the dicts carry 'velocity': 'group'; or 'ellipticity'
+                    (wave 'rayleigh' only): the pass is ForwardEngine.ell_sensitivity, the reduction receives dE/dm --
+                    of |H/V| with `absolute`, else of the signed ratio -- and counts a (row, period) by its E; the
+                    values are then changes of H/V per km/s (per g/cm^3), and the dicts carry 'velocity': 'ellipticity'
+                    (its 'vs_total' is formed per layer in vs_total()'s own operation order, bh_ell_sens_vs_total: the
+                    two parts cancel at short periods)
 
     -> a selection.SetList of dicts(mean, std, min, max [nper, bins]: km/s per km/s (per g/cm^3 for 'rho') of the layer
     kernel that falls into the bin; halfspace_mean, halfspace_std [nper]; nmodels, nexcluded [nper] (weighted rows that
@@ -251,12 +279,14 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
     first such set -- or, with strict=False, has the entry None and its message in the list's `failed`."""
     import torch
     from . import _device, datafits as df
-    from .engine import ForwardEngine, SwdSpec
+    from .engine import EllSpec, ForwardEngine, SwdSpec
     from .models import layers_from_voronoi
     if wave not in REFS:
         raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
     if velocity not in VELOCITIES:
-        raise ValueError("velocity %r: 'phase' or 'group'" % (velocity,))
+        raise ValueError("velocity %r: 'phase', 'group' or 'ellipticity'" % (velocity,))
+    if velocity == 'ellipticity' and wave != 'rayleigh':
+        raise ValueError("velocity 'ellipticity': wave %r; the ellipticity is the Rayleigh wave's" % (wave,))
     code, edges = _check_kind(kind), _check_edges(dep_edges)
     periods = np.ascontiguousarray(periods, dtype=np.float64)
     shape = getattr(models, 'shape', None) or np.asarray(models).shape
@@ -277,7 +307,8 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
         raise ValueError("periods: one at least")
     spec = SwdSpec(REFS[wave], periods)
     if spec.resample:
-        raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
+        raise ValueError("sensitivity: target '%s' has more than %d periods"
+                         % ('rellip' if velocity == 'ellipticity' else spec.ref, _lib.MAX_PERIODS))
     results, failed = [None] * Z, {}
     if R == 0:
         failed = {z: "empty selection: no models" for z in range(Z)}
@@ -285,14 +316,24 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
         return sel.SetList(results, failed)
     dev = _device.torch_device(device)
     with torch.cuda.device(dev):
-        eng = ForwardEngine(swd=[spec], device=dev)
+        if velocity == 'ellipticity':          # its phase velocities are a hidden 'rdispph' target's, as in an inversion
+            eng = ForwardEngine(ell=[EllSpec('rellip', periods, 0, absolute)], device=dev)
+        else:
+            eng = ForwardEngine(swd=[spec], device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         Lmax, nper = shape[1] // 2, periods.size
         if max_rows is None:       # half of the free device memory: K, c, dc/dT and the workspace, the row, its layers
             per_row = 8 * (4 * nper * Lmax + 3 * nper + eng.row + shape[1] + 8 * Lmax) + 16      # (packed, nuclei, q)
             if velocity == 'group':             # K_phase, U and the five further doubles of workspace per period
                 per_row += 8 * (4 * nper * Lmax + 6 * nper)
+            if velocity == 'ellipticity':       # K_phase, E and the two further doubles of workspace per period
+                per_row += 8 * (4 * nper * Lmax + 3 * nper)
             max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
+        # The ellipticity's K_vs and (vp / vs) K_vp cancel to 1e-7 of their size at short periods: its 'vs_total' is formed
+        # per layer in vs_total()'s own operation order (bh_ell_sens_vs_total, in place of K_vs) and reduced as kind 'vs'
+        plain_total = velocity == 'ellipticity' and kind == 'vs_total'
+        if plain_total:
+            code = _lib.SENS_KINDS['vs']
         with SensSets(set_start, nper, edges, code, drho_dvp, stream) as handle:
             for lo, hi in split_runs(set_start, max_rows):
                 rows = _device.to_device(models[lo:hi], torch.float64, dev)
@@ -306,10 +347,17 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
                 if velocity == 'group':
                     res = eng.group_sensitivity(dm, out=out, err=err)
                     K, c = res['K'], res['U']
+                elif velocity == 'ellipticity':
+                    res = eng.ell_sensitivity(dm, out=out, err=err)
+                    K, c = res['K'], res['E']
                 else:
                     res = eng.sensitivity(dm, out=out, err=err)
                     K, c = res['K'], res['c']
                 q = (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None
+                if plain_total:
+                    _lib.check(handle.lib.bh_ell_sens_vs_total(dm.B, dm.Lmax, nper, K.data_ptr(), q.data_ptr(), q.stride(0),
+                                                               float(drho_dvp), K.data_ptr(), stream))
+                    q = None
                 handle.add(lo, dm, K, c, q, w)
             sums = handle.finish()
     for z in range(Z):
@@ -321,12 +369,12 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
 
 
 def summarize(periods, wave, models, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None, device=None,
-              max_rows=None, drho_dvp=0.32, velocity='phase'):
+              max_rows=None, drho_dvp=0.32, velocity='phase', absolute=True):
     """The depth-binned sensitivity kernel over one set of sampled models: summarize_sets' dict for all rows (see there).
     ValueError for an empty selection."""
     shape = getattr(models, 'shape', None) or np.asarray(models).shape
     res = summarize_sets(periods, wave, models, [0, shape[0] if len(shape) == 2 else 0], vpvs, weights, dep_edges, kind,
-                         mantle, device, max_rows, strict=False, drho_dvp=drho_dvp, velocity=velocity)
+                         mantle, device, max_rows, strict=False, drho_dvp=drho_dvp, velocity=velocity, absolute=absolute)
     if res[0] is None:
         raise ValueError(res.failed[0])
     return res[0]
@@ -339,8 +387,13 @@ def pool_target(targets, ref=None, velocity='phase'):
     fundamental-mode phase target -- for velocity 'group' its only fundamental-mode group target, and a ValueError when
     there is none (a phase target is served when it is named).  ValueError for a pool
     without a dispersion target, an ambiguous choice, and -- in ForwardEngine.sensitivity's words -- a target the pass
-    does not serve.  The group pass serves phase and group targets alike: the wave type and the periods matter."""
+    does not serve.  The group pass serves phase and group targets alike: the wave type and the periods matter.
+    velocity 'ellipticity': the pool's ellipticity target (ref None: its only one) -> ('rayleigh', periods, ref);
+    ValueError for a pool without one, for flsph = 1 and for more than 60 periods."""
     from .layout import SWD_REFS
+    if velocity == 'ellipticity':
+        spec = _ell_spec(targets, ref)
+        return 'rayleigh', spec.periods, spec.ref
     specs = targets.batch_layout(ell=True)['layout'].swd
     if not specs:
         raise ValueError("sensitivity: the pool has no dispersion target")
@@ -367,14 +420,41 @@ def pool_target(targets, ref=None, velocity='phase'):
     return {1: 'love', 2: 'rayleigh'}[spec.iwave], spec.periods, spec.ref
 
 
+def _ell_spec(targets, ref=None):
+    """The EllSpec of a JointTarget's ellipticity target `ref` (None: its only one), checked for what the pass serves."""
+    from .layout import ELL_REFS
+    specs = targets.batch_layout(ell=True)['layout'].ell
+    if not specs:
+        raise ValueError("sensitivity: the pool has no ellipticity target")
+    if ref is None:
+        if len(specs) > 1:
+            raise ValueError("sensitivity: ref is one of %s" % ', '.join(repr(sp.ref) for sp in specs))
+        spec = specs[0]
+    else:
+        if ref not in ELL_REFS or not any(sp.ref == ref for sp in specs):
+            raise ValueError("sensitivity: no ellipticity target %r (there are %s)" % (ref, ', '.join(sp.ref for sp in specs)))
+        spec = next(sp for sp in specs if sp.ref == ref)
+    if spec.flsph != 0:
+        raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (spec.ref, spec.flsph))
+    if spec.periods.size > _lib.MAX_PERIODS:
+        raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
+    return spec
+
+
+def _pool_absolute(targets, tref, velocity):
+    return _ell_spec(targets, tref).absolute if velocity == 'ellipticity' else True
+
+
 def pool_sensitivity(pool, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
                      exclude_outliers=True, device=None, max_rows=None, velocity='phase'):
-    """ChainPool.sensitivity (velocity 'group': ChainPool.group_sensitivity): summarize() over the rows
+    """ChainPool.sensitivity (velocity 'group': ChainPool.group_sensitivity; 'ellipticity': ChainPool.ell_sensitivity,
+    with the target's `absolute`): summarize() over the rows
     ChainPool.posterior uses, plus 'ref' and 'chains' (global indices used)."""
     wave, periods, tref = pool_target(pool.targets, ref, velocity)
     ci, ri, w = sel.pool_rows(pool, selection, dev, exclude_outliers)
     res = summarize(periods, wave, pool.models[ci, ri], pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32),
-                    dep_edges, kind, pool.priors.get('mantle'), device, max_rows, velocity=velocity)
+                    dep_edges, kind, pool.priors.get('mantle'), device, max_rows, velocity=velocity,
+                    absolute=_pool_absolute(pool.targets, tref, velocity))
     res['ref'] = tref
     res['chains'] = np.unique(ci) + pool.first
     return res
@@ -389,7 +469,7 @@ class StationSensitivity(sel.StationResult):
     mean, std, min, max [nstations, nper, bins], halfspace_mean, halfspace_std [nstations, nper] (float64, NaN for a
     failed station), nmodels, nexcluded [nstations, nper] (0 for a failed station)"""
 
-    velocity = 'phase'      # 'group' on StationPool.group_sensitivity's result
+    velocity = 'phase'      # 'group' on StationPool.group_sensitivity's result, 'ellipticity' on ell_sensitivity's
 
     def __init__(self, names, results, failed, ref, periods, edges, kind):
         sel.StationResult.__init__(self, names, failed)
@@ -408,15 +488,15 @@ class StationSensitivity(sel.StationResult):
 
 def stations_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
                          exclude_outliers=True, device=None, max_rows=None, strict=False, velocity='phase'):
-    """StationPool.sensitivity (velocity 'group': StationPool.group_sensitivity): summarize_sets() over every station's
-    main-phase rows."""
+    """StationPool.sensitivity (velocity 'group': StationPool.group_sensitivity; 'ellipticity':
+    StationPool.ell_sensitivity): summarize_sets() over every station's main-phase rows."""
     pool, c = spool.pool, spool.chains_per_station
     wave, periods, tref = pool_target(spool.stations[0], ref, velocity)
     edges = _check_edges(dep_edges)
     ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
     res = summarize_sets(periods, wave, pool.models[ci, ri], set_start, pool.vpvs[ci, ri].astype(np.float64),
                          w.astype(np.int32), edges, kind, pool.priors.get('mantle'), device, max_rows, strict=False,
-                         velocity=velocity)
+                         velocity=velocity, absolute=_pool_absolute(spool.stations[0], tref, velocity))
     for z, msg in res.failed.items():
         failed.setdefault(z, msg)
     sel.raise_first_failed(failed, strict, "station", spool.names)

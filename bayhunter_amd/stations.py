@@ -549,6 +549,15 @@ class StationPool(object):
         return stations_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, strict,
                                     velocity='group')
 
+    def ell_sensitivity(self, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
+                        exclude_outliers=True, device=None, max_rows=None, strict=False):
+        """sensitivity() for the Rayleigh-wave ellipticity (ChainPool.ell_sensitivity): every station's depth-binned dE/dm
+        in one pass; per station every field is bit for bit what station(s).ell_sensitivity(...) returns.  `ref` defaults
+        to the stations' only ellipticity target.  -> sensitivity.StationSensitivity with `velocity` 'ellipticity'."""
+        from .sensitivity import stations_sensitivity
+        return stations_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, strict,
+                                    velocity='ellipticity')
+
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone
         writes (data/c%03d_... numbered from 0, data/<station name>_config.pkl with the station's targets).

@@ -266,6 +266,43 @@ int bh_sens_group_batch(int B, int Lmax, int model_stride, const int *nlay, cons
                         double *dU_dT /*[B][nper]*/, double *c_out /*[B][nper]*/, double *K_phase /*as K, or NULL*/,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- batched ellipticity sensitivity kernels (device pointers) ----------------------------- */
+/* dE/dm of the fundamental Rayleigh mode's ellipticity (H/V; csrc/ell_sens_core.h).  With F the period equation and
+ * G(c, T, m) the ratio bh_ell_batch forms, at any c, E(T, m) = G at the root c* of F and
+ *     K^E = dE/dm = G_m + G_c dc/dm,  dc/dm = -F_m / F_c;      dE/dT = G_T + G_c dc/dT,
+ * every partial derivative a central difference; one pass of the layer recursion gives F and G together.  E is G at the
+ * polished root in double precision -- not the value bh_ell_batch returns at the stored real*4 c.  Rayleigh waves;
+ * arguments as for bh_sens_batch, c what a fundamental-mode Rayleigh PHASE target (iflsph 0, the same periods) wrote.
+ *   absolute         != 0: E, dE_dT and K are those of |E| (multiplied by the sign of E), as in bh_ell_batch
+ *   K                [B][nper][4][Lmax]: dE/dh, dE/dvp, dE/dvs, dE/drho per layer (1/km; per km/s; per g/cm^3); the
+ *                    zeros of bh_sens_batch's K
+ *   E, dE_dT         [B][nper]: the ellipticity and its derivative with respect to the period
+ *   c_out            [B][nper]: the polished phase velocity, bit for bit bh_sens_batch's
+ *   K_phase          [B][nper][4][Lmax] or NULL: dc/dm, bit for bit bh_sens_batch's K
+ *   workspace        bh_ell_sens_workspace_bytes(B, nper) bytes
+ * A (model, period) without a value is NaN in K, K_phase, E, dE_dT and c_out together: bh_sens_batch's conditions
+ * (which hold bh_ell_batch's: water on top, fewer than two layers), no vertical motion at the root, or a derivative
+ * that is not finite.  Asynchronous on `stream`.  BH_ERR_ARG, before any device work, for flsph != 0, nper outside
+ * 1 .. 60, a launch that does not fit, and bh_sens_batch's other refusals; BH_ERR_WORKSPACE for a workspace that is
+ * too small. */
+size_t bh_ell_sens_workspace_bytes(int B, int nper);
+int bh_ell_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                      const double *vs, const double *rho, int nper, const double *periods, int flsph, int absolute,
+                      const double *c, int c_stride, const int *c_err, int err_stride,
+                      double *K /*[B][nper][4][Lmax]: h, vp, vs, rho*/, double *E /*[B][nper]*/,
+                      double *dE_dT /*[B][nper]*/, double *c_out /*[B][nper]*/, double *K_phase /*as K, or NULL*/,
+                      void *workspace, size_t workspace_bytes, void *stream);
+/* The ellipticity kernel with vp tied to vs and rho to vp, per layer, for bh_sens_sets_add:
+ *     G[b][p][2][l] = K[b][p][2][l] + q[b][l] (K[b][p][1][l] + drho_dvp K[b][p][3][l]),
+ * each operation rounded once -- the bits of K_vs + q * (K_vp + drho_dvp * K_rho) in IEEE double arithmetic, where
+ * BH_SENS_KIND_VS_TOTAL fuses the chain.  K_vs and q K_vp of the ellipticity cancel to 1e-7 of their size at short
+ * periods, and such a remainder is defined only together with its roundings (csrc/ell_sens_total.hip).  K and G
+ * [B][nper][4][Lmax] (only G's plane 2 is written; G may be K), q [B] rows of q_stride >= Lmax doubles (the layers'
+ * vp / vs).  Hand G to bh_sens_sets_add of a handle created with BH_SENS_KIND_VS.  Asynchronous on `stream`; BH_ERR_ARG,
+ * before any device work, for sizes out of range, a NULL pointer, or a launch that does not fit. */
+int bh_ell_sens_vs_total(int B, int Lmax, int nper, const double *K, const double *q, int q_stride, double drho_dvp,
+                         double *G, void *stream);
+
 /* ---- Voronoi nuclei -> layered models + prior checks (device pointers) ------------------- */
 /* The step in front of the forward path: Model.get_vp_vs_h (src/Models.py:26-52) and
  * SingleChain._validmodel (src/SingleChain.py:330-392) for a batch of proposals.  Input per model:
@@ -408,6 +445,12 @@ int bh_sensitivity(const float *thkm, const float *vpm, const float *vsm, const 
 int bh_group_sensitivity(const float *thkm, const float *vpm, const float *vsm, const float *rhom, int nlayer,
                          int iflsph, int iwave, int kmax, const double *t, double *K /*[kmax][4][nlayer]*/,
                          double *U_out, double *dU_dT, double *c_out, double *K_phase /*as K, or NULL*/, int *err);
+/* Ellipticity sensitivity kernels of one model: the Rayleigh phase search (mode 1, igr 0), then bh_ell_sens_batch's
+ * pass.  K and K_phase (or NULL) [kmax][4][nlayer], E, dE_dT and c_out [kmax].  *err is the search's flag; when it is
+ * set, everything is NaN.  iflsph != 0 is refused (BH_ERR_ARG). */
+int bh_ellipticity_sensitivity(const float *thkm, const float *vpm, const float *vsm, const float *rhom, int nlayer,
+                               int iflsph, int absolute, int kmax, const double *t, double *K /*[kmax][4][nlayer]*/,
+                               double *E, double *dE_dT, double *c_out, double *K_phase /*as K, or NULL*/, int *err);
 
 /* ---- the reference's literal FFI symbols ------------------------------------------------ */
 /* Thin aliases of the two drop-ins above under the names the reference's generated glue binds, so that
