@@ -19,8 +19,8 @@ SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "swd_launch.hip", "rf_c
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
            "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "depthcov_core.h", "datacov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h",
-           "ell_core.h", "ell_launch.h", "interfaces_core.h", "sens_core.h", "sens_launch.h", "sens_sets_core.h",
-           "sens_group_core.h", "sens_group_launch.h", "ell_sens_core.h", "ell_sens_launch.h"]
+           "ell_core.h", "ell_launch.h", "interfaces_core.h", "sens_core.h", "sens_pass.h", "sens_capi_common.h", "sens_sets_core.h",
+           "sens_group_core.h", "ell_sens_core.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->

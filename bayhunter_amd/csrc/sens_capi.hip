@@ -1,16 +1,12 @@
 // sens_capi.hip -- the C ABI of the phase-velocity sensitivity kernels (include/bayhunter_amd.h): bh_sens_batch on device
 // pointers and the synchronous single-model form bh_sensitivity.  Host code only; the kernels are in sensitivity.hip.
-#include <hip/hip_runtime.h>
-#include <vector>
-#include "sens_launch.h"
-#include "host_common.h"
+#include "sens_capi_common.h"
 
 extern "C" {
 
 size_t bh_sens_workspace_bytes(int B, int nper)
 {
-    if (B < 0 || nper < 0) return 0;
-    return (size_t)B * (size_t)nper * sizeof(double);
+    return bh::sens_pass_workspace_bytes(B, nper, 1);
 }
 
 int bh_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp, const double *vs,
@@ -18,27 +14,12 @@ int bh_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const doub
                   const int *c_err, int err_stride, double *K, double *c_out, double *dc_dT, void *workspace,
                   size_t workspace_bytes, void *stream)
 {
-    if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return bh::fail_arg_("B/Lmax out of range");
-    if (model_stride < Lmax) return bh::fail_arg_("model_stride < Lmax");
-    if (iwave != 1 && iwave != 2) return bh::fail_arg_("iwave is neither 1 (Love) nor 2 (Rayleigh)");
-    if (nper < 1 || nper > BH_MAX_PERIODS) return bh::fail_arg_("nper out of range (1 .. 60)");
-    if (flsph != 0) return bh::fail_arg_("flsph: sensitivity kernels are formed on a flat earth only");
-    if (c_stride < nper) return bh::fail_arg_("c_stride shorter than nper");
-    if (err_stride < 1) return bh::fail_arg_("err_stride < 1");
-    if (!nlay || !h || !vp || !vs || !rho || !periods || !c || !c_err || !K || !c_out || !dc_dT)
-        return bh::fail_arg_("NULL pointer");
-    if (B == 0) return BH_OK;
-    if (!workspace || workspace_bytes < bh_sens_workspace_bytes(B, nper))
-        return bh::fail_(BH_ERR_WORKSPACE, "workspace too small (bh_sens_workspace_bytes)");
     bh::SensArgs A;
-    A.B = B; A.Lmax = Lmax; A.nper = nper; A.mstride = model_stride; A.iwave = iwave;
-    A.c_stride = c_stride; A.err_stride = err_stride;
-    A.nlay = nlay; A.h = h; A.vp = vp; A.vs = vs; A.rho = rho;
-    A.periods = periods; A.c = c; A.c_err = c_err;
-    A.K = K; A.c_out = c_out; A.dc_dT = dc_dT; A.fc = (double *)workspace;
-    if (!bh::sens_fits(A)) return bh::fail_arg_("B * nper * 4 * Lmax lanes do not fit one launch");
-    int rc = bh::require_device();
-    if (rc) return rc;
+    const int rc = bh::sens_pass_check(A, B, Lmax, model_stride, nlay, h, vp, vs, rho, &iwave, nper, periods, flsph, c, c_stride,
+                                       c_err, err_stride, K, c_out, dc_dT != nullptr, workspace, workspace_bytes,
+                                       bh_sens_workspace_bytes(B, nper), "workspace too small (bh_sens_workspace_bytes)");
+    if (rc || B == 0) return rc;
+    A.iwave = iwave; A.dc_dT = dc_dT; A.fc = (double *)workspace;
     BH_HIP(bh::launch_sens(A, (hipStream_t)stream));
     return BH_OK;
 }
@@ -46,42 +27,12 @@ int bh_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const doub
 int bh_sensitivity(const float *thkm, const float *vpm, const float *vsm, const float *rhom, int nlayer, int iflsph,
                    int iwave, int kmax, const double *t, double *K, double *c_out, double *dc_dT, int *err)
 {
-    if (!thkm || !vpm || !vsm || !rhom || !t || !K || !c_out || !dc_dT || !err) return bh::fail_arg_("NULL pointer");
-    if (nlayer < 1 || nlayer > BH_MAX_LAYERS) return bh::fail_arg_("nlayer out of range (max 100)");
-    if (kmax < 1 || kmax > BH_MAX_PERIODS) return bh::fail_arg_("kmax out of range (1 .. 60)");
-    if (iwave != 1 && iwave != 2) return bh::fail_arg_("iwave is neither 1 (Love) nor 2 (Rayleigh)");
-    if (iflsph != 0) return bh::fail_arg_("iflsph: sensitivity kernels are formed on a flat earth only");
-    // the search: fundamental-mode phase velocities, through the dispersion drop-in
-    std::vector<double> cg(kmax);
-    int rc = bh_surfdisp96(thkm, vpm, vsm, rhom, nlayer, 0, iwave, 1, 0, kmax, t, cg.data(), err);
-    if (rc) return rc;
-    // the pass: [h|vp|vs|rho|t|c] fp64 (exactly representable fp32 layers), then [c_out|dc_dT|F_c|K] and [nlay, err]
-    const int L = nlayer;
-    std::vector<double> hb(4 * (size_t)L + 2 * (size_t)kmax);
-    for (int i = 0; i < L; i++) {
-        hb[i] = thkm[i]; hb[L + i] = vpm[i]; hb[2 * L + i] = vsm[i]; hb[3 * L + i] = rhom[i];
-    }
-    for (int k = 0; k < kmax; k++) { hb[4 * L + k] = t[k]; hb[4 * L + kmax + k] = cg[k]; }
-    const size_t nK = (size_t)kmax * 4 * L;
-    const size_t off_out = hb.size() * sizeof(double);
-    const size_t off_int = off_out + (3 * (size_t)kmax + nK) * sizeof(double);
-    rc = bh::g_scratch.ensure(off_int + 2 * sizeof(int));
-    if (rc) return rc;
-    char *d = (char *)bh::g_scratch.p;
-    BH_HIP(hipMemcpy(d, hb.data(), off_out, hipMemcpyHostToDevice));
-    const int ints[2] = {nlayer, *err};
-    BH_HIP(hipMemcpy(d + off_int, ints, sizeof(ints), hipMemcpyHostToDevice));
-    const double *dm = (const double *)d;
-    double *dout = (double *)(d + off_out);
-    rc = bh_sens_batch(1, L, L, (const int *)(d + off_int), dm, dm + L, dm + 2 * L, dm + 3 * L, iwave, kmax, dm + 4 * L, 0,
-                       dm + 4 * L + kmax, kmax, (const int *)(d + off_int) + 1, 1, dout + 3 * kmax, dout, dout + kmax,
-                       dout + 2 * kmax, kmax * sizeof(double), nullptr);
-    if (rc) return rc;
-    BH_HIP(hipDeviceSynchronize());
-    BH_HIP(hipMemcpy(c_out, dout, kmax * sizeof(double), hipMemcpyDeviceToHost));
-    BH_HIP(hipMemcpy(dc_dT, dout + kmax, kmax * sizeof(double), hipMemcpyDeviceToHost));
-    BH_HIP(hipMemcpy(K, dout + 3 * kmax, nK * sizeof(double), hipMemcpyDeviceToHost));
-    return BH_OK;
+    double *const out[] = {c_out, dc_dT};
+    return bh::sens_pass_single(thkm, vpm, vsm, rhom, nlayer, iflsph, &iwave, kmax, t, 1, K, nullptr, out, 2, err,
+                                [&](const bh::SensStaged &s) {
+                                    return bh_sens_batch(1, s.L, s.L, s.nlay, s.h, s.vp, s.vs, s.rho, iwave, s.kmax, s.t, 0, s.c,
+                                                         s.kmax, s.err, 1, s.K, s.out[0], s.out[1], s.ws, s.ws_bytes, nullptr);
+                                });
 }
 
 }  // extern "C"

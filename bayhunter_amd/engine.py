@@ -207,17 +207,14 @@ class ForwardEngine(object):
                     t.record_stream(side)
         return out, err
 
-    def sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, target=0, stream=None):
-        """Depth sensitivity kernels of dispersion target `target` for the batch (bh_sens_batch, asynchronous): the
-        polished phase velocity c [B, nper], dc/dT [B, nper] and K [B, nper, 4, Lmax] = dc/dh, dc/dvp, dc/dvs, dc/drho
-        per layer, device tensors in a dict.  `out`, `err`: what run() returned for these models -- the pass reads the
-        engine's own phase velocities -- or None: run() is called first.  Fundamental-mode phase targets on a flat earth
-        with at most 60 periods only; a (model, period) without a value is NaN (include/bayhunter_amd.h)."""
-        models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
+    # -- the sensitivity passes (csrc/sens_pass.h)
+    def _sens_swd_target(self, target, igr=False):
+        """Dispersion target `target`, checked for what the phase and group passes serve (igr: a group-velocity target
+        is served too)."""
         if not 0 <= target < len(self.layout.swd_all):
             raise ValueError("target %r: the engine solves %d dispersion targets" % (target, len(self.layout.swd_all)))
         spec = self.layout.swd_all[target]
-        if spec.igr != 0:
+        if spec.igr != 0 and not igr:
             raise ValueError("sensitivity: target '%s' has igr = %d; group-velocity targets are not served" % (spec.ref, spec.igr))
         if spec.mode != 1:
             raise ValueError("sensitivity: target '%s' has mode = %d; only the fundamental mode is served" % (spec.ref, spec.mode))
@@ -225,21 +222,43 @@ class ForwardEngine(object):
             raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (spec.ref, spec.flsph))
         if spec.resample:
             raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
+        return spec
+
+    def _sens_buffers(self, src, models, out, err, nper, workspace_bytes, stream, nK, nrow):
+        """What a pass reads and writes: (out, err) as given, or of `src`.run(models); the launch stream; nK tensors
+        [B, nper, 4, Lmax], nrow tensors [B, nper] and the workspace (workspace_bytes: the pass's bh_*_workspace_bytes),
+        allocated on that stream."""
         if out is None or err is None:
-            out, err = self.run(models, stream=stream)
+            out, err = src.run(models, stream=stream)
         st = torch.cuda.current_stream(self.device) if stream is None else stream
-        B, Lmax, nper = models.B, models.Lmax, spec.periods.size
-        tg = self._tg[target]
-        need = self.lib.bh_sens_workspace_bytes(B, nper)
+        B, Lmax = models.B, models.Lmax
+        need = workspace_bytes(B, nper)
         with torch.cuda.stream(st):
-            K = torch.empty((B, nper, 4, Lmax), dtype=torch.float64, device=self.device)
-            c = torch.empty((B, nper), dtype=torch.float64, device=self.device)
-            dc_dT = torch.empty((B, nper), dtype=torch.float64, device=self.device)
+            Ks = [torch.empty((B, nper, 4, Lmax), dtype=torch.float64, device=self.device) for _ in range(nK)]
+            rows = [torch.empty((B, nper), dtype=torch.float64, device=self.device) for _ in range(nrow)]
             ws = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=self.device)
+        return out, err, st, Ks, rows, ws
+
+    @staticmethod
+    def _sens_models(models):
+        """The leading arguments of a pass's batch entry point: B, Lmax, model_stride, nlay, h, vp, vs, rho."""
+        return (models.B, models.Lmax, 4 * models.Lmax, models.nlay.data_ptr(), models.H.data_ptr(), models.VP.data_ptr(),
+                models.VS.data_ptr(), models.RHO.data_ptr())
+
+    def sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, out=None, err=None, target=0, stream=None):
+        """Depth sensitivity kernels of dispersion target `target` for the batch (bh_sens_batch, asynchronous): the
+        polished phase velocity c [B, nper], dc/dT [B, nper] and K [B, nper, 4, Lmax] = dc/dh, dc/dvp, dc/dvs, dc/drho
+        per layer, device tensors in a dict.  `out`, `err`: what run() returned for these models -- the pass reads the
+        engine's own phase velocities -- or None: run() is called first.  Fundamental-mode phase targets on a flat earth
+        with at most 60 periods only; a (model, period) without a value is NaN (include/bayhunter_amd.h)."""
+        models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
+        spec = self._sens_swd_target(target)
+        nper, tg = spec.periods.size, self._tg[target]
+        out, err, st, (K,), (c, dc_dT), ws = self._sens_buffers(self, models, out, err, nper,
+                                                                 self.lib.bh_sens_workspace_bytes, stream, 1, 2)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.bh_sens_batch(
-                B, Lmax, 4 * Lmax, models.nlay.data_ptr(), models.H.data_ptr(), models.VP.data_ptr(), models.VS.data_ptr(),
-                models.RHO.data_ptr(), spec.iwave, nper, self.periods.data_ptr() + 8 * tg.per_off, 0,
+                *self._sens_models(models), spec.iwave, nper, self.periods.data_ptr() + 8 * tg.per_off, 0,
                 out.data_ptr() + 8 * tg.out_off, self.row, err.data_ptr() + 4 * target, max(1, self._nswd), K.data_ptr(),
                 c.data_ptr(), dc_dT.data_ptr(), ws.data_ptr(), ws.numel() * 8, C.c_void_p(st.cuda_stream)))
         return {'c': c, 'dc_dT': dc_dT, 'K': K}
@@ -254,16 +273,7 @@ class ForwardEngine(object):
         and run on the same DeviceModels.  `out`, `err`: what run() returned for these models, or None: run() is called
         first.  Fundamental mode, flat earth, at most 60 periods; a (model, period) without a value is NaN."""
         models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
-        if not 0 <= target < len(self.layout.swd_all):
-            raise ValueError("target %r: the engine solves %d dispersion targets" % (target, len(self.layout.swd_all)))
-        spec = self.layout.swd_all[target]
-        if spec.mode != 1:
-            raise ValueError("sensitivity: target '%s' has mode = %d; only the fundamental mode is served" % (spec.ref, spec.mode))
-        if spec.flsph != 0:
-            raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (spec.ref, spec.flsph))
-        if spec.resample:
-            raise ValueError("sensitivity: target '%s' has more than %d periods" % (spec.ref, _lib.MAX_PERIODS))
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        spec = self._sens_swd_target(target, igr=True)
         src, source = self, target
         if spec.igr != 0:
             equal = [t for t, sp in enumerate(self.layout.swd_all)
@@ -279,19 +289,12 @@ class ForwardEngine(object):
                     src = self._phase_companions[target] = ForwardEngine(
                         swd=[SwdSpec('rdispph' if spec.iwave == 2 else 'ldispph', spec.periods)], device=self.device)
                 source, out, err = 0, None, None
-        if out is None or err is None:
-            out, err = src.run(models, stream=stream)
-        B, Lmax, nper = models.B, models.Lmax, spec.periods.size
-        tg = src._tg[source]
-        need = self.lib.bh_sens_group_workspace_bytes(B, nper)
-        with torch.cuda.stream(st):
-            K, Kp = (torch.empty((B, nper, 4, Lmax), dtype=torch.float64, device=self.device) for _ in range(2))
-            U, dU_dT, c = (torch.empty((B, nper), dtype=torch.float64, device=self.device) for _ in range(3))
-            ws = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=self.device)
+        nper, tg = spec.periods.size, src._tg[source]
+        out, err, st, (K, Kp), (U, dU_dT, c), ws = self._sens_buffers(src, models, out, err, nper,
+                                                                      self.lib.bh_sens_group_workspace_bytes, stream, 2, 3)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.bh_sens_group_batch(
-                B, Lmax, 4 * Lmax, models.nlay.data_ptr(), models.H.data_ptr(), models.VP.data_ptr(), models.VS.data_ptr(),
-                models.RHO.data_ptr(), spec.iwave, nper, src.periods.data_ptr() + 8 * tg.per_off, 0,
+                *self._sens_models(models), spec.iwave, nper, src.periods.data_ptr() + 8 * tg.per_off, 0,
                 out.data_ptr() + 8 * tg.out_off, src.row, err.data_ptr() + 4 * source, max(1, src._nswd), K.data_ptr(),
                 U.data_ptr(), dU_dT.data_ptr(), c.data_ptr(), Kp.data_ptr(), ws.data_ptr(), ws.numel() * 8,
                 C.c_void_p(st.cuda_stream)))
@@ -313,21 +316,14 @@ class ForwardEngine(object):
         e = self.ell[target]
         if e.flsph != 0:
             raise ValueError("sensitivity: target '%s' has flsph = %d; only a flat earth is served" % (e.ref, e.flsph))
-        if out is None or err is None:
-            out, err = self.run(models, stream=stream)
-        st = torch.cuda.current_stream(self.device) if stream is None else stream
         t, per_off, c_off = self.layout.ell_src[target]
-        B, Lmax, nper = models.B, models.Lmax, e.periods.size
+        nper = e.periods.size
         absolute = e.absolute if absolute is None else bool(absolute)
-        need = self.lib.bh_ell_sens_workspace_bytes(B, nper)
-        with torch.cuda.stream(st):
-            K, Kp = (torch.empty((B, nper, 4, Lmax), dtype=torch.float64, device=self.device) for _ in range(2))
-            E, dE_dT, c = (torch.empty((B, nper), dtype=torch.float64, device=self.device) for _ in range(3))
-            ws = torch.empty(max(1, (need + 7) // 8), dtype=torch.float64, device=self.device)
+        out, err, st, (K, Kp), (E, dE_dT, c), ws = self._sens_buffers(self, models, out, err, nper,
+                                                                      self.lib.bh_ell_sens_workspace_bytes, stream, 2, 3)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.bh_ell_sens_batch(
-                B, Lmax, 4 * Lmax, models.nlay.data_ptr(), models.H.data_ptr(), models.VP.data_ptr(), models.VS.data_ptr(),
-                models.RHO.data_ptr(), nper, self.periods.data_ptr() + 8 * per_off, 0, 1 if absolute else 0,
+                *self._sens_models(models), nper, self.periods.data_ptr() + 8 * per_off, 0, 1 if absolute else 0,
                 out.data_ptr() + 8 * c_off, self.row, err.data_ptr() + 4 * t, max(1, self._nswd), K.data_ptr(), E.data_ptr(),
                 dE_dT.data_ptr(), c.data_ptr(), Kp.data_ptr(), ws.data_ptr(), ws.numel() * 8, C.c_void_p(st.cuda_stream)))
         return {'K': K, 'E': E, 'dE_dT': dE_dT, 'c': c, 'K_phase': Kp}

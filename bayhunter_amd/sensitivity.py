@@ -40,59 +40,52 @@ from . import _lib, selection as sel
 KINDS = ('h', 'vp', 'vs', 'rho')          # K's kind axis
 REFS = {'rayleigh': 'rdispph', 'love': 'ldispph'}
 GROUP_REFS = {'rayleigh': 'rdispgr', 'love': 'ldispgr'}
-VELOCITIES = ('phase', 'group', 'ellipticity')
+# per velocity: the engine's pass, the key of the value that counts a (row, period), and the doubles per (row, period) the
+# pass holds beyond the phase pass's besides its K_phase (None: no K_phase either) -- group: U and the five further
+# doubles of workspace; ellipticity: E and the two further doubles of workspace
+PASSES = {'phase': ('sensitivity', 'c', None), 'group': ('group_sensitivity', 'U', 6), 'ellipticity': ('ell_sensitivity', 'E', 3)}
+VELOCITIES = tuple(PASSES)
+
+
+def _batch(eng, method, H, VP, VS, RHO, nlay):
+    """The search and pass `method` of engine `eng` for B models, every result as a numpy array, plus err [B]."""
+    import torch
+    models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
+    out, err = eng.run(models)
+    res = getattr(eng, method)(models, out=out, err=err)
+    torch.cuda.synchronize(eng.device)
+    res = {k: v.cpu().numpy() for k, v in res.items()}
+    res['err'] = err.cpu().numpy()[:, 0]
+    return res
+
+
+def _phase_engine(periods, wave):
+    from .engine import ForwardEngine, SwdSpec
+    if wave not in REFS:
+        raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
+    return ForwardEngine(swd=[SwdSpec(REFS[wave], periods)])
 
 
 def batch(periods, H, VP, VS, RHO, nlay, wave='rayleigh'):
     """Search and pass on the device for B models ([B, Lmax] arrays, nlay [B]) at up to 60 periods: dict of numpy
     arrays c [B, nper] (the polished phase velocity), dc_dT [B, nper], K [B, nper, 4, Lmax] (KINDS), err [B] (the
     search's flag).  A (model, period) without a value is NaN."""
-    import torch
-    from .engine import ForwardEngine, SwdSpec
-    if wave not in REFS:
-        raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
-    eng = ForwardEngine(swd=[SwdSpec(REFS[wave], periods)])
-    models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
-    out, err = eng.run(models)
-    res = eng.sensitivity(models, out=out, err=err)
-    torch.cuda.synchronize(eng.device)
-    res = {k: v.cpu().numpy() for k, v in res.items()}
-    res['err'] = err.cpu().numpy()[:, 0]
-    return res
+    return _batch(_phase_engine(periods, wave), 'sensitivity', H, VP, VS, RHO, nlay)
 
 
 def group_batch(periods, H, VP, VS, RHO, nlay, wave='rayleigh'):
     """batch() for the group velocity: dict of numpy arrays U [B, nper] (the analytic group velocity), dU_dT, c [B, nper],
     K [B, nper, 4, Lmax] = dU/dm (KINDS), K_phase (batch()'s K), err [B] (the phase search's flag).  A (model, period)
     without a value is NaN in all of them."""
-    import torch
-    from .engine import ForwardEngine, SwdSpec
-    if wave not in REFS:
-        raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
-    eng = ForwardEngine(swd=[SwdSpec(REFS[wave], periods)])
-    models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
-    out, err = eng.run(models)
-    res = eng.group_sensitivity(models, out=out, err=err)
-    torch.cuda.synchronize(eng.device)
-    res = {k: v.cpu().numpy() for k, v in res.items()}
-    res['err'] = err.cpu().numpy()[:, 0]
-    return res
+    return _batch(_phase_engine(periods, wave), 'group_sensitivity', H, VP, VS, RHO, nlay)
 
 
 def ell_batch(periods, H, VP, VS, RHO, nlay, absolute=True):
     """batch() for the Rayleigh-wave ellipticity: dict of numpy arrays E [B, nper] (H/V at the polished root; |H/V| with
     absolute), dE_dT, c [B, nper], K [B, nper, 4, Lmax] = dE/dm (KINDS), K_phase (batch()'s K for Rayleigh waves), err [B]
     (the phase search's flag).  A (model, period) without a value is NaN in all of them."""
-    import torch
     from .engine import EllSpec, ForwardEngine
-    eng = ForwardEngine(ell=[EllSpec('rellip', periods, 0, absolute)])
-    models = eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32))
-    out, err = eng.run(models)
-    res = eng.ell_sensitivity(models, out=out, err=err)
-    torch.cuda.synchronize(eng.device)
-    res = {k: v.cpu().numpy() for k, v in res.items()}
-    res['err'] = err.cpu().numpy()[:, 0]
-    return res
+    return _batch(ForwardEngine(ell=[EllSpec('rellip', periods, 0, absolute)]), 'ell_sensitivity', H, VP, VS, RHO, nlay)
 
 
 def vs_total(K, dvp_dvs, drho_dvp=0.32):
@@ -287,6 +280,7 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
         raise ValueError("velocity %r: 'phase', 'group' or 'ellipticity'" % (velocity,))
     if velocity == 'ellipticity' and wave != 'rayleigh':
         raise ValueError("velocity 'ellipticity': wave %r; the ellipticity is the Rayleigh wave's" % (wave,))
+    method, counted, extra = PASSES[velocity]
     code, edges = _check_kind(kind), _check_edges(dep_edges)
     periods = np.ascontiguousarray(periods, dtype=np.float64)
     shape = getattr(models, 'shape', None) or np.asarray(models).shape
@@ -324,10 +318,8 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
         Lmax, nper = shape[1] // 2, periods.size
         if max_rows is None:       # half of the free device memory: K, c, dc/dT and the workspace, the row, its layers
             per_row = 8 * (4 * nper * Lmax + 3 * nper + eng.row + shape[1] + 8 * Lmax) + 16      # (packed, nuclei, q)
-            if velocity == 'group':             # K_phase, U and the five further doubles of workspace per period
-                per_row += 8 * (4 * nper * Lmax + 6 * nper)
-            if velocity == 'ellipticity':       # K_phase, E and the two further doubles of workspace per period
-                per_row += 8 * (4 * nper * Lmax + 3 * nper)
+            if extra is not None:
+                per_row += 8 * (4 * nper * Lmax + extra * nper)
             max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
         # The ellipticity's K_vs and (vp / vs) K_vp cancel to 1e-7 of their size at short periods: its 'vs_total' is formed
         # per layer in vs_total()'s own operation order (bh_ell_sens_vs_total, in place of K_vs) and reduced as kind 'vs'
@@ -344,15 +336,8 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
                 vsn, zv, nl = df._layers(rows, dev)
                 dm, _ = layers_from_voronoi(vsn, zv, nl, v, df._OPEN_PRIORS, mantle=mantle, device=dev)
                 out, err = eng.run(dm)
-                if velocity == 'group':
-                    res = eng.group_sensitivity(dm, out=out, err=err)
-                    K, c = res['K'], res['U']
-                elif velocity == 'ellipticity':
-                    res = eng.ell_sensitivity(dm, out=out, err=err)
-                    K, c = res['K'], res['E']
-                else:
-                    res = eng.sensitivity(dm, out=out, err=err)
-                    K, c = res['K'], res['c']
+                res = getattr(eng, method)(dm, out=out, err=err)
+                K, c = res['K'], res[counted]
                 q = (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None
                 if plain_total:
                     _lib.check(handle.lib.bh_ell_sens_vs_total(dm.B, dm.Lmax, nper, K.data_ptr(), q.data_ptr(), q.stride(0),
