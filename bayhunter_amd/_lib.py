@@ -15,12 +15,12 @@ SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "swd_launch.hip", "rf_c
            "datafits.hip", "moho.hip", "pairs.hip", "autocov.hip", "depthcov.hip", "datacov.hip", "math_probe.hip", "rf_probe.hip",
            "ellipticity.hip", "ell_rows.hip", "ell_capi.hip", "interfaces.hip", "sensitivity.hip", "sens_capi.hip", "sens_sets.hip",
            "sens_group.hip", "sens_group_capi.hip", "ell_sens.hip", "ell_sens_capi.hip",
-           "ell_sens_total.hip"]
+           "ell_sens_total.hip", "rf_sens.hip", "rf_sens_capi.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
            "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "depthcov_core.h", "datacov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h",
            "ell_core.h", "ell_launch.h", "interfaces_core.h", "sens_core.h", "sens_pass.h", "sens_capi_common.h", "sens_sets_core.h",
-           "sens_group_core.h", "ell_sens_core.h"]
+           "sens_group_core.h", "ell_sens_core.h", "rf_sens_core.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->
@@ -260,6 +260,11 @@ _SIGS = {
     "bh_ell_sens_vs_total": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_double, _vp, _vp]),
     "bh_ellipticity_sensitivity": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp,
                                              _vp, C.POINTER(C.c_int)]),
+    "bh_rf_sens_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "bh_rf_sens_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RfParams), _vp,
+                                   C.c_longlong, _vp, C.c_int, _vp, C.c_size_t, _vp]),
+    "bh_rf_sensitivity": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                    C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bh_sens_sets_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_double, _vp]),
     "bh_sens_sets_add": (C.c_int, [_vp, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "bh_sens_sets_finish": (C.c_int, [_vp] * 7),

@@ -34,6 +34,19 @@ extern thread_local Scratch g_scratch;
 
 // rf_capi.hip.  bh_rf_batch's parameter checks: bh_forward_batch (evalplan.hip) makes them before its first launch
 int check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool zr);
+// rf_capi.hip.  The two cached device tables of a receiver-function launch (FFT twiddles; per-frequency constants) for
+// the launch constants P of rf_fill_launch: rf_sens_capi.hip launches with the tables bh_rf_batch's launches read.  The
+// frequency table stays pinned in its cache until the RfTables object goes.
+struct RfLaunch;
+struct RfTables {
+    const double *tw = nullptr, *ftab = nullptr;
+    void *pin = nullptr;
+    RfTables() = default;
+    RfTables(const RfTables &) = delete;
+    RfTables &operator=(const RfTables &) = delete;
+    ~RfTables();
+};
+int rf_get_tables(const RfLaunch &P, double fsamp, RfTables *tables);
 
 // like_capi.hip: the kept-sample tables of a set_present mask (evalplan.hip: bh_eval_set_gaps), and the likelihood of
 // observation sets with or without data gaps (bh_likelihood_sets, bh_likelihood_sets_gaps; evalplan.hip)

@@ -177,6 +177,17 @@ int bh::check_rf_params(const bh_rf_params *par, int Lmax, int out_stride, bool 
     return BH_OK;
 }
 
+bh::RfTables::~RfTables() { delete (FreqTablePin *)pin; }
+
+int bh::rf_get_tables(const bh::RfLaunch &P, double fsamp, bh::RfTables *tables)
+{
+    int rc = get_twiddles(P.nsamp, &tables->tw);
+    if (rc) return rc;
+    FreqTablePin *pin = new FreqTablePin;
+    tables->pin = pin;
+    return get_freq_table(P, fsamp, &tables->ftab, pin);
+}
+
 extern "C" {
 
 size_t bh_rf_workspace_bytes(int, int, const bh_rf_params *) { return 0; }

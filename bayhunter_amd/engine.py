@@ -327,3 +327,26 @@ class ForwardEngine(object):
                 out.data_ptr() + 8 * c_off, self.row, err.data_ptr() + 4 * t, max(1, self._nswd), K.data_ptr(), E.data_ptr(),
                 dE_dT.data_ptr(), c.data_ptr(), Kp.data_ptr(), ws.data_ptr(), ws.numel() * 8, C.c_void_p(st.cuda_stream)))
         return {'K': K, 'E': E, 'dE_dT': dE_dT, 'c': c, 'K_phase': Kp}
+
+    def rf_sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, target=0, stream=None):
+        """Sensitivity kernels of RECEIVER-FUNCTION target `target` (an index into the engine's receiver-function targets)
+        for the batch (bh_rf_sens_batch, asynchronous): K [B, nt, 4, Lmax] = dRF(t)/dh, dRF/dvp, dRF/dvs, dRF/drho per
+        layer and sample of the target's time axis, and rf [B, nt], the trace itself, bit for bit what run() writes into
+        the target's columns -- device tensors in a dict, with 't' [nt], the time axis (numpy).  The time samples sit
+        where the dispersion kernels have periods.  The engine's slowness for every row (run()'s rf_sets are not served);
+        K is 0 for the half-space's thickness and NaN in the layers a model does not have (include/bayhunter_amd.h)."""
+        models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
+        if not 0 <= target < len(self.rf):
+            raise ValueError("target %r: the engine has %d receiver-function targets" % (target, len(self.rf)))
+        if models.packed.device != self.device:
+            raise ValueError("models live on %s, engine on %s" % (models.packed.device, self.device))
+        spec, par = self.rf[target], self._rfp[target]
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        B, Lmax, nt = models.B, models.Lmax, spec.obsx.size
+        with torch.cuda.stream(st):
+            K = torch.empty((B, nt, 4, Lmax), dtype=torch.float64, device=self.device)
+            rf = torch.empty((B, nt), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.bh_rf_sens_batch(*self._sens_models(models), None, None, C.byref(par), K.data_ptr(),
+                                                 nt * 4 * Lmax, rf.data_ptr(), nt, None, 0, C.c_void_p(st.cuda_stream)))
+        return {'K': K, 'rf': rf, 't': (np.arange(int(spec.nsamp)) / spec.fsamp - spec.tshft)[:nt]}

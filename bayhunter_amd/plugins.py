@@ -215,6 +215,29 @@ class RFminiModRF(_Plugin):
         h, vp, vs, rho = (np.asarray(a, dtype=float) for a in (h, vp, vs, rho))
         return self.compute_rf(h, vp, vs, rho, **params)
 
+    def sensitivity(self, h, vp, vs, rho, **params):
+        """Sensitivity kernels of the receiver function of one model through bh_rf_sensitivity: dict K [nt, 4, nlayer] =
+        dRF(t)/dh, dRF/dvp, dRF/dvs, dRF/drho per layer and sample (change of the trace per km, per km/s, per g/cm^3),
+        rf [nt] (run_model's trace) and t [nt], on the observed time axis.  The derivative is that of the trace as
+        run_model computes it with the plugin's modelparams (p, gauss, nsv, wtype; `water` has no effect): Poisson's
+        ratio -- and nsv when it is None -- follow the perturbed top layer, qp and qs are held fixed.  NaN throughout
+        for a model without a trace (run_model: (nan, nan) or a NaN trace), but the 0 of the half-space's thickness."""
+        h, vp, vs, rho = (np.ascontiguousarray(a, dtype=np.float64) for a in (h, vp, vs, rho))
+        if not (h.size == vp.size == vs.size == rho.size):
+            raise AssertionError("h, vp, vs, rho must have the same length")
+        lib = _lib.load()
+        n, nt, nsamp = h.size, self.obsx.size, int(self.nsamp)
+        qp = np.ascontiguousarray(params.get('qp', np.full(n, 500.)), dtype=np.float64)
+        qs = np.ascontiguousarray(params.get('qs', np.full(n, 225.)), dtype=np.float64)
+        depth = np.ascontiguousarray(np.concatenate(([0], np.cumsum(h)[:-1])))   # layer tops
+        nsv = self.modelparams['nsv']
+        trace, K = np.zeros(nsamp), np.zeros((nsamp, 4, n))
+        _lib.check(lib.bh_rf_sensitivity(nsamp, self.fsamp, self.tshft, self.modelparams['p'], self.modelparams['gauss'],
+                                         -1.0 if nsv is None else nsv, float('nan'), self._waveno(), n, depth.ctypes.data,
+                                         vp.ctypes.data, vs.ctypes.data, rho.ctypes.data, qp.ctypes.data, qs.ctypes.data,
+                                         None, None, trace.ctypes.data, K.ctypes.data))
+        return {'K': K[:nt].copy(), 'rf': trace[:nt].copy(), 't': self._time_axis()}
+
     def run_models(self, H, VP, VS, RHO, nlay):
         """Batch of models ([B, Lmax] arrays) -> (time, RF[B, nobs])."""
         if self._engine is None:

@@ -32,6 +32,13 @@ K^E = dE/dm = G_m + G_c dc/dm, the change of H/V per km/s of the layer (per g/cm
     ell_batch(periods, H, VP, VS, RHO, nlay, absolute)   the device search and the ellipticity pass for a batch of models
     summarize / summarize_sets (velocity='ellipticity')  the depth-binned dE/dm over an ensemble
     ChainPool.ell_sensitivity / StationPool.ell_sensitivity          (pool_sensitivity, stations_sensitivity)
+
+And for the receiver function (csrc/rf_sens_core.h): K[t] = dRF(t)/dm, central differences of two
+perturbed traces per entry, formed in LDS.  Time samples sit where the other kernels have periods, so vs_total and
+to_depth apply unchanged.  There is no summary over pools (bh_sens_sets holds at most 60 "periods").
+
+    rf_batch(rfparams, H, VP, VS, RHO, nlay, ref)        the pass for a batch of models
+    plugins.RFminiModRF.sensitivity / ForwardEngine.rf_sensitivity
 """
 import numpy as np
 
@@ -86,6 +93,24 @@ def ell_batch(periods, H, VP, VS, RHO, nlay, absolute=True):
     (the phase search's flag).  A (model, period) without a value is NaN in all of them."""
     from .engine import EllSpec, ForwardEngine
     return _batch(ForwardEngine(ell=[EllSpec('rellip', periods, 0, absolute)]), 'ell_sensitivity', H, VP, VS, RHO, nlay)
+
+
+def rf_batch(rfparams, H, VP, VS, RHO, nlay, ref='prf'):
+    """The receiver-function pass on the device for B models ([B, Lmax] arrays, nlay [B]): dict of numpy arrays
+    K [B, nt, 4, Lmax] = dRF(t)/dm (KINDS), rf [B, nt] (the trace, bh_rf_batch's bits) and t [nt].  rfparams: a dict with
+    'obsx', the uniformly sampled time axis of the target, and optionally 'gauss' (1.0), 'p' [s/deg] (6.4) and 'nsv'
+    (None: the top layer's vs) -- plugins.RFminiModRF's modelparams; ref 'prf' | 'seis' (incident P) or 'srf' (SV).
+    NaN in the layers a model does not have, and throughout for a model without a trace."""
+    import torch
+    from .engine import ForwardEngine, RfSpec
+    unknown = set(rfparams) - {'obsx', 'gauss', 'p', 'nsv', 'water', 'wtype'}
+    if 'obsx' not in rfparams or unknown:
+        raise ValueError("rfparams: a dict with 'obsx' and optionally 'gauss', 'p', 'nsv' (unknown: %s)" % sorted(unknown))
+    eng = ForwardEngine(rf=[RfSpec(ref, rfparams['obsx'], rfparams.get('gauss', 1.0), rfparams.get('p', 6.4),
+                                   rfparams.get('nsv'), wtype=rfparams.get('wtype'))])
+    res = eng.rf_sensitivity(eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32)))
+    torch.cuda.synchronize(eng.device)
+    return {'K': res['K'].cpu().numpy(), 'rf': res['rf'].cpu().numpy(), 't': res['t']}
 
 
 def vs_total(K, dvp_dvs, drho_dvp=0.32):

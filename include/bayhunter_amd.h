@@ -303,6 +303,29 @@ int bh_ell_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const 
 int bh_ell_sens_vs_total(int B, int Lmax, int nper, const double *K, const double *q, int q_stride, double drho_dvp,
                          double *G, void *stream);
 
+/* dRF(t)/dm of the receiver function (csrc/rf_sens_core.h): K[t][kind][layer] is the derivative of sample t of the trace
+ * bh_rf_batch returns -- spectral division, Gauss filter and normalisation included -- with respect to the thickness,
+ * vp, vs and density of every layer.  The trace is an explicit function of the model, so each entry is a central
+ * difference of two traces with the one entry multiplied by 1 +- r, r a power of two per kind; the perturbed traces are
+ * computed and differenced in LDS by one kernel, rf_sens_kernel, which runs the phases of bh_rf_batch's kernel.  qp and
+ * qs are held fixed; the rotation velocities derived from the top layer follow the perturbed top layer.
+ * Arguments as for bh_rf_batch (device pointers, thickness rows; there is no depth form), with the same par:
+ *   K                [B] rows of k_stride >= nout * 4 * Lmax doubles, [nout][4][Lmax]: dRF/dh, dRF/dvp, dRF/dvs, dRF/drho
+ *                    per layer (1/km; per km/s; per g/cm^3).  0 for the half-space's thickness and for an entry whose
+ *                    value is zero; NaN in the layers from nlay on, and throughout for a model bh_rf_batch returns NaN
+ *                    for (nlay outside 1 .. Lmax)
+ *   rf               NULL, or [B] rows of rf_stride >= nout doubles: the unperturbed trace, bit for bit bh_rf_batch's
+ *   par->out_off     ignored: K and rf are rows of their own
+ *   workspace        none is needed: bh_rf_sens_workspace_bytes is 0 and workspace may be NULL
+ * Asynchronous on `stream`.  BH_ERR_ARG, before any device work, for bh_rf_batch's refusals, a k_stride or rf_stride
+ * shorter than the row, and a launch that does not fit (B times the slot chunks of a model above 2^31 - 1). */
+size_t bh_rf_sens_workspace_bytes(int Lmax, int nsamp);
+int bh_rf_sens_batch(int B, int Lmax, int model_stride, const int *nlay, const double *h, const double *vp,
+                     const double *vs, const double *rho, const double *qp /*[B][Lmax] or NULL*/,
+                     const double *qs /*[B][Lmax] or NULL*/, const bh_rf_params *par,
+                     double *K /*[B][nout][4][Lmax]: h, vp, vs, rho*/, long long k_stride, double *rf /*[B][nout] or NULL*/,
+                     int rf_stride, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Voronoi nuclei -> layered models + prior checks (device pointers) ------------------- */
 /* The step in front of the forward path: Model.get_vp_vs_h (src/Models.py:26-52) and
  * SingleChain._validmodel (src/SingleChain.py:330-392) for a batch of proposals.  Input per model:
@@ -451,6 +474,15 @@ int bh_group_sensitivity(const float *thkm, const float *vpm, const float *vsm, 
 int bh_ellipticity_sensitivity(const float *thkm, const float *vpm, const float *vsm, const float *rhom, int nlayer,
                                int iflsph, int absolute, int kmax, const double *t, double *K /*[kmax][4][nlayer]*/,
                                double *E, double *dE_dT, double *c_out, double *K_phase /*as K, or NULL*/, int *err);
+
+/* Receiver-function sensitivity kernels of one model from host memory: the argument list of bh_synrf plus K
+ * [nsamp][4][nlay].  rf (and fz, fr when given) are bh_synrf's; K is bh_rf_sens_batch's pass on the thicknesses
+ * z[i+1] - z[i].  sigma NaN and nsv <= 0: Poisson's ratio and the rotation velocity of the top layer, which then follow
+ * the perturbed top layer as in bh_rf_sens_batch; given values are held fixed. */
+int bh_rf_sensitivity(int nsamp, double fsamp, double tshift, double p, double a, double nsv, double sigma,
+                      int waveno, int nlay, const double *z, const double *vp, const double *vs,
+                      const double *rh, const double *qp, const double *qs,
+                      double *fz, double *fr, double *rf, double *K /*[nsamp][4][nlay]*/);
 
 /* ---- the reference's literal FFI symbols ------------------------------------------------ */
 /* Thin aliases of the two drop-ins above under the names the reference's generated glue binds, so that
