@@ -15,12 +15,12 @@ SOURCES = ["kernels.hip", "like_kernel.hip", "capi.hip", "swd_launch.hip", "rf_c
            "datafits.hip", "moho.hip", "pairs.hip", "autocov.hip", "depthcov.hip", "datacov.hip", "math_probe.hip", "rf_probe.hip",
            "ellipticity.hip", "ell_rows.hip", "ell_capi.hip", "interfaces.hip", "sensitivity.hip", "sens_capi.hip", "sens_sets.hip",
            "sens_group.hip", "sens_group_capi.hip", "ell_sens.hip", "ell_sens_capi.hip",
-           "ell_sens_total.hip", "rf_sens.hip", "rf_sens_capi.hip"]
+           "ell_sens_total.hip", "rf_sens.hip", "rf_sens_capi.hip", "rf_sens_sets.hip"]
 HEADERS = ["bh_common.h", "bh_math.h", "swd_core.h", "swd_team.h", "rf_core.h", "rf_host.h", "kernels.h", "like_core.h",
            "swd_form_table.h", "posterior_core.h", "posterior_kernel.h", "datafits_kernel.h", "stats_core.h",
            "stats_host.h", "moho_core.h", "pairs_core.h", "autocov_core.h", "depthcov_core.h", "datacov_core.h", "math_probe.h", "rf_fft.h", "host_common.h", "slot_ring.h",
            "ell_core.h", "ell_launch.h", "interfaces_core.h", "sens_core.h", "sens_pass.h", "sens_capi_common.h", "sens_sets_core.h",
-           "sens_group_core.h", "ell_sens_core.h", "rf_sens_core.h"]
+           "sens_group_core.h", "ell_sens_core.h", "rf_sens_core.h", "sens_sets_host.h", "rf_sens_sets_core.h"]
 # -disable-machine-licm (device code only): the kernels are register-bound, and constants hoisted out
 # of the persistent loops (polynomial coefficients, masks) end up in VGPR pairs or spilled SGPRs and are
 # copied back at every use; rematerialised next to their use they are scalar moves.  swd_kernel 254 ->
@@ -39,6 +39,7 @@ DATACOV_MAX_S = 1024              # BH_DATACOV_MAX_S
 INTERFACES_MAX_DEPTH_BINS, INTERFACES_MAX_JUMP_BINS = 1024, 256     # BH_INTERFACES_MAX_DEPTH_BINS, BH_INTERFACES_MAX_JUMP_BINS
 SENS_KINDS = {'vp': 1, 'vs': 2, 'rho': 3, 'vs_total': 4}          # BH_SENS_KIND_*
 SENS_SETS_BLOCK_ROWS, SENS_SETS_MAX_BINS = 256, 1024              # BH_SENS_SETS_BLOCK_ROWS, BH_SENS_SETS_MAX_BINS
+RF_SENS_SETS_MAX_SAMPLES, RF_SENS_SETS_MAX_ACC_BYTES = 4096, 1 << 30      # BH_RF_SENS_SETS_MAX_SAMPLES, _MAX_ACC_BYTES
 
 
 class SwdTarget(C.Structure):
@@ -269,6 +270,12 @@ _SIGS = {
     "bh_sens_sets_add": (C.c_int, [_vp, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     "bh_sens_sets_finish": (C.c_int, [_vp] * 7),
     "bh_sens_sets_destroy": (None, [_vp]),
+    "bh_rf_sens_sets_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int,
+                                         C.c_double, _vp]),
+    "bh_rf_sens_sets_add": (C.c_int, [_vp, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp,
+                                      C.c_longlong, _vp, C.c_int, _vp]),
+    "bh_rf_sens_sets_finish": (C.c_int, [_vp] * 7),
+    "bh_rf_sens_sets_destroy": (None, [_vp]),
     "bh_synrf": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                            C.c_double, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bh_selftest_division": (C.c_int, [C.c_long, C.c_uint, C.c_int, C.POINTER(C.c_long)]),

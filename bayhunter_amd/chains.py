@@ -681,6 +681,18 @@ class ChainPool(object):
         return pool_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows,
                                 velocity='ellipticity')
 
+    def rf_sensitivity(self, ref=None, dep_edges=None, kind='vs_total', t=None, every=1, selection='weighted', dev=0.05,
+                       exclude_outliers=True, device=None, max_rows=None):
+        """Where in depth the receiver function looks across the ensemble: dRF(t)/dm of every row posterior() uses, at the
+        target's gauss, p, nsv, wave type and time axis (csrc/rf_sens_core.h), spread over depth bins, and its mean,
+        standard deviation, minimum and maximum per sample of the trace and bin (sensitivity.rf_summarize: the pass and
+        the reduction bh_rf_sens_sets_* on the device).  `ref` defaults to the pool's only receiver-function target;
+        t = (tmin, tmax) and `every` choose the samples.  -> dict(mean, std, min, max [nsel, bins], halfspace_mean,
+        halfspace_std [nsel], nmodels, nexcluded, t, samples, edges, kind, ref, chains).  ValueError for a pool without
+        a receiver-function target, an ambiguous choice, an unknown ref and an empty selection."""
+        from .sensitivity import pool_rf_sensitivity
+        return pool_rf_sensitivity(self, ref, dep_edges, kind, t, every, selection, dev, exclude_outliers, device, max_rows)
+
     def save(self, savepath=None, chainidx_offset=None):
         """Write <savepath>/data/c%03d_p{1,2}{models,likes,misfits,noise,vpvs}.npy like
         SingleChain.save_finalmodels (:654-690), thinned to initparams['maxmodels'] main-phase

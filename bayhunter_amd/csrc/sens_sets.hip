@@ -21,17 +21,13 @@
 #include <new>
 #include <vector>
 #include "sens_sets_core.h"
-#include "host_common.h"
-#include "stats_host.h"
+#include "sens_sets_host.h"
 
 namespace {
 
 using bh::u64;
 using bh::SensSetsAcc;
 using bh::kSensSetsThreads;
-using bh::kSensSetsBlockRows;
-
-constexpr size_t kSlabBytes = 64u << 20;            // the most the slab of block partials takes
 
 struct SensSetsArgs {
     const int3 *blocks;                // [grid.x]: (set, first row within the call, rows)
@@ -141,8 +137,7 @@ struct SensSets {
     int nsets = 0, nper = 0, nb = 0, kind = 0;
     double drho = 0.0;
     hipStream_t st = nullptr;
-    std::vector<long long> start;                  // [nsets + 1]
-    long long next = 0;                            // the row the next add begins with
+    bh::SensSetRows rows;                          // the sets, and the row the next add begins with
     size_t cap = 1;                                // blocks the slab holds
     bh::DevBufs bufs;
     double *dedges = nullptr;
@@ -152,35 +147,12 @@ struct SensSets {
     u64 *neg = nullptr;
 
     size_t nitems() const { return (size_t)nper * (nb + 1); }
-    long long total_rows() const { return start[nsets]; }
-    // the set row r lies in (r < total_rows()): the last set that begins at or before r
-    int set_of(long long r) const
-    {
-        int lo = 0, hi = nsets;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) / 2;
-            if (start[mid] <= r) lo = mid;
-            else hi = mid;
-        }
-        return lo;
-    }
-    // may a call begin or end at row r: at a set's first row, at the end, or a whole number of blocks into a set
-    bool cut_ok(long long r) const
-    {
-        if (r == 0 || r == total_rows()) return true;
-        return (r - start[set_of(r)]) % kSensSetsBlockRows == 0;
-    }
 };
 
 int create(SensSets *s, const double *edges, int nedges)
 {
     const size_t n = s->nitems();
-    long long blocks = 0;
-    for (int z = 0; z < s->nsets; z++)
-        blocks += (s->start[z + 1] - s->start[z] + kSensSetsBlockRows - 1) / kSensSetsBlockRows;
-    const size_t fit = kSlabBytes / (n * sizeof(SensSetsAcc));
-    s->cap = fit < 1 ? 1 : fit;
-    if ((long long)s->cap > blocks) s->cap = blocks < 1 ? 1 : (size_t)blocks;
+    s->cap = s->rows.slab_blocks(n);
     BH_HIP(s->bufs.alloc(s->dedges, (size_t)nedges));
     BH_HIP(s->bufs.alloc(s->dblocks, s->cap));
     BH_HIP(s->bufs.alloc(s->slab, s->cap * n));
@@ -204,17 +176,9 @@ extern "C" int bh_sens_sets_create(void **handle, const long long *set_start, in
                                    int nedges, int kind, double drho_dvp, void *stream)
 {
     const char *who = "bh_sens_sets_create";
-    if (!handle) return bh::fail_who(who, "NULL handle");
-    *handle = nullptr;
-    if (nsets < 1 || nsets > BH_PAIRS_MAX_SETS) return bh::fail_who(who, "1 to 65535 sets");
-    if (!set_start || set_start[0] != 0) return bh::fail_who(who, "set_start must begin at 0");
-    if (int rc = bh::check_set_start(who, set_start, nsets, set_start[nsets])) return rc;
+    if (int rc = bh::sens_sets_check_sets(who, handle, set_start, nsets)) return rc;
     if (nper < 1 || nper > BH_MAX_PERIODS) return bh::fail_who(who, "nper out of range (1 .. 60)");
-    if (!edges || nedges < 2 || nedges > BH_SENS_SETS_MAX_BINS + 1) return bh::fail_who(who, "depth edges: 2 to 1025");
-    if (!bh::ascending(edges, nedges) || !std::isfinite(edges[0]) || !std::isfinite(edges[nedges - 1]))
-        return bh::fail_who(who, "depth edges must be finite and ascending");
-    if (!bh::sens_sets_kind_ok(kind)) return bh::fail_who(who, "kind: BH_SENS_KIND_VP, _VS, _RHO or _VS_TOTAL");
-    if (!std::isfinite(drho_dvp)) return bh::fail_who(who, "drho_dvp must be finite");
+    if (int rc = bh::sens_sets_check_grid(who, edges, nedges, kind, drho_dvp)) return rc;
     if (int rc = bh::require_device()) return rc;
     SensSets *s = new (std::nothrow) SensSets;
     if (!s) return bh::fail_who(who, "out of host memory");
@@ -224,7 +188,8 @@ extern "C" int bh_sens_sets_create(void **handle, const long long *set_start, in
     s->kind = kind;
     s->drho = drho_dvp;
     s->st = (hipStream_t)stream;
-    s->start.assign(set_start, set_start + nsets + 1);
+    s->rows.nsets = nsets;
+    s->rows.start.assign(set_start, set_start + nsets + 1);
     if (int rc = create(s, edges, nedges)) {
         delete s;
         return rc;
@@ -242,23 +207,15 @@ extern "C" int bh_sens_sets_add(void *handle, long long row0, int B, int Lmax, i
     if (!s) return bh::fail_who(who, "handle is NULL");
     if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return bh::fail_who(who, "B/Lmax out of range");
     if (model_stride < Lmax) return bh::fail_who(who, "model_stride < Lmax");
-    if (row0 != s->next) return bh::fail_who(who, "the rows must arrive in ascending order without a gap");
-    if (row0 + B > s->total_rows()) return bh::fail_who(who, "more rows than set_start holds");
+    if (const char *fault = bh::sens_sets_rows_fault(s->rows, row0, B)) return bh::fail_who(who, fault);
     if (B == 0) return BH_OK;
     if (s->kind == BH_SENS_KIND_VS_TOTAL && !q) return bh::fail_who(who, "BH_SENS_KIND_VS_TOTAL needs q");
     if (q && q_stride < Lmax) return bh::fail_who(who, "q_stride < Lmax");
     if (!nlay || !hthk || !K || !c_out) return bh::fail_who(who, "NULL pointer");
-    if (!s->cut_ok(row0) || !s->cut_ok(row0 + B))
-        return bh::fail_who(who, "a call may begin or end inside a set only at a multiple of BH_SENS_SETS_BLOCK_ROWS "
-                                 "rows from the set's first row");
+    if (!s->rows.cut_ok(row0) || !s->rows.cut_ok(row0 + B)) return bh::fail_who(who, bh::kSensSetsCutFault);
     std::vector<int3> blocks;
     bh::CallBufs drain(s->st);                      // (owns nothing: an early return waits for the copies of `blocks`)
-    const long long end = row0 + B;
-    for (int z = s->set_of(row0); z < s->nsets && s->start[z] < end; z++) {
-        const long long a = s->start[z] > row0 ? s->start[z] : row0, b = s->start[z + 1] < end ? s->start[z + 1] : end;
-        for (long long r = a; r < b; r += kSensSetsBlockRows)
-            blocks.push_back(make_int3(z, (int)(r - row0), (int)(b - r < kSensSetsBlockRows ? b - r : kSensSetsBlockRows)));
-    }
+    s->rows.call_blocks(row0, B, blocks);
     SensSetsArgs a;
     std::memset(&a, 0, sizeof(a));
     a.blocks = s->dblocks;
@@ -284,7 +241,7 @@ extern "C" int bh_sens_sets_add(void *handle, long long row0, int B, int Lmax, i
     u64 bad = 0;
     BH_HIP(hipMemcpyAsync(&bad, s->neg, sizeof(u64), hipMemcpyDeviceToHost, s->st));
     BH_HIP(hipStreamSynchronize(s->st));
-    s->next = end;
+    s->rows.next = row0 + B;
     if (bad) return bh::fail_who(who, "negative weight");
     return BH_OK;
 }
@@ -295,7 +252,7 @@ extern "C" int bh_sens_sets_finish(void *handle, long long *total, long long *ex
     const char *who = "bh_sens_sets_finish";
     SensSets *s = (SensSets *)handle;
     if (!s) return bh::fail_who(who, "handle is NULL");
-    if (s->next != s->total_rows()) return bh::fail_who(who, "not all rows of set_start were added");
+    if (s->rows.next != s->rows.total_rows()) return bh::fail_who(who, "not all rows of set_start were added");
     const size_t n = s->nitems(), cells = (size_t)s->nsets * n, nw = (size_t)s->nsets * s->nper;
     std::vector<SensSetsAcc> acc(cells);
     std::vector<long long> wacc(nw * 2);

@@ -328,19 +328,24 @@ class ForwardEngine(object):
                 dE_dT.data_ptr(), c.data_ptr(), Kp.data_ptr(), ws.data_ptr(), ws.numel() * 8, C.c_void_p(st.cuda_stream)))
         return {'K': K, 'E': E, 'dE_dT': dE_dT, 'c': c, 'K_phase': Kp}
 
-    def rf_sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, target=0, stream=None):
+    def rf_sensitivity(self, H, VP=None, VS=None, RHO=None, nlay=None, target=0, stream=None, p=None):
         """Sensitivity kernels of RECEIVER-FUNCTION target `target` (an index into the engine's receiver-function targets)
         for the batch (bh_rf_sens_batch, asynchronous): K [B, nt, 4, Lmax] = dRF(t)/dh, dRF/dvp, dRF/dvs, dRF/drho per
         layer and sample of the target's time axis, and rf [B, nt], the trace itself, bit for bit what run() writes into
         the target's columns -- device tensors in a dict, with 't' [nt], the time axis (numpy).  The time samples sit
         where the dispersion kernels have periods.  The engine's slowness for every row (run()'s rf_sets are not served);
-        K is 0 for the half-space's thickness and NaN in the layers a model does not have (include/bayhunter_amd.h)."""
+        K is 0 for the half-space's thickness and NaN in the layers a model does not have (include/bayhunter_amd.h).
+        p: a ray parameter [s/deg] for this call in place of the target's (a copy of its bh_rf_params goes to the
+        library; the engine keeps its own)."""
         models = H if isinstance(H, DeviceModels) else self.upload(H, VP, VS, RHO, nlay)
         if not 0 <= target < len(self.rf):
             raise ValueError("target %r: the engine has %d receiver-function targets" % (target, len(self.rf)))
         if models.packed.device != self.device:
             raise ValueError("models live on %s, engine on %s" % (models.packed.device, self.device))
         spec, par = self.rf[target], self._rfp[target]
+        if p is not None:
+            par = _lib.RfParams.from_buffer_copy(par)
+            par.p = float(p)
         st = torch.cuda.current_stream(self.device) if stream is None else stream
         B, Lmax, nt = models.B, models.Lmax, spec.obsx.size
         with torch.cuda.stream(st):

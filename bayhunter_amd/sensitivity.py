@@ -35,10 +35,14 @@ K^E = dE/dm = G_m + G_c dc/dm, the change of H/V per km/s of the layer (per g/cm
 
 And for the receiver function (csrc/rf_sens_core.h): K[t] = dRF(t)/dm, central differences of two
 perturbed traces per entry, formed in LDS.  Time samples sit where the other kernels have periods, so vs_total and
-to_depth apply unchanged.  There is no summary over pools (bh_sens_sets holds at most 60 "periods").
+to_depth apply unchanged.  Over an ensemble the reduction is bh_rf_sens_sets_* (csrc/rf_sens_sets_core.h; DESIGN.md
+section 7k): bh_sens_sets' sums at a selection of the trace's samples, a row counting for all samples or for none.
 
     rf_batch(rfparams, H, VP, VS, RHO, nlay, ref)        the pass for a batch of models
     plugins.RFminiModRF.sensitivity / ForwardEngine.rf_sensitivity
+    rf_summarize(rfparams, models, vpvs, ...)            the depth-binned dRF(t)/dm over an ensemble
+    rf_summarize_sets(rfparams, models, set_start, ...)  the same for every set of rows, each at its own ray parameter
+    ChainPool.rf_sensitivity / StationPool.rf_sensitivity            (pool_rf_sensitivity, stations_rf_sensitivity)
 """
 import numpy as np
 
@@ -518,3 +522,296 @@ def stations_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', selec
     if velocity != 'phase':
         out.velocity = velocity
     return out
+
+
+# ---- the receiver function over an ensemble: depth-binned dRF(t)/dm per set of rows and selected sample --------------------
+
+_RF_EMPTY = "empty selection (no row with a trace)"
+
+
+def _rf_spec(rfparams, ref='prf'):
+    """rf_batch's rfparams (or a layout.RfSpec) -> layout.RfSpec"""
+    from .layout import RfSpec
+    if isinstance(rfparams, RfSpec):
+        return rfparams
+    unknown = set(rfparams) - {'obsx', 'gauss', 'p', 'nsv', 'water', 'wtype'}
+    if 'obsx' not in rfparams or unknown:
+        raise ValueError("rfparams: a dict with 'obsx' and optionally 'gauss', 'p', 'nsv' (unknown: %s)" % sorted(unknown))
+    return RfSpec(ref, rfparams['obsx'], rfparams.get('gauss', 1.0), rfparams.get('p', 6.4), rfparams.get('nsv'),
+                  wtype=rfparams.get('wtype'))
+
+
+def rf_time_axis(spec):
+    """The time of every sample of K and of the trace that ForwardEngine.rf_sensitivity returns for `spec`."""
+    return (np.arange(int(spec.nsamp)) / spec.fsamp - spec.tshft)[:spec.obsx.size]
+
+
+def rf_samples(taxis, t=None, every=1):
+    """The samples rf_summarize reads: those with t[0] <= time <= t[1] (None: all), every `every`-th of them."""
+    every = int(every)
+    if every < 1:
+        raise ValueError("every >= 1")
+    idx = np.arange(taxis.size)
+    if t is not None:
+        if len(t) != 2 or not t[0] <= t[1]:
+            raise ValueError("t: (tmin, tmax)")
+        idx = idx[(taxis >= t[0]) & (taxis <= t[1])]
+    idx = idx[::every]
+    if idx.size < 1:
+        raise ValueError("t, every: no sample of the trace is selected")
+    return np.ascontiguousarray(idx, dtype=np.int32)
+
+
+class RfSensSets(object):
+    """One bh_rf_sens_sets handle: add(row0, models, K, rf, q, weights) run after run, then finish()."""
+
+    def __init__(self, set_start, nout, samples, edges, kind, drho_dvp, stream):
+        import ctypes as C
+        self.lib = _lib.load()
+        self.set_start = np.ascontiguousarray(set_start, dtype=np.int64)
+        self.samples = np.ascontiguousarray(samples, dtype=np.int32)
+        self.nsets, self.nout, self.edges = self.set_start.size - 1, int(nout), np.ascontiguousarray(edges, dtype=np.float64)
+        self.h = C.c_void_p()
+        _lib.check(self.lib.bh_rf_sens_sets_create(C.byref(self.h), self.set_start.ctypes.data, self.nsets, self.nout,
+                                                   self.samples.ctypes.data, self.samples.size, self.edges.ctypes.data,
+                                                   self.edges.size, int(kind), float(drho_dvp), stream))
+
+    def add(self, row0, models, K, rf, q=None, weights=None):
+        """Rows row0 .. of the numbering: models an engine.DeviceModels, K and rf what ForwardEngine.rf_sensitivity
+        returned for them, q [B, Lmax] float64 or None, weights int32 [B] or None -- device tensors."""
+        _lib.check(self.lib.bh_rf_sens_sets_add(
+            self.h, int(row0), models.B, models.Lmax, 4 * models.Lmax, models.nlay.data_ptr(), models.H.data_ptr(),
+            None if q is None else q.data_ptr(), 0 if q is None else q.stride(0), K.data_ptr(), K.stride(0), rf.data_ptr(),
+            rf.stride(0), None if weights is None else weights.data_ptr()))
+
+    def finish(self):
+        """-> dict(total, excluded [sets] int64, s1, s2, vmin, vmax [sets, samples, bins + 1])"""
+        Z, S, C1 = self.nsets, self.samples.size, self.edges.size
+        out = dict(total=np.zeros(Z, dtype=np.int64), excluded=np.zeros(Z, dtype=np.int64))
+        for k in ('s1', 's2', 'vmin', 'vmax'):
+            out[k] = np.zeros((Z, S, C1))
+        _lib.check(self.lib.bh_rf_sens_sets_finish(self.h, *[out[k].ctypes.data for k in
+                                                             ('total', 'excluded', 's1', 's2', 'vmin', 'vmax')]))
+        return out
+
+    def close(self):
+        if self.h:
+            self.lib.bh_rf_sens_sets_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _rf_result(sums, z, taxis, samples, edges, kind):
+    """rf_summarize()'s dict of set z, or None for a set without a counting row."""
+    total = int(sums['total'][z])
+    if not total:
+        return None
+    mean, std = from_sums(np.full(samples.size, total), sums['s1'][z], sums['s2'][z], sums['vmin'][z], sums['vmax'][z])
+    return {'mean': mean[:, :-1], 'std': std[:, :-1], 'min': sums['vmin'][z][:, :-1].copy(),
+            'max': sums['vmax'][z][:, :-1].copy(), 'halfspace_mean': mean[:, -1], 'halfspace_std': std[:, -1],
+            'nmodels': total, 'nexcluded': int(sums['excluded'][z]), 't': taxis[samples], 'samples': samples.copy(),
+            'edges': edges, 'kind': kind}
+
+
+def _p_runs(runs, set_start, p):
+    """split_runs' runs cut further wherever the ray parameter changes between sets -> [(lo, hi, p)]."""
+    out = []
+    for lo, hi in runs:
+        z = int(np.searchsorted(set_start, lo, side='right')) - 1      # the set row lo lies in (the empty ones before it skipped)
+        a, pa = lo, p[z]
+        while True:
+            end = min(hi, int(set_start[z + 1]))
+            if end >= hi:
+                out.append((a, hi, pa))
+                break
+            z = int(np.searchsorted(set_start, end, side='right')) - 1
+            if p[z] != pa:
+                out.append((a, end, pa))
+                a, pa = end, p[z]
+    return out
+
+
+def rf_summarize_sets(rfparams, models, set_start, vpvs, weights=None, dep_edges=None, kind='vs_total', ref='prf', t=None,
+                      every=1, mantle=None, device=None, max_rows=None, drho_dvp=0.32, p=None, strict=True):
+    """rf_summarize() of every set of rows in one pass: set s is models[set_start[s]:set_start[s + 1]] with its vpvs and
+    weights (set_start as for summarize_sets).
+
+    rfparams        rf_batch's: a dict with 'obsx', the target's time axis, and optionally 'gauss', 'p', 'nsv', 'wtype'
+    models, vpvs, mantle, weights, dep_edges, kind, drho_dvp     as for summarize_sets
+    ref             'prf' | 'seis' (incident P) or 'srf' (SV)
+    t, every        the samples the reduction reads: those with t[0] <= time <= t[1] (None: all), every `every`-th of them
+    p               None: rfparams' ray parameter; a number; or one per set (a station's own)
+    max_rows        the rows are taken in split_runs' runs, cut further wherever p changes between sets; per run the
+                    layers, the pass (ForwardEngine.rf_sensitivity at the run's p), q = vp / vs and bh_rf_sens_sets_add.
+                    Default: what half of the free device memory holds, K counted at 8 nout 4 Lmax bytes a row; no
+                    result depends on it
+
+    -> a selection.SetList of dicts(mean, std, min, max [nsel, bins]: change of the trace's sample per km/s (per g/cm^3
+    for 'rho') of the layer kernel that falls into the bin; halfspace_mean, halfspace_std [nsel]; nmodels, nexcluded
+    (integers: the weighted rows that count; left out: no model, no trace); t [nsel], samples (their indices), edges,
+    kind), every field bit for bit what rf_summarize returns for the set's rows alone at the set's p.  A set without a row
+    that counts raises a ValueError naming the first such set -- or, with strict=False, has the entry None and its message
+    in the list's `failed`."""
+    import torch
+    from . import _device, datafits as df
+    from .engine import ForwardEngine
+    from .models import layers_from_voronoi
+    code, edges = _check_kind(kind), _check_edges(dep_edges)
+    spec = _rf_spec(rfparams, ref)
+    taxis = rf_time_axis(spec)
+    nout = taxis.size
+    if nout > _lib.RF_SENS_SETS_MAX_SAMPLES:
+        raise ValueError("rf_sensitivity: the trace has more than %d samples" % _lib.RF_SENS_SETS_MAX_SAMPLES)
+    samples = rf_samples(taxis, t, every)
+    shape = getattr(models, 'shape', None) or np.asarray(models).shape
+    if len(shape) != 2:
+        raise ValueError("models: [rows, 2*maxlayers]")
+    R = shape[0]
+    set_start, Z = sel.check_set_start(set_start, R)
+    if Z * samples.size * edges.size * 32 > _lib.RF_SENS_SETS_MAX_ACC_BYTES:
+        raise ValueError("rf_sensitivity: %d sets x %d samples x %d cells exceed the accumulator budget of %d bytes; "
+                         "narrow t or raise every" % (Z, samples.size, edges.size, _lib.RF_SENS_SETS_MAX_ACC_BYTES))
+    vp = None if np.ndim(vpvs) == 0 else vpvs
+    if vp is not None and len(vp) != R:
+        raise ValueError("vpvs: one per row, or a scalar")
+    if weights is not None and len(weights) != R:
+        raise ValueError("one weight per row")
+    if weights is not None and not hasattr(weights, 'is_cuda') and np.any(np.asarray(weights) < 0):
+        raise ValueError("negative weight")
+    if max_rows is not None and int(max_rows) < 1:
+        raise ValueError("max_rows >= 1")
+    pz = np.full(Z, spec.p if p is None else np.nan, dtype=np.float64)
+    if p is not None:
+        if np.ndim(p) != 0 and len(p) != Z:
+            raise ValueError("p: a number, or one per set")
+        pz[:] = p
+        if not np.all(np.isfinite(pz)):
+            raise ValueError("p: finite")
+    results, failed = [None] * Z, {}
+    if R == 0:
+        failed = {z: "empty selection: no models" for z in range(Z)}
+        sel.raise_first_failed(failed, strict, "set")
+        return sel.SetList(results, failed)
+    dev = _device.torch_device(device)
+    with torch.cuda.device(dev):
+        eng = ForwardEngine(rf=[spec], device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        Lmax = shape[1] // 2
+        if max_rows is None:       # half of the free device memory: K, the trace, the row, its layers (packed, nuclei, q)
+            per_row = 8 * (nout * 4 * Lmax + nout + shape[1] + 8 * Lmax) + 16
+            max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
+        with RfSensSets(set_start, nout, samples, edges, code, drho_dvp, stream) as handle:
+            for lo, hi, prun in _p_runs(split_runs(set_start, max_rows), set_start, pz):
+                rows = _device.to_device(models[lo:hi], torch.float64, dev)
+                v = vpvs if vp is None else vp[lo:hi]
+                v = _device.to_device(np.broadcast_to(np.asarray(v, dtype=np.float64), (hi - lo,)).copy()
+                                      if not isinstance(v, torch.Tensor) else v, torch.float64, dev)
+                w = None if weights is None else _device.to_device(weights[lo:hi], torch.int32, dev)
+                vsn, zv, nl = df._layers(rows, dev)
+                dm, _ = layers_from_voronoi(vsn, zv, nl, v, df._OPEN_PRIORS, mantle=mantle, device=dev)
+                res = eng.rf_sensitivity(dm, p=None if p is None else float(prun))
+                q = (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None
+                handle.add(lo, dm, res['K'], res['rf'], q, w)
+            sums = handle.finish()
+    for z in range(Z):
+        results[z] = _rf_result(sums, z, taxis, samples, edges, kind)
+        if results[z] is None:
+            failed[z] = "empty selection: no models" if set_start[z] == set_start[z + 1] else _RF_EMPTY
+    sel.raise_first_failed(failed, strict, "set")
+    return sel.SetList(results, failed)
+
+
+def rf_summarize(rfparams, models, vpvs, weights=None, dep_edges=None, kind='vs_total', ref='prf', t=None, every=1,
+                 mantle=None, device=None, max_rows=None, drho_dvp=0.32):
+    """The depth-binned receiver-function sensitivity kernel over one set of sampled models: rf_summarize_sets' dict for
+    all rows (see there).  ValueError for an empty selection."""
+    shape = getattr(models, 'shape', None) or np.asarray(models).shape
+    res = rf_summarize_sets(rfparams, models, [0, shape[0] if len(shape) == 2 else 0], vpvs, weights, dep_edges, kind, ref,
+                            t, every, mantle, device, max_rows, drho_dvp, strict=False)
+    if res[0] is None:
+        raise ValueError(res.failed[0])
+    return res[0]
+
+
+def pool_rf_target(targets, ref=None):
+    """The receiver-function target of a JointTarget the kernels are formed for -> (layout.RfSpec, its index among the
+    receiver-function targets).  ref None: its only one.  ValueError for a pool without a receiver-function target, an
+    ambiguous choice and an unknown ref."""
+    specs = targets.batch_layout(ell=True)['layout'].rf
+    if not specs:
+        raise ValueError("rf_sensitivity: the pool has no receiver-function target")
+    if ref is None:
+        if len(specs) > 1:
+            raise ValueError("rf_sensitivity: ref is one of %s" % ', '.join(repr(sp.ref) for sp in specs))
+        return specs[0], 0
+    if not any(sp.ref == ref for sp in specs):
+        raise ValueError("rf_sensitivity: no receiver-function target %r (there are %s)" % (ref, ', '.join(sp.ref for sp in specs)))
+    i = next(i for i, sp in enumerate(specs) if sp.ref == ref)
+    return specs[i], i
+
+
+def pool_rf_sensitivity(pool, ref=None, dep_edges=None, kind='vs_total', t=None, every=1, selection='weighted', dev=0.05,
+                        exclude_outliers=True, device=None, max_rows=None):
+    """ChainPool.rf_sensitivity: rf_summarize() over the rows ChainPool.posterior uses, at the target's gauss, p, nsv,
+    wave type and time axis, plus 'ref' and 'chains' (global indices used)."""
+    spec, _ = pool_rf_target(pool.targets, ref)
+    ci, ri, w = sel.pool_rows(pool, selection, dev, exclude_outliers)
+    res = rf_summarize(spec, pool.models[ci, ri], pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32), dep_edges, kind,
+                       spec.ref, t, every, pool.priors.get('mantle'), device, max_rows)
+    res['ref'] = spec.ref
+    res['chains'] = np.unique(ci) + pool.first
+    return res
+
+
+class StationRfSensitivity(sel.StationResult):
+    """StationPool.rf_sensitivity's result, every array in the pool's station order.
+
+    names, failed    the stations; {station name: message} (such a station is NaN throughout)
+    stations         {station name: the dict pool.station(name).rf_sensitivity(...) returns}, failed stations left out
+    ref, t, samples, edges, kind   the target, the selected samples' times and indices, the depth edges all stations share
+    p                [nstations] the ray parameter every station's kernels were formed at
+    mean, std, min, max [nstations, nsel, bins], halfspace_mean, halfspace_std [nstations, nsel] (float64, NaN for a
+    failed station), nmodels, nexcluded [nstations] (0 for a failed station)"""
+
+    def __init__(self, names, results, failed, ref, t, samples, edges, kind, p):
+        sel.StationResult.__init__(self, names, failed)
+        self.stations = {n: r for n, r in zip(names, results) if r is not None}
+        self.ref, self.t, self.samples, self.edges, self.kind, self.p = ref, t, samples, edges, kind, p
+        Z, S, nb = len(results), t.size, edges.size - 1
+        for k in ('mean', 'std', 'min', 'max'):
+            setattr(self, k, np.full((Z, S, nb), np.nan))
+        self.halfspace_mean, self.halfspace_std = np.full((Z, S), np.nan), np.full((Z, S), np.nan)
+        self.nmodels, self.nexcluded = np.zeros(Z, dtype=np.int64), np.zeros(Z, dtype=np.int64)
+        for z, r in enumerate(results):
+            if r is not None:
+                for k in ('mean', 'std', 'min', 'max', 'halfspace_mean', 'halfspace_std', 'nmodels', 'nexcluded'):
+                    getattr(self, k)[z] = r[k]
+
+
+def stations_rf_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', t=None, every=1, selection='weighted',
+                            dev=0.05, exclude_outliers=True, device=None, max_rows=None, strict=False):
+    """StationPool.rf_sensitivity: rf_summarize_sets() over every station's main-phase rows, every station at its own ray
+    parameter when the pool was built with per_station=('p',)."""
+    pool, c = spool.pool, spool.chains_per_station
+    spec, i = pool_rf_target(spool.stations[0], ref)
+    edges = _check_edges(dep_edges)
+    p = np.array([pool_rf_target(joint, spec.ref)[0].p for joint in spool.stations], dtype=np.float64)
+    ci, ri, w, set_start, failed = sel.station_rows(pool, c, selection, dev, exclude_outliers)
+    res = rf_summarize_sets(spec, pool.models[ci, ri], set_start, pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32),
+                            edges, kind, spec.ref, t, every, pool.priors.get('mantle'), device, max_rows,
+                            p=p if 'p' in spool.per_station else None, strict=False)
+    for z, msg in res.failed.items():
+        failed.setdefault(z, msg)
+    sel.raise_first_failed(failed, strict, "station", spool.names)
+    for z, r in enumerate(res):
+        if r is not None:
+            r['ref'] = spec.ref
+            r['chains'] = sel.station_chains(ci, set_start, z, c)
+    taxis = rf_time_axis(spec)
+    samples = rf_samples(taxis, t, every)
+    return StationRfSensitivity(spool.names, res, failed, spec.ref, taxis[samples], samples, edges, kind, p)

@@ -558,6 +558,17 @@ class StationPool(object):
         return stations_sensitivity(self, ref, dep_edges, kind, selection, dev, exclude_outliers, device, max_rows, strict,
                                     velocity='ellipticity')
 
+    def rf_sensitivity(self, ref=None, dep_edges=None, kind='vs_total', t=None, every=1, selection='weighted', dev=0.05,
+                       exclude_outliers=True, device=None, max_rows=None, strict=False):
+        """The depth-binned receiver-function sensitivity kernel of every station in one pass (ChainPool.rf_sensitivity;
+        sensitivity.rf_summarize_sets: per run of rows the pass and bh_rf_sens_sets_add on one handle) -- every station at
+        its own ray parameter with per_station=('p',).  Per station every field is bit for bit what
+        station(s).rf_sensitivity(...) returns.  -> sensitivity.StationRfSensitivity: `names`, `stations[name]` those
+        dicts, `failed`, and the stacked arrays [nstations, nsel, bins]."""
+        from .sensitivity import stations_rf_sensitivity
+        return stations_rf_sensitivity(self, ref, dep_edges, kind, t, every, selection, dev, exclude_outliers, device,
+                                       max_rows, strict)
+
     def save(self, savepath=None):
         """One directory <savepath>/<station name> per station, each holding what a ChainPool of that station alone
         writes (data/c%03d_... numbered from 0, data/<station name>_config.pkl with the station's targets).

@@ -1173,6 +1173,52 @@ int  bh_sens_sets_finish(void *handle, long long *total, long long *excluded, do
                          double *vmax);
 void bh_sens_sets_destroy(void *handle);
 
+/* ---- posterior receiver-function sensitivity: depth-binned dRF(t)/dm per set, sample and depth cell ------------------- */
+/* bh_sens_sets_* for the receiver function: the layer kernel bh_rf_sens_batch wrote for every row, spread over depth bins
+ * all rows share, and its moments per set of rows (a station), with a trace's samples where bh_sens_sets_* has periods.
+ * A trace has hundreds of samples, so the reduction reads K at a selection of them and has a kernel of its own
+ * (csrc/rf_sens_sets.hip: a workgroup takes a tile of cells x samples, a thread one cell and four samples).
+ *
+ * create  set_start, nsets, edges, nedges, kind, drho_dvp   exactly as for bh_sens_sets_create
+ *         nout          samples of every row's K and trace, 1 .. BH_RF_SENS_SETS_MAX_SAMPLES
+ *         samples       HOST int32 [nsel], strictly ascending indices in 0 .. nout - 1: the samples the reduction reads
+ *                       (a time window, a decimation); NULL for all of them (nsel is then ignored and is nout)
+ *         The accumulators take nsets * nsel * (nb + 1) * 32 bytes on the device, and as much again on the host in
+ *         finish; a combination above BH_RF_SENS_SETS_MAX_ACC_BYTES is refused.  create touches no device: the buffers
+ *         are made by the first add that brings rows, after that call's arguments were checked.
+ * add     rows row0 .. row0 + B - 1, under bh_sens_sets_add's rules of order and cuts.
+ *         nlay, hthk, model_stride, q, q_stride, weights   as for bh_sens_sets_add
+ *         K, k_stride   DEVICE [B] rows of k_stride >= nout * 4 * Lmax doubles, [nout][4][Lmax]: what bh_rf_sens_batch wrote
+ *         rf, rf_stride DEVICE [B] rows of rf_stride >= nout doubles: the trace bh_rf_sens_batch wrote
+ *         Synchronises the handle's stream: the arrays are free when it returns.
+ * finish  HOST outputs, each optional: total, excluded [nsets]; s1, s2, vmin, vmax [nsets][nsel][nb + 1].
+ *
+ * Per row and selected sample the cells x_j are bh_sens_sets_*'s, formed from the sample's [4][Lmax] block of K.  A row
+ * counts for all samples or for none: its weight is positive, 2 <= nlay <= Lmax and rf[b][0] is not NaN (bh_rf_batch gives
+ * NaN throughout for a model without a trace); a row of positive weight that does not count adds its weight to
+ * excluded[s].  The sums and their order are bh_sens_sets_*'s (csrc/sens_sets_core.h): for nsel <= 60 every s1, s2, vmin
+ * and vmax is bit for bit what bh_sens_sets_* returns for the same K, hthk, q and weights with a finite c_out.  Two runs
+ * are bit-identical, and a set's result depends neither on the other sets, nor on where its rows lie, nor on how the rows
+ * were split into calls.  An empty set, or one without a row that counts, is no error: total 0, sums 0, vmin and vmax NaN.
+ * BH_ERR_ARG: bh_sens_sets_*'s refusals, nout out of range, a sample index out of range or not ascending, the accumulator
+ * budget, a k_stride or rf_stride shorter than the row.  All arguments but the weights' sign are checked before any
+ * device is touched.
+ *
+ * The budget: 1 GiB holds 256 sets of 256 samples and 512 cells, or 1000 stations of 256 samples on the default 100 bins.
+ * The device holds the accumulators next to the rows' K (the caller sizes its runs of rows by what is free) and the
+ * 64 MiB slab of block partials, and finish stages them once more on the host next to the caller's four output arrays.
+ * Above it the caller splits the samples over handles: every sample's result is independent of the others. */
+#define BH_RF_SENS_SETS_MAX_SAMPLES   4096
+#define BH_RF_SENS_SETS_MAX_ACC_BYTES (1ll << 30)
+int  bh_rf_sens_sets_create(void **handle, const long long *set_start, int nsets, int nout, const int *samples, int nsel,
+                            const double *edges, int nedges, int kind, double drho_dvp, void *stream);
+int  bh_rf_sens_sets_add(void *handle, long long row0, int B, int Lmax, int model_stride, const int *nlay,
+                         const double *hthk, const double *q, int q_stride, const double *K, long long k_stride,
+                         const double *rf, int rf_stride, const int *weights);
+int  bh_rf_sens_sets_finish(void *handle, long long *total, long long *excluded, double *s1, double *s2, double *vmin,
+                            double *vmax);
+void bh_rf_sens_sets_destroy(void *handle);
+
 /* ---- plumbing for hosts without their own device allocator ------------------------------ */
 int bh_malloc(void **dptr, size_t bytes);
 int bh_free(void *dptr);
