@@ -13,13 +13,15 @@
 //                              trace's first sample are uniform in the workgroup: a row that does not count costs no
 //                              barrier.  The partials go to the block's row of the slab; thread 0 of tile 0 carries the
 //                              block's total and excluded weight.
-//   rf_sens_sets_fold_kernel   one thread per item (and one for the weights) adds the slab's rows to their sets' sums in
-//                              block order.
+//   sens_sets_fold_kernel      (sens_sets_host.h, with nw = 1 weight pair a block) one thread per item, and one for the
+//                              weights, adds the slab's rows to their sets' sums in block order.
 //
 // The slab holds a bounded number of blocks: a call's blocks are taken in chunks, each folded before the next is
-// launched, which is the order of one pass over all of them.  create checks and records; the device is first touched by
-// the first add that brings rows, after all of that call's arguments were checked.  No scratch; LDS
-// rf_sens_sets_lds_doubles and the tile's sample offsets (14 464 B at 100 layers).
+// launched, which is the order of one pass over all of them.  The handle, that loop and the finish are
+// sens_sets_host.h's SensSetsHandle; here are the main kernel, its arguments and launch, the samples, and the checks of
+// what only this reduction takes.  create checks and records; the device is first touched by the first add that brings
+// rows, after all of that call's arguments were checked.  No scratch; LDS rf_sens_sets_lds_doubles and the tile's sample
+// offsets (14 464 B at 100 layers).
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -114,83 +116,20 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4))) v
     }
 }
 
-// thread t < nitems: item t of every block's partial into its set's sums; thread nitems: the weights
-__global__ void rf_sens_sets_fold_kernel(const int3 *blocks, int nblocks, int nitems, const SensSetsAcc *slab,
-                                         const long long *wslab, SensSetsAcc *acc, long long *wacc)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nitems) {
-        int z = -1;
-        SensSetsAcc cur;
-        bh::sens_sets_acc_init(cur);
-        for (int b = 0; b < nblocks; b++) {
-            const int zb = blocks[b].x;
-            if (zb != z) {
-                if (z >= 0) acc[(size_t)z * nitems + t] = cur;
-                z = zb;
-                cur = acc[(size_t)z * nitems + t];
-            }
-            bh::sens_sets_acc_fold(cur, slab[(size_t)b * nitems + t]);
-        }
-        if (z >= 0) acc[(size_t)z * nitems + t] = cur;
-    } else if (t == nitems) {
-        for (int b = 0; b < nblocks; b++) {
-            long long *out = wacc + (size_t)blocks[b].x * 2;
-            out[0] += wslab[(size_t)b * 2];
-            out[1] += wslab[(size_t)b * 2 + 1];
-        }
-    }
-}
-
-__global__ void rf_sens_sets_init_kernel(SensSetsAcc *acc, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) bh::sens_sets_acc_init(acc[i]);
-}
-
-struct RfSensSets {
-    int nsets = 0, nout = 0, nsel = 0, nb = 0, kind = 0;
-    double drho = 0.0;
-    hipStream_t st = nullptr;
-    bh::SensSetRows rows;                          // the sets, and the row the next add begins with
+struct RfSensSets : bh::SensSetsHandle {          // nw = 1: a block carries one weight pair
+    int nout = 0, nsel = 0;
     std::vector<int> samples;                      // [nsel]
-    std::vector<double> edges;                     // [nb + 1]
-    bool ready = false;                            // the device buffers are there
-    size_t cap = 1;                                // blocks the slab holds
-    bh::DevBufs bufs;
-    double *dedges = nullptr;
     int *dsamples = nullptr;
-    int3 *dblocks = nullptr;
-    SensSetsAcc *slab = nullptr, *acc = nullptr;   // [cap][nitems], [nsets][nitems]
-    long long *wslab = nullptr, *wacc = nullptr;   // [cap][2], [nsets][2]
-    u64 *neg = nullptr;
-
-    size_t nitems() const { return (size_t)nsel * (nb + 1); }
 };
 
-// the first add that brings rows: the device, the buffers, the accumulators at their start
+// the first add that brings rows: the device, the samples, the handle's buffers
 int make_ready(RfSensSets *s)
 {
     if (s->ready) return BH_OK;
     if (int rc = bh::require_device()) return rc;
-    const size_t n = s->nitems(), cells = (size_t)s->nsets * n;
-    s->cap = s->rows.slab_blocks(n);
-    BH_HIP(s->bufs.alloc(s->dedges, s->edges.size()));
     BH_HIP(s->bufs.alloc(s->dsamples, (size_t)s->nsel));
-    BH_HIP(s->bufs.alloc(s->dblocks, s->cap));
-    BH_HIP(s->bufs.alloc(s->slab, s->cap * n));
-    BH_HIP(s->bufs.alloc(s->wslab, s->cap * 2));
-    BH_HIP(s->bufs.alloc(s->acc, cells));
-    BH_HIP(s->bufs.alloc(s->wacc, (size_t)s->nsets * 2));
-    BH_HIP(s->bufs.alloc(s->neg, 1));
-    BH_HIP(hipMemcpyAsync(s->dedges, s->edges.data(), sizeof(double) * s->edges.size(), hipMemcpyHostToDevice, s->st));
     BH_HIP(hipMemcpyAsync(s->dsamples, s->samples.data(), sizeof(int) * s->nsel, hipMemcpyHostToDevice, s->st));
-    BH_HIP(hipMemsetAsync(s->wacc, 0, sizeof(long long) * (size_t)s->nsets * 2, s->st));
-    BH_HIP(hipMemsetAsync(s->neg, 0, sizeof(u64), s->st));
-    hipLaunchKernelGGL(rf_sens_sets_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s->st, s->acc, cells);
-    BH_HIP(hipGetLastError());
-    s->ready = true;
-    return BH_OK;
+    return s->make_ready();
 }
 
 }  // namespace
@@ -216,16 +155,10 @@ extern "C" int bh_rf_sens_sets_create(void **handle, const long long *set_start,
                                  "BH_RF_SENS_SETS_MAX_ACC_BYTES: fewer samples or sets a handle");
     RfSensSets *s = new (std::nothrow) RfSensSets;
     if (!s) return bh::fail_who(who, "out of host memory");
-    s->nsets = nsets;
+    s->init(set_start, nsets, edges, nedges, kind, drho_dvp, stream);
+    s->nitems = (size_t)nsel * nedges;
     s->nout = nout;
     s->nsel = nsel;
-    s->nb = nedges - 1;
-    s->kind = kind;
-    s->drho = drho_dvp;
-    s->st = (hipStream_t)stream;
-    s->rows.nsets = nsets;
-    s->rows.start.assign(set_start, set_start + nsets + 1);
-    s->edges.assign(edges, edges + nedges);
     s->samples.resize(nsel);
     for (int i = 0; i < nsel; i++) s->samples[i] = samples ? samples[i] : i;
     *handle = s;
@@ -239,20 +172,12 @@ extern "C" int bh_rf_sens_sets_add(void *handle, long long row0, int B, int Lmax
     const char *who = "bh_rf_sens_sets_add";
     RfSensSets *s = (RfSensSets *)handle;
     if (!s) return bh::fail_who(who, "handle is NULL");
-    if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return bh::fail_who(who, "B/Lmax out of range");
-    if (model_stride < Lmax) return bh::fail_who(who, "model_stride < Lmax");
-    if (const char *fault = bh::sens_sets_rows_fault(s->rows, row0, B)) return bh::fail_who(who, fault);
+    const char *own = !rf ? "NULL pointer"
+                      : k_stride < (long long)s->nout * 4 * Lmax ? "k_stride < nout * 4 * Lmax"
+                      : rf_stride < s->nout ? "rf_stride < nout" : nullptr;
+    if (int rc = s->check_add(who, row0, B, Lmax, model_stride, nlay, hthk, q, q_stride, K, own)) return rc;
     if (B == 0) return BH_OK;
-    if (s->kind == BH_SENS_KIND_VS_TOTAL && !q) return bh::fail_who(who, "BH_SENS_KIND_VS_TOTAL needs q");
-    if (q && q_stride < Lmax) return bh::fail_who(who, "q_stride < Lmax");
-    if (!nlay || !hthk || !K || !rf) return bh::fail_who(who, "NULL pointer");
-    if (k_stride < (long long)s->nout * 4 * Lmax) return bh::fail_who(who, "k_stride < nout * 4 * Lmax");
-    if (rf_stride < s->nout) return bh::fail_who(who, "rf_stride < nout");
-    if (!s->rows.cut_ok(row0) || !s->rows.cut_ok(row0 + B)) return bh::fail_who(who, bh::kSensSetsCutFault);
     if (int rc = make_ready(s)) return rc;
-    std::vector<int3> blocks;
-    bh::CallBufs drain(s->st);                      // (owns nothing: an early return waits for the copies of `blocks`)
-    s->rows.call_blocks(row0, B, blocks);
     RfSensSetsArgs a;
     std::memset(&a, 0, sizeof(a));
     a.blocks = s->dblocks;
@@ -262,65 +187,21 @@ extern "C" int bh_rf_sens_sets_add(void *handle, long long row0, int B, int Lmax
     a.drho = s->drho;
     a.nlay = nlay; a.w = weights; a.samples = s->dsamples; a.h = hthk; a.q = q; a.K = K; a.rf = rf; a.edges = s->dedges;
     a.slab = s->slab; a.wslab = s->wslab; a.neg = s->neg;
-    const int nitems = (int)s->nitems();
     const unsigned tiles = (unsigned)(a.ctiles * bh::rf_sens_sets_sample_tiles(s->nsel));
-    const unsigned fold = (unsigned)((nitems + 1 + 255) / 256);
-    for (size_t b0 = 0; b0 < blocks.size(); b0 += s->cap) {
-        const size_t nb = blocks.size() - b0 < s->cap ? blocks.size() - b0 : s->cap;
-        BH_HIP(hipMemcpyAsync(s->dblocks, blocks.data() + b0, sizeof(int3) * nb, hipMemcpyHostToDevice, s->st));
-        hipLaunchKernelGGL(rf_sens_sets_kernel, dim3((unsigned)nb, tiles), dim3(kThreads), lds_bytes(Lmax), s->st, a);
-        BH_HIP(hipGetLastError());
-        hipLaunchKernelGGL(rf_sens_sets_fold_kernel, dim3(fold), dim3(256), 0, s->st, (const int3 *)s->dblocks, (int)nb,
-                           nitems, (const SensSetsAcc *)s->slab, (const long long *)s->wslab, s->acc, s->wacc);
-        BH_HIP(hipGetLastError());
-    }
-    // the call's arrays are free when it returns, and a negative weight is reported by the call that brought it
-    u64 bad = 0;
-    BH_HIP(hipMemcpyAsync(&bad, s->neg, sizeof(u64), hipMemcpyDeviceToHost, s->st));
-    BH_HIP(hipStreamSynchronize(s->st));
-    s->rows.next = row0 + B;
-    if (bad) return bh::fail_who(who, "negative weight");
-    return BH_OK;
+    return s->add(who, row0, B, [&](unsigned nblocks) {
+        hipLaunchKernelGGL(rf_sens_sets_kernel, dim3(nblocks, tiles), dim3(kThreads), lds_bytes(Lmax), s->st, a);
+    });
 }
 
 extern "C" int bh_rf_sens_sets_finish(void *handle, long long *total, long long *excluded, double *s1, double *s2,
                                       double *vmin, double *vmax)
 {
     const char *who = "bh_rf_sens_sets_finish";
-    RfSensSets *s = (RfSensSets *)handle;
-    if (!s) return bh::fail_who(who, "handle is NULL");
-    if (s->rows.next != s->rows.total_rows()) return bh::fail_who(who, "not all rows of set_start were added");
-    const size_t n = s->nitems(), cells = (size_t)s->nsets * n;
-    std::vector<SensSetsAcc> acc;
-    std::vector<long long> wacc((size_t)s->nsets * 2, 0);
-    if (s->ready) {                                 // (not ready: no set has a row)
-        u64 bad = 0;
-        acc.resize(cells);
-        BH_HIP(hipMemcpyAsync(acc.data(), s->acc, sizeof(SensSetsAcc) * cells, hipMemcpyDeviceToHost, s->st));
-        BH_HIP(hipMemcpyAsync(wacc.data(), s->wacc, sizeof(long long) * wacc.size(), hipMemcpyDeviceToHost, s->st));
-        BH_HIP(hipMemcpyAsync(&bad, s->neg, sizeof(u64), hipMemcpyDeviceToHost, s->st));
-        BH_HIP(hipStreamSynchronize(s->st));
-        if (bad) return bh::fail_who(who, "negative weight");
-    }
-    const double nan = std::nan("");
-    for (size_t z = 0; z < (size_t)s->nsets; z++) {
-        const bool any = wacc[2 * z] > 0;              // a set without a row that counts: sums 0, min / max NaN
-        if (total) total[z] = wacc[2 * z];
-        if (excluded) excluded[z] = wacc[2 * z + 1];
-        for (size_t i = z * n; i < (z + 1) * n; i++) {
-            if (s1) s1[i] = any ? acc[i].s1 : 0.0;
-            if (s2) s2[i] = any ? acc[i].s2 : 0.0;
-            if (vmin) vmin[i] = any ? acc[i].vmin : nan;
-            if (vmax) vmax[i] = any ? acc[i].vmax : nan;
-        }
-    }
-    return BH_OK;
+    if (!handle) return bh::fail_who(who, "handle is NULL");
+    return ((RfSensSets *)handle)->finish(who, total, excluded, s1, s2, vmin, vmax);
 }
 
 extern "C" void bh_rf_sens_sets_destroy(void *handle)
 {
-    RfSensSets *s = (RfSensSets *)handle;
-    if (!s) return;
-    if (s->dedges) (void)hipStreamSynchronize(s->st);      // (a handle that never saw a row never saw the device)
-    delete s;
+    delete (RfSensSets *)handle;
 }

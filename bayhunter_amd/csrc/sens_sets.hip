@@ -10,12 +10,13 @@
 //                           index are uniform in the workgroup: a row without weight or without a model costs no barrier.
 //                           The partial goes to the block's row of the slab; the thread of cell 0 of a period also
 //                           carries the period's total and excluded weight.
-//   sens_sets_fold_kernel   one thread per item (and one per period for the weights) adds the slab's rows to their sets'
-//                           sums in block order.
+//   sens_sets_fold_kernel   (sens_sets_host.h, with nw = nper weight pairs a block) one thread per item, and one per
+//                           period for the weights, adds the slab's rows to their sets' sums in block order.
 //
 // The slab holds a bounded number of blocks: a call's blocks are taken in chunks, each folded before the next is
-// launched, which is the order of one pass over all of them.  No scratch; LDS sens_sets_lds_doubles (49 KiB at 100
-// layers and 60 periods).
+// launched, which is the order of one pass over all of them.  The handle, that loop and the finish are
+// sens_sets_host.h's SensSetsHandle; here are the main kernel, its arguments and launch, and the checks of what only
+// this reduction takes.  No scratch; LDS sens_sets_lds_doubles (49 KiB at 100 layers and 60 periods).
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -98,77 +99,7 @@ __global__ __launch_bounds__(kSensSetsThreads) void sens_sets_kernel(SensSetsArg
     }
 }
 
-// thread t < nitems: item t of every block's partial into its set's sums; the next nper threads: the weights
-__global__ void sens_sets_fold_kernel(const int3 *blocks, int nblocks, int nitems, int nper, const SensSetsAcc *slab,
-                                      const long long *wslab, SensSetsAcc *acc, long long *wacc)
-{
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nitems) {
-        int z = -1;
-        SensSetsAcc cur;
-        bh::sens_sets_acc_init(cur);
-        for (int b = 0; b < nblocks; b++) {
-            const int zb = blocks[b].x;
-            if (zb != z) {
-                if (z >= 0) acc[(size_t)z * nitems + t] = cur;
-                z = zb;
-                cur = acc[(size_t)z * nitems + t];
-            }
-            bh::sens_sets_acc_fold(cur, slab[(size_t)b * nitems + t]);
-        }
-        if (z >= 0) acc[(size_t)z * nitems + t] = cur;
-    } else if (t < nitems + nper) {
-        const int p = t - nitems;
-        for (int b = 0; b < nblocks; b++) {
-            long long *out = wacc + ((size_t)blocks[b].x * nper + p) * 2;
-            out[0] += wslab[((size_t)b * nper + p) * 2];
-            out[1] += wslab[((size_t)b * nper + p) * 2 + 1];
-        }
-    }
-}
-
-__global__ void sens_sets_init_kernel(SensSetsAcc *acc, size_t n)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) bh::sens_sets_acc_init(acc[i]);
-}
-
-struct SensSets {
-    int nsets = 0, nper = 0, nb = 0, kind = 0;
-    double drho = 0.0;
-    hipStream_t st = nullptr;
-    bh::SensSetRows rows;                          // the sets, and the row the next add begins with
-    size_t cap = 1;                                // blocks the slab holds
-    bh::DevBufs bufs;
-    double *dedges = nullptr;
-    int3 *dblocks = nullptr;
-    SensSetsAcc *slab = nullptr, *acc = nullptr;   // [cap][nitems], [nsets][nitems]
-    long long *wslab = nullptr, *wacc = nullptr;   // [cap][nper][2], [nsets][nper][2]
-    u64 *neg = nullptr;
-
-    size_t nitems() const { return (size_t)nper * (nb + 1); }
-};
-
-int create(SensSets *s, const double *edges, int nedges)
-{
-    const size_t n = s->nitems();
-    s->cap = s->rows.slab_blocks(n);
-    BH_HIP(s->bufs.alloc(s->dedges, (size_t)nedges));
-    BH_HIP(s->bufs.alloc(s->dblocks, s->cap));
-    BH_HIP(s->bufs.alloc(s->slab, s->cap * n));
-    BH_HIP(s->bufs.alloc(s->wslab, s->cap * s->nper * 2));
-    BH_HIP(s->bufs.alloc(s->acc, (size_t)s->nsets * n));
-    BH_HIP(s->bufs.alloc(s->wacc, (size_t)s->nsets * s->nper * 2));
-    BH_HIP(s->bufs.alloc(s->neg, 1));
-    BH_HIP(hipMemcpyAsync(s->dedges, edges, sizeof(double) * nedges, hipMemcpyHostToDevice, s->st));
-    BH_HIP(hipMemsetAsync(s->wacc, 0, sizeof(long long) * (size_t)s->nsets * s->nper * 2, s->st));
-    BH_HIP(hipMemsetAsync(s->neg, 0, sizeof(u64), s->st));
-    const size_t cells = (size_t)s->nsets * n;
-    hipLaunchKernelGGL(sens_sets_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s->st, s->acc, cells);
-    BH_HIP(hipGetLastError());
-    BH_HIP(hipStreamSynchronize(s->st));           // `edges` is the caller's
-    return BH_OK;
-}
+typedef bh::SensSetsHandle SensSets;    // nw = nper: a block carries a weight pair per period
 
 }  // namespace
 
@@ -182,15 +113,10 @@ extern "C" int bh_sens_sets_create(void **handle, const long long *set_start, in
     if (int rc = bh::require_device()) return rc;
     SensSets *s = new (std::nothrow) SensSets;
     if (!s) return bh::fail_who(who, "out of host memory");
-    s->nsets = nsets;
-    s->nper = nper;
-    s->nb = nedges - 1;
-    s->kind = kind;
-    s->drho = drho_dvp;
-    s->st = (hipStream_t)stream;
-    s->rows.nsets = nsets;
-    s->rows.start.assign(set_start, set_start + nsets + 1);
-    if (int rc = create(s, edges, nedges)) {
+    s->init(set_start, nsets, edges, nedges, kind, drho_dvp, stream);
+    s->nw = nper;
+    s->nitems = (size_t)nper * nedges;
+    if (int rc = s->make_ready()) {
         delete s;
         return rc;
     }
@@ -205,83 +131,34 @@ extern "C" int bh_sens_sets_add(void *handle, long long row0, int B, int Lmax, i
     const char *who = "bh_sens_sets_add";
     SensSets *s = (SensSets *)handle;
     if (!s) return bh::fail_who(who, "handle is NULL");
-    if (B < 0 || Lmax < 1 || Lmax > BH_MAX_LAYERS) return bh::fail_who(who, "B/Lmax out of range");
-    if (model_stride < Lmax) return bh::fail_who(who, "model_stride < Lmax");
-    if (const char *fault = bh::sens_sets_rows_fault(s->rows, row0, B)) return bh::fail_who(who, fault);
+    if (int rc = s->check_add(who, row0, B, Lmax, model_stride, nlay, hthk, q, q_stride, K, c_out ? nullptr : "NULL pointer"))
+        return rc;
     if (B == 0) return BH_OK;
-    if (s->kind == BH_SENS_KIND_VS_TOTAL && !q) return bh::fail_who(who, "BH_SENS_KIND_VS_TOTAL needs q");
-    if (q && q_stride < Lmax) return bh::fail_who(who, "q_stride < Lmax");
-    if (!nlay || !hthk || !K || !c_out) return bh::fail_who(who, "NULL pointer");
-    if (!s->rows.cut_ok(row0) || !s->rows.cut_ok(row0 + B)) return bh::fail_who(who, bh::kSensSetsCutFault);
-    std::vector<int3> blocks;
-    bh::CallBufs drain(s->st);                      // (owns nothing: an early return waits for the copies of `blocks`)
-    s->rows.call_blocks(row0, B, blocks);
+    const int nper = s->nw;
     SensSetsArgs a;
     std::memset(&a, 0, sizeof(a));
     a.blocks = s->dblocks;
-    a.Lmax = Lmax; a.mstride = model_stride; a.qstride = q_stride; a.nper = s->nper; a.nb = s->nb; a.kind = s->kind;
-    a.span = bh::sens_sets_span(s->nper, s->nb);
+    a.Lmax = Lmax; a.mstride = model_stride; a.qstride = q_stride; a.nper = nper; a.nb = s->nb; a.kind = s->kind;
+    a.span = bh::sens_sets_span(nper, s->nb);
     a.drho = s->drho;
     a.nlay = nlay; a.w = weights; a.h = hthk; a.q = q; a.K = K; a.c = c_out; a.edges = s->dedges;
     a.slab = s->slab; a.wslab = s->wslab; a.neg = s->neg;
-    const size_t lds = sizeof(double) * (size_t)bh::sens_sets_lds_doubles(Lmax, s->nper, s->nb);
-    const int nitems = (int)s->nitems();
-    const unsigned groups = (unsigned)((nitems + kSensSetsThreads - 1) / kSensSetsThreads);
-    const unsigned fold = (unsigned)((nitems + s->nper + 255) / 256);
-    for (size_t b0 = 0; b0 < blocks.size(); b0 += s->cap) {
-        const size_t nb = blocks.size() - b0 < s->cap ? blocks.size() - b0 : s->cap;
-        BH_HIP(hipMemcpyAsync(s->dblocks, blocks.data() + b0, sizeof(int3) * nb, hipMemcpyHostToDevice, s->st));
-        hipLaunchKernelGGL(sens_sets_kernel, dim3((unsigned)nb, groups), dim3(kSensSetsThreads), lds, s->st, a);
-        BH_HIP(hipGetLastError());
-        hipLaunchKernelGGL(sens_sets_fold_kernel, dim3(fold), dim3(256), 0, s->st, (const int3 *)s->dblocks, (int)nb, nitems,
-                           s->nper, (const SensSetsAcc *)s->slab, (const long long *)s->wslab, s->acc, s->wacc);
-        BH_HIP(hipGetLastError());
-    }
-    // the call's arrays are free when it returns, and a negative weight is reported by the call that brought it
-    u64 bad = 0;
-    BH_HIP(hipMemcpyAsync(&bad, s->neg, sizeof(u64), hipMemcpyDeviceToHost, s->st));
-    BH_HIP(hipStreamSynchronize(s->st));
-    s->rows.next = row0 + B;
-    if (bad) return bh::fail_who(who, "negative weight");
-    return BH_OK;
+    const size_t lds = sizeof(double) * (size_t)bh::sens_sets_lds_doubles(Lmax, nper, s->nb);
+    const unsigned groups = (unsigned)(((int)s->nitems + kSensSetsThreads - 1) / kSensSetsThreads);
+    return s->add(who, row0, B, [&](unsigned nblocks) {
+        hipLaunchKernelGGL(sens_sets_kernel, dim3(nblocks, groups), dim3(kSensSetsThreads), lds, s->st, a);
+    });
 }
 
 extern "C" int bh_sens_sets_finish(void *handle, long long *total, long long *excluded, double *s1, double *s2,
                                    double *vmin, double *vmax)
 {
     const char *who = "bh_sens_sets_finish";
-    SensSets *s = (SensSets *)handle;
-    if (!s) return bh::fail_who(who, "handle is NULL");
-    if (s->rows.next != s->rows.total_rows()) return bh::fail_who(who, "not all rows of set_start were added");
-    const size_t n = s->nitems(), cells = (size_t)s->nsets * n, nw = (size_t)s->nsets * s->nper;
-    std::vector<SensSetsAcc> acc(cells);
-    std::vector<long long> wacc(nw * 2);
-    u64 bad = 0;
-    BH_HIP(hipMemcpyAsync(acc.data(), s->acc, sizeof(SensSetsAcc) * cells, hipMemcpyDeviceToHost, s->st));
-    BH_HIP(hipMemcpyAsync(wacc.data(), s->wacc, sizeof(long long) * nw * 2, hipMemcpyDeviceToHost, s->st));
-    BH_HIP(hipMemcpyAsync(&bad, s->neg, sizeof(u64), hipMemcpyDeviceToHost, s->st));
-    BH_HIP(hipStreamSynchronize(s->st));
-    if (bad) return bh::fail_who(who, "negative weight");
-    const double nan = std::nan("");
-    for (size_t zp = 0; zp < nw; zp++) {
-        const bool any = wacc[2 * zp] > 0;             // a period without a row that counts: sums 0, min / max NaN
-        if (total) total[zp] = wacc[2 * zp];
-        if (excluded) excluded[zp] = wacc[2 * zp + 1];
-        for (size_t j = 0; j <= (size_t)s->nb; j++) {
-            const size_t i = zp * (s->nb + 1) + j;
-            if (s1) s1[i] = any ? acc[i].s1 : 0.0;
-            if (s2) s2[i] = any ? acc[i].s2 : 0.0;
-            if (vmin) vmin[i] = any ? acc[i].vmin : nan;
-            if (vmax) vmax[i] = any ? acc[i].vmax : nan;
-        }
-    }
-    return BH_OK;
+    if (!handle) return bh::fail_who(who, "handle is NULL");
+    return ((SensSets *)handle)->finish(who, total, excluded, s1, s2, vmin, vmax);
 }
 
 extern "C" void bh_sens_sets_destroy(void *handle)
 {
-    SensSets *s = (SensSets *)handle;
-    if (!s) return;
-    (void)hipStreamSynchronize(s->st);
-    delete s;
+    delete (SensSets *)handle;
 }

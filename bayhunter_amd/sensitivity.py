@@ -44,6 +44,8 @@ section 7k): bh_sens_sets' sums at a selection of the trace's samples, a row cou
     rf_summarize_sets(rfparams, models, set_start, ...)  the same for every set of rows, each at its own ray parameter
     ChainPool.rf_sensitivity / StationPool.rf_sensitivity            (pool_rf_sensitivity, stations_rf_sensitivity)
 """
+import collections
+
 import numpy as np
 
 from . import _lib, selection as sel
@@ -106,12 +108,8 @@ def rf_batch(rfparams, H, VP, VS, RHO, nlay, ref='prf'):
     (None: the top layer's vs) -- plugins.RFminiModRF's modelparams; ref 'prf' | 'seis' (incident P) or 'srf' (SV).
     NaN in the layers a model does not have, and throughout for a model without a trace."""
     import torch
-    from .engine import ForwardEngine, RfSpec
-    unknown = set(rfparams) - {'obsx', 'gauss', 'p', 'nsv', 'water', 'wtype'}
-    if 'obsx' not in rfparams or unknown:
-        raise ValueError("rfparams: a dict with 'obsx' and optionally 'gauss', 'p', 'nsv' (unknown: %s)" % sorted(unknown))
-    eng = ForwardEngine(rf=[RfSpec(ref, rfparams['obsx'], rfparams.get('gauss', 1.0), rfparams.get('p', 6.4),
-                                   rfparams.get('nsv'), wtype=rfparams.get('wtype'))])
+    from .engine import ForwardEngine
+    eng = ForwardEngine(rf=[_rf_spec(rfparams, ref)])
     res = eng.rf_sensitivity(eng.upload(H, VP, VS, RHO, np.asarray(nlay, dtype=np.int32)))
     torch.cuda.synchronize(eng.device)
     return {'K': res['K'].cpu().numpy(), 'rf': res['rf'].cpu().numpy(), 't': res['t']}
@@ -215,39 +213,41 @@ def split_runs(set_start, max_rows):
     return runs
 
 
-class SensSets(object):
-    """One bh_sens_sets handle: add(row0, models, K, c, q, weights) run after run, then finish()."""
+class _SetsHandle(object):
+    """One handle of a depth-binned reduction bh_<name>_*: a subclass creates it and adds run after run, then finish()."""
 
-    def __init__(self, set_start, nper, edges, kind, drho_dvp, stream):
+    def _create(self, name, set_start, own, counts, nitems, edges, kind, drho_dvp, stream):
+        """bh_<name>_create with the arguments `own` between the sets and the edges; finish() returns total and excluded
+        [sets] + counts and the sums [sets, nitems, bins + 1]."""
         import ctypes as C
-        self.lib = _lib.load()
+        self.lib, self.name, self.stream = _lib.load(), name, stream
         self.set_start = np.ascontiguousarray(set_start, dtype=np.int64)
-        self.nsets, self.nper, self.edges = self.set_start.size - 1, int(nper), np.ascontiguousarray(edges, dtype=np.float64)
+        self.nsets, self.edges = self.set_start.size - 1, np.ascontiguousarray(edges, dtype=np.float64)
+        self.shapes = (self.nsets,) + counts, (self.nsets, nitems, self.edges.size)
         self.h = C.c_void_p()
-        _lib.check(self.lib.bh_sens_sets_create(C.byref(self.h), self.set_start.ctypes.data, self.nsets, self.nper,
-                                                self.edges.ctypes.data, self.edges.size, int(kind), float(drho_dvp), stream))
+        _lib.check(getattr(self.lib, 'bh_%s_create' % name)(
+            C.byref(self.h), self.set_start.ctypes.data, self.nsets, *own, self.edges.ctypes.data, self.edges.size, int(kind),
+            float(drho_dvp), stream))
 
-    def add(self, row0, models, K, c, q=None, weights=None):
-        """Rows row0 .. of the numbering: models an engine.DeviceModels, K and c what ForwardEngine.sensitivity returned
-        for them, q [B, Lmax] float64 or None, weights int32 [B] or None -- device tensors."""
-        _lib.check(self.lib.bh_sens_sets_add(
+    def _add(self, row0, models, q, weights, K, *own):
+        _lib.check(getattr(self.lib, 'bh_%s_add' % self.name)(
             self.h, int(row0), models.B, models.Lmax, 4 * models.Lmax, models.nlay.data_ptr(), models.H.data_ptr(),
-            None if q is None else q.data_ptr(), 0 if q is None else q.stride(0), K.data_ptr(), c.data_ptr(),
+            None if q is None else q.data_ptr(), 0 if q is None else q.stride(0), K.data_ptr(), *own,
             None if weights is None else weights.data_ptr()))
 
     def finish(self):
-        """-> dict(total, excluded [sets, nper] int64, s1, s2, vmin, vmax [sets, nper, bins + 1])"""
-        Z, P, C1 = self.nsets, self.nper, self.edges.size
-        out = dict(total=np.zeros((Z, P), dtype=np.int64), excluded=np.zeros((Z, P), dtype=np.int64))
+        """-> dict(total, excluded int64, s1, s2, vmin, vmax float64): SensSets [sets, nper] and [sets, nper, bins + 1],
+        RfSensSets [sets] and [sets, samples, bins + 1]"""
+        out = dict(total=np.zeros(self.shapes[0], dtype=np.int64), excluded=np.zeros(self.shapes[0], dtype=np.int64))
         for k in ('s1', 's2', 'vmin', 'vmax'):
-            out[k] = np.zeros((Z, P, C1))
-        _lib.check(self.lib.bh_sens_sets_finish(self.h, *[out[k].ctypes.data for k in
-                                                          ('total', 'excluded', 's1', 's2', 'vmin', 'vmax')]))
+            out[k] = np.zeros(self.shapes[1])
+        _lib.check(getattr(self.lib, 'bh_%s_finish' % self.name)(self.h, *[out[k].ctypes.data for k in
+                                                                         ('total', 'excluded', 's1', 's2', 'vmin', 'vmax')]))
         return out
 
     def close(self):
         if self.h:
-            self.lib.bh_sens_sets_destroy(self.h)
+            getattr(self.lib, 'bh_%s_destroy' % self.name)(self.h)
             self.h = None
 
     def __enter__(self):
@@ -257,19 +257,98 @@ class SensSets(object):
         self.close()
 
 
-def _result(sums, z, periods, edges, kind, velocity='phase'):
-    """summarize()'s dict of set z, or None for a set without a counting row at any period."""
+class SensSets(_SetsHandle):
+    """One bh_sens_sets handle: add(row0, models, K, c, q, weights) run after run, then finish()."""
+
+    def __init__(self, set_start, nper, edges, kind, drho_dvp, stream):
+        self.nper = int(nper)
+        self._create('sens_sets', set_start, (self.nper,), (self.nper,), self.nper, edges, kind, drho_dvp, stream)
+
+    def add(self, row0, models, K, c, q=None, weights=None):
+        """Rows row0 .. of the numbering: models an engine.DeviceModels, K and c what ForwardEngine.sensitivity returned
+        for them, q [B, Lmax] float64 or None, weights int32 [B] or None -- device tensors."""
+        self._add(row0, models, q, weights, K, c.data_ptr())
+
+
+def _set_result(sums, z, axes, edges, kind):
+    """The dict of set z from a handle's sums, or None for a set without a counting row: summarize()'s with the counts
+    [nper] and axes = {'periods': }, rf_summarize()'s with integer counts and axes = {'t': , 'samples': }."""
     total = sums['total'][z]
-    if not total.any():
+    if not np.any(total):
         return None
+    count = np.copy if np.ndim(total) else int
     mean, std = from_sums(total, sums['s1'][z], sums['s2'][z], sums['vmin'][z], sums['vmax'][z])
     res = {'mean': mean[:, :-1], 'std': std[:, :-1], 'min': sums['vmin'][z][:, :-1].copy(),
            'max': sums['vmax'][z][:, :-1].copy(), 'halfspace_mean': mean[:, -1], 'halfspace_std': std[:, -1],
-           'nmodels': total.copy(), 'nexcluded': sums['excluded'][z].copy(), 'periods': periods, 'edges': edges,
-           'kind': kind}
-    if velocity != 'phase':                     # (the phase result keeps the keys it had)
-        res['velocity'] = velocity
+           'nmodels': count(total), 'nexcluded': count(sums['excluded'][z])}
+    res.update(axes, edges=edges, kind=kind)
     return res
+
+
+# What differs between the two reductions, for _summarize_sets:
+#   check(Z)                         the pass's own checks that need the number of sets, before a device is touched
+#   engine(dev)                      its ForwardEngine
+#   row_bytes(eng, Lmax)             the device bytes a row takes in the pass, for the default max_rows
+#   runs(set_start, max_rows)        the runs of rows in order, (lo, hi, ...)
+#   handle(set_start, stream)        its SensSets or RfSensSets
+#   add(handle, eng, run, dm, q, w)  the pass for the run's models dm, and handle.add
+#   result(sums, z)                  the dict of set z, or None
+#   empty                            the message of a set whose rows do not count
+_Pass = collections.namedtuple('_Pass', 'check engine row_bytes runs handle add result empty')
+
+
+def _summarize_sets(ps, models, set_start, vpvs, weights, kind, mantle, device, max_rows, strict):
+    """summarize_sets and rf_summarize_sets behind their own checks: the checks of the rows, then per run of the _Pass
+    `ps` the upload, the layers, q = vp / vs and the pass, and every set's result."""
+    import torch
+    from . import _device, datafits as df
+    from .models import layers_from_voronoi
+    shape = getattr(models, 'shape', None) or np.asarray(models).shape
+    if len(shape) != 2:
+        raise ValueError("models: [rows, 2*maxlayers]")
+    R = shape[0]
+    set_start, Z = sel.check_set_start(set_start, R)
+    vp = None if np.ndim(vpvs) == 0 else vpvs
+    if vp is not None and len(vp) != R:
+        raise ValueError("vpvs: one per row, or a scalar")
+    if weights is not None and len(weights) != R:
+        raise ValueError("one weight per row")
+    if weights is not None and not hasattr(weights, 'is_cuda') and np.any(np.asarray(weights) < 0):
+        raise ValueError("negative weight")
+    if max_rows is not None and int(max_rows) < 1:
+        raise ValueError("max_rows >= 1")
+    ps.check(Z)
+    results, failed = [None] * Z, {}
+    if R == 0:
+        failed = {z: "empty selection: no models" for z in range(Z)}
+        sel.raise_first_failed(failed, strict, "set")
+        return sel.SetList(results, failed)
+    dev = _device.torch_device(device)
+    with torch.cuda.device(dev):
+        eng = ps.engine(dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        Lmax = shape[1] // 2
+        if max_rows is None:       # half of the free device memory: the pass's arrays, the row, its layers (packed, nuclei, q)
+            per_row = ps.row_bytes(eng, Lmax) + 8 * (shape[1] + 8 * Lmax) + 16
+            max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
+        with ps.handle(set_start, stream) as handle:
+            for run in ps.runs(set_start, max_rows):
+                lo, hi = run[:2]
+                rows = _device.to_device(models[lo:hi], torch.float64, dev)
+                v = vpvs if vp is None else vp[lo:hi]
+                v = _device.to_device(np.broadcast_to(np.asarray(v, dtype=np.float64), (hi - lo,)).copy()
+                                      if not isinstance(v, torch.Tensor) else v, torch.float64, dev)
+                w = None if weights is None else _device.to_device(weights[lo:hi], torch.int32, dev)
+                vsn, zv, nl = df._layers(rows, dev)
+                dm, _ = layers_from_voronoi(vsn, zv, nl, v, df._OPEN_PRIORS, mantle=mantle, device=dev)
+                ps.add(handle, eng, run, dm, (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None, w)
+            sums = handle.finish()
+    for z in range(Z):
+        results[z] = ps.result(sums, z)
+        if results[z] is None:
+            failed[z] = "empty selection: no models" if set_start[z] == set_start[z + 1] else ps.empty
+    sel.raise_first_failed(failed, strict, "set")
+    return sel.SetList(results, failed)
 
 
 def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None,
@@ -299,10 +378,7 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
     count; left out: no model, a failed search, no root); periods, edges, kind), every field bit for bit what summarize
     returns for the set's rows alone.  A set without a row that counts at any period raises a ValueError naming the
     first such set -- or, with strict=False, has the entry None and its message in the list's `failed`."""
-    import torch
-    from . import _device, datafits as df
     from .engine import EllSpec, ForwardEngine, SwdSpec
-    from .models import layers_from_voronoi
     if wave not in REFS:
         raise ValueError("wave %r: 'rayleigh' or 'love'" % (wave,))
     if velocity not in VELOCITIES:
@@ -312,74 +388,47 @@ def summarize_sets(periods, wave, models, set_start, vpvs, weights=None, dep_edg
     method, counted, extra = PASSES[velocity]
     code, edges = _check_kind(kind), _check_edges(dep_edges)
     periods = np.ascontiguousarray(periods, dtype=np.float64)
-    shape = getattr(models, 'shape', None) or np.asarray(models).shape
-    if len(shape) != 2:
-        raise ValueError("models: [rows, 2*maxlayers]")
-    R = shape[0]
-    set_start, Z = sel.check_set_start(set_start, R)
-    vp = None if np.ndim(vpvs) == 0 else vpvs
-    if vp is not None and len(vp) != R:
-        raise ValueError("vpvs: one per row, or a scalar")
-    if weights is not None and len(weights) != R:
-        raise ValueError("one weight per row")
-    if weights is not None and not hasattr(weights, 'is_cuda') and np.any(np.asarray(weights) < 0):
-        raise ValueError("negative weight")
-    if max_rows is not None and int(max_rows) < 1:
-        raise ValueError("max_rows >= 1")
-    if periods.ndim != 1 or periods.size < 1:
-        raise ValueError("periods: one at least")
-    spec = SwdSpec(REFS[wave], periods)
-    if spec.resample:
-        raise ValueError("sensitivity: target '%s' has more than %d periods"
-                         % ('rellip' if velocity == 'ellipticity' else spec.ref, _lib.MAX_PERIODS))
-    results, failed = [None] * Z, {}
-    if R == 0:
-        failed = {z: "empty selection: no models" for z in range(Z)}
-        sel.raise_first_failed(failed, strict, "set")
-        return sel.SetList(results, failed)
-    dev = _device.torch_device(device)
-    with torch.cuda.device(dev):
+    nper = periods.size
+    # The ellipticity's K_vs and (vp / vs) K_vp cancel to 1e-7 of their size at short periods: its 'vs_total' is formed
+    # per layer in vs_total()'s own operation order (bh_ell_sens_vs_total, in place of K_vs) and reduced as kind 'vs'
+    plain_total = velocity == 'ellipticity' and kind == 'vs_total'
+    if plain_total:
+        code = _lib.SENS_KINDS['vs']
+
+    def check(Z):
+        if periods.ndim != 1 or nper < 1:
+            raise ValueError("periods: one at least")
+        if SwdSpec(REFS[wave], periods).resample:
+            raise ValueError("sensitivity: target '%s' has more than %d periods"
+                             % ('rellip' if velocity == 'ellipticity' else REFS[wave], _lib.MAX_PERIODS))
+
+    def engine(dev):
         if velocity == 'ellipticity':          # its phase velocities are a hidden 'rdispph' target's, as in an inversion
-            eng = ForwardEngine(ell=[EllSpec('rellip', periods, 0, absolute)], device=dev)
-        else:
-            eng = ForwardEngine(swd=[spec], device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        Lmax, nper = shape[1] // 2, periods.size
-        if max_rows is None:       # half of the free device memory: K, c, dc/dT and the workspace, the row, its layers
-            per_row = 8 * (4 * nper * Lmax + 3 * nper + eng.row + shape[1] + 8 * Lmax) + 16      # (packed, nuclei, q)
-            if extra is not None:
-                per_row += 8 * (4 * nper * Lmax + extra * nper)
-            max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
-        # The ellipticity's K_vs and (vp / vs) K_vp cancel to 1e-7 of their size at short periods: its 'vs_total' is formed
-        # per layer in vs_total()'s own operation order (bh_ell_sens_vs_total, in place of K_vs) and reduced as kind 'vs'
-        plain_total = velocity == 'ellipticity' and kind == 'vs_total'
+            return ForwardEngine(ell=[EllSpec('rellip', periods, 0, absolute)], device=dev)
+        return ForwardEngine(swd=[SwdSpec(REFS[wave], periods)], device=dev)
+
+    def row_bytes(eng, Lmax):                  # K, c, dc/dT and the workspace; a second K and the pass's own beyond the phase's
+        return 8 * (4 * nper * Lmax + 3 * nper + eng.row + (0 if extra is None else 4 * nper * Lmax + extra * nper))
+
+    def add(handle, eng, run, dm, q, w):
+        out, err = eng.run(dm)
+        res = getattr(eng, method)(dm, out=out, err=err)
+        K = res['K']
         if plain_total:
-            code = _lib.SENS_KINDS['vs']
-        with SensSets(set_start, nper, edges, code, drho_dvp, stream) as handle:
-            for lo, hi in split_runs(set_start, max_rows):
-                rows = _device.to_device(models[lo:hi], torch.float64, dev)
-                v = vpvs if vp is None else vp[lo:hi]
-                v = _device.to_device(np.broadcast_to(np.asarray(v, dtype=np.float64), (hi - lo,)).copy()
-                                      if not isinstance(v, torch.Tensor) else v, torch.float64, dev)
-                w = None if weights is None else _device.to_device(weights[lo:hi], torch.int32, dev)
-                vsn, zv, nl = df._layers(rows, dev)
-                dm, _ = layers_from_voronoi(vsn, zv, nl, v, df._OPEN_PRIORS, mantle=mantle, device=dev)
-                out, err = eng.run(dm)
-                res = getattr(eng, method)(dm, out=out, err=err)
-                K, c = res['K'], res[counted]
-                q = (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None
-                if plain_total:
-                    _lib.check(handle.lib.bh_ell_sens_vs_total(dm.B, dm.Lmax, nper, K.data_ptr(), q.data_ptr(), q.stride(0),
-                                                               float(drho_dvp), K.data_ptr(), stream))
-                    q = None
-                handle.add(lo, dm, K, c, q, w)
-            sums = handle.finish()
-    for z in range(Z):
-        results[z] = _result(sums, z, periods, edges, kind, velocity)
-        if results[z] is None:
-            failed[z] = "empty selection: no models" if set_start[z] == set_start[z + 1] else _EMPTY
-    sel.raise_first_failed(failed, strict, "set")
-    return sel.SetList(results, failed)
+            _lib.check(handle.lib.bh_ell_sens_vs_total(dm.B, dm.Lmax, nper, K.data_ptr(), q.data_ptr(), q.stride(0),
+                                                       float(drho_dvp), K.data_ptr(), handle.stream))
+            q = None
+        handle.add(run[0], dm, K, res[counted], q, w)
+
+    def result(sums, z):
+        res = _set_result(sums, z, {'periods': periods}, edges, kind)
+        if res is not None and velocity != 'phase':                     # (the phase result keeps the keys it had)
+            res['velocity'] = velocity
+        return res
+    return _summarize_sets(_Pass(check, engine, row_bytes, split_runs,
+                                 lambda set_start, stream: SensSets(set_start, nper, edges, code, drho_dvp, stream), add,
+                                 result, _EMPTY),
+                           models, set_start, vpvs, weights, kind, mantle, device, max_rows, strict)
 
 
 def summarize(periods, wave, models, vpvs, weights=None, dep_edges=None, kind='vs_total', mantle=None, device=None,
@@ -474,7 +523,38 @@ def pool_sensitivity(pool, ref=None, dep_edges=None, kind='vs_total', selection=
     return res
 
 
-class StationSensitivity(sel.StationResult):
+class _StationArrays(sel.StationResult):
+    """What StationSensitivity and StationRfSensitivity share: `stations`, ref, edges, kind, and the per-station arrays
+    of n periods or samples -- the counts [nstations] + counts -- filled from the stations' dicts."""
+
+    def __init__(self, names, results, failed, ref, edges, kind, n, counts):
+        sel.StationResult.__init__(self, names, failed)
+        self.stations = {name: r for name, r in zip(names, results) if r is not None}
+        self.ref, self.edges, self.kind = ref, edges, kind
+        Z, nb = len(results), edges.size - 1
+        for k in ('mean', 'std', 'min', 'max'):
+            setattr(self, k, np.full((Z, n, nb), np.nan))
+        self.halfspace_mean, self.halfspace_std = np.full((Z, n), np.nan), np.full((Z, n), np.nan)
+        self.nmodels, self.nexcluded = np.zeros((Z,) + counts, dtype=np.int64), np.zeros((Z,) + counts, dtype=np.int64)
+        for z, r in enumerate(results):
+            if r is not None:
+                for k in ('mean', 'std', 'min', 'max', 'halfspace_mean', 'halfspace_std', 'nmodels', 'nexcluded'):
+                    getattr(self, k)[z] = r[k]
+
+
+def _finish_stations(spool, res, failed, strict, ref, ci, set_start):
+    """The end of both station calls: the sets' failures join the stations' (raised with `strict`), and every station's
+    dict gets 'ref' and 'chains'."""
+    for z, msg in res.failed.items():
+        failed.setdefault(z, msg)
+    sel.raise_first_failed(failed, strict, "station", spool.names)
+    for z, r in enumerate(res):
+        if r is not None:
+            r['ref'] = ref
+            r['chains'] = sel.station_chains(ci, set_start, z, spool.chains_per_station)
+
+
+class StationSensitivity(_StationArrays):
     """StationPool.sensitivity's result, every array in the pool's station order.
 
     names, failed    the stations; {station name: message} (such a station is NaN throughout)
@@ -486,18 +566,8 @@ class StationSensitivity(sel.StationResult):
     velocity = 'phase'      # 'group' on StationPool.group_sensitivity's result, 'ellipticity' on ell_sensitivity's
 
     def __init__(self, names, results, failed, ref, periods, edges, kind):
-        sel.StationResult.__init__(self, names, failed)
-        self.stations = {n: r for n, r in zip(names, results) if r is not None}
-        self.ref, self.periods, self.edges, self.kind = ref, periods, edges, kind
-        Z, P, nb = len(results), periods.size, edges.size - 1
-        for k in ('mean', 'std', 'min', 'max'):
-            setattr(self, k, np.full((Z, P, nb), np.nan))
-        self.halfspace_mean, self.halfspace_std = np.full((Z, P), np.nan), np.full((Z, P), np.nan)
-        self.nmodels, self.nexcluded = np.zeros((Z, P), dtype=np.int64), np.zeros((Z, P), dtype=np.int64)
-        for z, r in enumerate(results):
-            if r is not None:
-                for k in ('mean', 'std', 'min', 'max', 'halfspace_mean', 'halfspace_std', 'nmodels', 'nexcluded'):
-                    getattr(self, k)[z] = r[k]
+        self.periods = periods
+        _StationArrays.__init__(self, names, results, failed, ref, edges, kind, periods.size, (periods.size,))
 
 
 def stations_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', selection='weighted', dev=0.05,
@@ -511,13 +581,7 @@ def stations_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', selec
     res = summarize_sets(periods, wave, pool.models[ci, ri], set_start, pool.vpvs[ci, ri].astype(np.float64),
                          w.astype(np.int32), edges, kind, pool.priors.get('mantle'), device, max_rows, strict=False,
                          velocity=velocity, absolute=_pool_absolute(spool.stations[0], tref, velocity))
-    for z, msg in res.failed.items():
-        failed.setdefault(z, msg)
-    sel.raise_first_failed(failed, strict, "station", spool.names)
-    for z, r in enumerate(res):
-        if r is not None:
-            r['ref'] = tref
-            r['chains'] = sel.station_chains(ci, set_start, z, c)
+    _finish_stations(spool, res, failed, strict, tref, ci, set_start)
     out = StationSensitivity(spool.names, res, failed, tref, periods, edges, kind)
     if velocity != 'phase':
         out.velocity = velocity
@@ -562,60 +626,18 @@ def rf_samples(taxis, t=None, every=1):
     return np.ascontiguousarray(idx, dtype=np.int32)
 
 
-class RfSensSets(object):
+class RfSensSets(_SetsHandle):
     """One bh_rf_sens_sets handle: add(row0, models, K, rf, q, weights) run after run, then finish()."""
 
     def __init__(self, set_start, nout, samples, edges, kind, drho_dvp, stream):
-        import ctypes as C
-        self.lib = _lib.load()
-        self.set_start = np.ascontiguousarray(set_start, dtype=np.int64)
-        self.samples = np.ascontiguousarray(samples, dtype=np.int32)
-        self.nsets, self.nout, self.edges = self.set_start.size - 1, int(nout), np.ascontiguousarray(edges, dtype=np.float64)
-        self.h = C.c_void_p()
-        _lib.check(self.lib.bh_rf_sens_sets_create(C.byref(self.h), self.set_start.ctypes.data, self.nsets, self.nout,
-                                                   self.samples.ctypes.data, self.samples.size, self.edges.ctypes.data,
-                                                   self.edges.size, int(kind), float(drho_dvp), stream))
+        self.nout, self.samples = int(nout), np.ascontiguousarray(samples, dtype=np.int32)
+        self._create('rf_sens_sets', set_start, (self.nout, self.samples.ctypes.data, self.samples.size), (),
+                     self.samples.size, edges, kind, drho_dvp, stream)
 
     def add(self, row0, models, K, rf, q=None, weights=None):
         """Rows row0 .. of the numbering: models an engine.DeviceModels, K and rf what ForwardEngine.rf_sensitivity
         returned for them, q [B, Lmax] float64 or None, weights int32 [B] or None -- device tensors."""
-        _lib.check(self.lib.bh_rf_sens_sets_add(
-            self.h, int(row0), models.B, models.Lmax, 4 * models.Lmax, models.nlay.data_ptr(), models.H.data_ptr(),
-            None if q is None else q.data_ptr(), 0 if q is None else q.stride(0), K.data_ptr(), K.stride(0), rf.data_ptr(),
-            rf.stride(0), None if weights is None else weights.data_ptr()))
-
-    def finish(self):
-        """-> dict(total, excluded [sets] int64, s1, s2, vmin, vmax [sets, samples, bins + 1])"""
-        Z, S, C1 = self.nsets, self.samples.size, self.edges.size
-        out = dict(total=np.zeros(Z, dtype=np.int64), excluded=np.zeros(Z, dtype=np.int64))
-        for k in ('s1', 's2', 'vmin', 'vmax'):
-            out[k] = np.zeros((Z, S, C1))
-        _lib.check(self.lib.bh_rf_sens_sets_finish(self.h, *[out[k].ctypes.data for k in
-                                                             ('total', 'excluded', 's1', 's2', 'vmin', 'vmax')]))
-        return out
-
-    def close(self):
-        if self.h:
-            self.lib.bh_rf_sens_sets_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-def _rf_result(sums, z, taxis, samples, edges, kind):
-    """rf_summarize()'s dict of set z, or None for a set without a counting row."""
-    total = int(sums['total'][z])
-    if not total:
-        return None
-    mean, std = from_sums(np.full(samples.size, total), sums['s1'][z], sums['s2'][z], sums['vmin'][z], sums['vmax'][z])
-    return {'mean': mean[:, :-1], 'std': std[:, :-1], 'min': sums['vmin'][z][:, :-1].copy(),
-            'max': sums['vmax'][z][:, :-1].copy(), 'halfspace_mean': mean[:, -1], 'halfspace_std': std[:, -1],
-            'nmodels': total, 'nexcluded': int(sums['excluded'][z]), 't': taxis[samples], 'samples': samples.copy(),
-            'edges': edges, 'kind': kind}
+        self._add(row0, models, q, weights, K, K.stride(0), rf.data_ptr(), rf.stride(0))
 
 
 def _p_runs(runs, set_start, p):
@@ -657,10 +679,7 @@ def rf_summarize_sets(rfparams, models, set_start, vpvs, weights=None, dep_edges
     kind), every field bit for bit what rf_summarize returns for the set's rows alone at the set's p.  A set without a row
     that counts raises a ValueError naming the first such set -- or, with strict=False, has the entry None and its message
     in the list's `failed`."""
-    import torch
-    from . import _device, datafits as df
     from .engine import ForwardEngine
-    from .models import layers_from_voronoi
     code, edges = _check_kind(kind), _check_edges(dep_edges)
     spec = _rf_spec(rfparams, ref)
     taxis = rf_time_axis(spec)
@@ -668,62 +687,29 @@ def rf_summarize_sets(rfparams, models, set_start, vpvs, weights=None, dep_edges
     if nout > _lib.RF_SENS_SETS_MAX_SAMPLES:
         raise ValueError("rf_sensitivity: the trace has more than %d samples" % _lib.RF_SENS_SETS_MAX_SAMPLES)
     samples = rf_samples(taxis, t, every)
-    shape = getattr(models, 'shape', None) or np.asarray(models).shape
-    if len(shape) != 2:
-        raise ValueError("models: [rows, 2*maxlayers]")
-    R = shape[0]
-    set_start, Z = sel.check_set_start(set_start, R)
-    if Z * samples.size * edges.size * 32 > _lib.RF_SENS_SETS_MAX_ACC_BYTES:
-        raise ValueError("rf_sensitivity: %d sets x %d samples x %d cells exceed the accumulator budget of %d bytes; "
-                         "narrow t or raise every" % (Z, samples.size, edges.size, _lib.RF_SENS_SETS_MAX_ACC_BYTES))
-    vp = None if np.ndim(vpvs) == 0 else vpvs
-    if vp is not None and len(vp) != R:
-        raise ValueError("vpvs: one per row, or a scalar")
-    if weights is not None and len(weights) != R:
-        raise ValueError("one weight per row")
-    if weights is not None and not hasattr(weights, 'is_cuda') and np.any(np.asarray(weights) < 0):
-        raise ValueError("negative weight")
-    if max_rows is not None and int(max_rows) < 1:
-        raise ValueError("max_rows >= 1")
-    pz = np.full(Z, spec.p if p is None else np.nan, dtype=np.float64)
-    if p is not None:
-        if np.ndim(p) != 0 and len(p) != Z:
+
+    def check(Z):
+        if Z * samples.size * edges.size * 32 > _lib.RF_SENS_SETS_MAX_ACC_BYTES:
+            raise ValueError("rf_sensitivity: %d sets x %d samples x %d cells exceed the accumulator budget of %d bytes; "
+                             "narrow t or raise every" % (Z, samples.size, edges.size, _lib.RF_SENS_SETS_MAX_ACC_BYTES))
+        if p is not None and np.ndim(p) != 0 and len(p) != Z:
             raise ValueError("p: a number, or one per set")
-        pz[:] = p
-        if not np.all(np.isfinite(pz)):
+        if p is not None and not np.all(np.isfinite(np.asarray(p, dtype=np.float64))):
             raise ValueError("p: finite")
-    results, failed = [None] * Z, {}
-    if R == 0:
-        failed = {z: "empty selection: no models" for z in range(Z)}
-        sel.raise_first_failed(failed, strict, "set")
-        return sel.SetList(results, failed)
-    dev = _device.torch_device(device)
-    with torch.cuda.device(dev):
-        eng = ForwardEngine(rf=[spec], device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        Lmax = shape[1] // 2
-        if max_rows is None:       # half of the free device memory: K, the trace, the row, its layers (packed, nuclei, q)
-            per_row = 8 * (nout * 4 * Lmax + nout + shape[1] + 8 * Lmax) + 16
-            max_rows = max(1, int(torch.cuda.mem_get_info(dev)[0] // (2 * per_row)))
-        with RfSensSets(set_start, nout, samples, edges, code, drho_dvp, stream) as handle:
-            for lo, hi, prun in _p_runs(split_runs(set_start, max_rows), set_start, pz):
-                rows = _device.to_device(models[lo:hi], torch.float64, dev)
-                v = vpvs if vp is None else vp[lo:hi]
-                v = _device.to_device(np.broadcast_to(np.asarray(v, dtype=np.float64), (hi - lo,)).copy()
-                                      if not isinstance(v, torch.Tensor) else v, torch.float64, dev)
-                w = None if weights is None else _device.to_device(weights[lo:hi], torch.int32, dev)
-                vsn, zv, nl = df._layers(rows, dev)
-                dm, _ = layers_from_voronoi(vsn, zv, nl, v, df._OPEN_PRIORS, mantle=mantle, device=dev)
-                res = eng.rf_sensitivity(dm, p=None if p is None else float(prun))
-                q = (dm.VP / dm.VS).contiguous() if kind == 'vs_total' else None
-                handle.add(lo, dm, res['K'], res['rf'], q, w)
-            sums = handle.finish()
-    for z in range(Z):
-        results[z] = _rf_result(sums, z, taxis, samples, edges, kind)
-        if results[z] is None:
-            failed[z] = "empty selection: no models" if set_start[z] == set_start[z + 1] else _RF_EMPTY
-    sel.raise_first_failed(failed, strict, "set")
-    return sel.SetList(results, failed)
+
+    def runs(set_start, max_rows):
+        pz = np.broadcast_to(np.asarray(spec.p if p is None else p, dtype=np.float64), (set_start.size - 1,))
+        return _p_runs(split_runs(set_start, max_rows), set_start, pz)
+
+    def add(handle, eng, run, dm, q, w):
+        res = eng.rf_sensitivity(dm, p=None if p is None else float(run[2]))
+        handle.add(run[0], dm, res['K'], res['rf'], q, w)
+    return _summarize_sets(_Pass(check, lambda dev: ForwardEngine(rf=[spec], device=dev),
+                                 lambda eng, Lmax: 8 * (nout * 4 * Lmax + nout), runs,               # (K and the trace)
+                                 lambda set_start, stream: RfSensSets(set_start, nout, samples, edges, code, drho_dvp, stream),
+                                 add, lambda sums, z: _set_result(sums, z, {'t': taxis[samples], 'samples': samples.copy()},
+                                                                  edges, kind), _RF_EMPTY),
+                           models, set_start, vpvs, weights, kind, mantle, device, max_rows, strict)
 
 
 def rf_summarize(rfparams, models, vpvs, weights=None, dep_edges=None, kind='vs_total', ref='prf', t=None, every=1,
@@ -768,7 +754,7 @@ def pool_rf_sensitivity(pool, ref=None, dep_edges=None, kind='vs_total', t=None,
     return res
 
 
-class StationRfSensitivity(sel.StationResult):
+class StationRfSensitivity(_StationArrays):
     """StationPool.rf_sensitivity's result, every array in the pool's station order.
 
     names, failed    the stations; {station name: message} (such a station is NaN throughout)
@@ -779,18 +765,8 @@ class StationRfSensitivity(sel.StationResult):
     failed station), nmodels, nexcluded [nstations] (0 for a failed station)"""
 
     def __init__(self, names, results, failed, ref, t, samples, edges, kind, p):
-        sel.StationResult.__init__(self, names, failed)
-        self.stations = {n: r for n, r in zip(names, results) if r is not None}
-        self.ref, self.t, self.samples, self.edges, self.kind, self.p = ref, t, samples, edges, kind, p
-        Z, S, nb = len(results), t.size, edges.size - 1
-        for k in ('mean', 'std', 'min', 'max'):
-            setattr(self, k, np.full((Z, S, nb), np.nan))
-        self.halfspace_mean, self.halfspace_std = np.full((Z, S), np.nan), np.full((Z, S), np.nan)
-        self.nmodels, self.nexcluded = np.zeros(Z, dtype=np.int64), np.zeros(Z, dtype=np.int64)
-        for z, r in enumerate(results):
-            if r is not None:
-                for k in ('mean', 'std', 'min', 'max', 'halfspace_mean', 'halfspace_std', 'nmodels', 'nexcluded'):
-                    getattr(self, k)[z] = r[k]
+        self.t, self.samples, self.p = t, samples, p
+        _StationArrays.__init__(self, names, results, failed, ref, edges, kind, t.size, ())
 
 
 def stations_rf_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', t=None, every=1, selection='weighted',
@@ -805,13 +781,7 @@ def stations_rf_sensitivity(spool, ref=None, dep_edges=None, kind='vs_total', t=
     res = rf_summarize_sets(spec, pool.models[ci, ri], set_start, pool.vpvs[ci, ri].astype(np.float64), w.astype(np.int32),
                             edges, kind, spec.ref, t, every, pool.priors.get('mantle'), device, max_rows,
                             p=p if 'p' in spool.per_station else None, strict=False)
-    for z, msg in res.failed.items():
-        failed.setdefault(z, msg)
-    sel.raise_first_failed(failed, strict, "station", spool.names)
-    for z, r in enumerate(res):
-        if r is not None:
-            r['ref'] = spec.ref
-            r['chains'] = sel.station_chains(ci, set_start, z, c)
+    _finish_stations(spool, res, failed, strict, spec.ref, ci, set_start)
     taxis = rf_time_axis(spec)
     samples = rf_samples(taxis, t, every)
     return StationRfSensitivity(spool.names, res, failed, spec.ref, taxis[samples], samples, edges, kind, p)

@@ -179,3 +179,23 @@ def test_the_layout_at_the_limits(lib, rsim):
     assert_equal(got, twin(rsim, host(c), [0, 3], samples, edges, 'vs_total', Lmax=Lmax, nout=nout))
     assert got['total'][0] == 6 and got['excluded'][0] == 0
     assert np.isfinite(got['s1']).all() and (got['vmin'] <= got['vmax']).all() and got['s2'][0, :, :800].any()
+
+
+def test_a_call_of_more_blocks_than_the_slab_holds(lib, rsim):
+    """All 60 samples x 1025 cells are 61 500 items a block, so the slab of 64 MiB holds 34 blocks; 33 sets of one row
+    and one of 300 rows are 35.  The second chunk is the last set's second block: it takes up the set's sums where the
+    first chunk left them."""
+    nout, Lmax, sizes = 60, 8, [1] * 33 + [300]
+    edges = np.linspace(0., 128., 1025)
+    assert len(sizes) + 1 == 35 > (64 << 20) // (nout * edges.size * 32)
+    rs = np.random.RandomState(79)
+    R = sum(sizes)
+    c = dict(nlay=rs.randint(2, Lmax + 1, R).astype(np.int32), h=rs.uniform(0.2, 9., (R, Lmax + 3)),
+             q=rs.uniform(1.6, 1.95, (R, Lmax + 2)), K=rs.standard_normal((R, nout * 4 * Lmax)),
+             rf=rs.standard_normal((R, nout + 1)), w=rs.randint(1, 4, R).astype(np.int32))
+    c['nlay'][[7, 300]] = 1, Lmax + 1                       # no model: a one-row set, and a row of the last set's second block
+    start = np.concatenate(([0], np.cumsum(sizes)))
+    got = device(c, start, None, edges, 'vs_total', nout=nout)
+    assert_equal(got, twin(rsim, host(c), start, None, edges, 'vs_total', nout=nout))
+    assert got['excluded'][7] == c['w'][7] and got['excluded'][33] == c['w'][300] and not got['total'][7]
+    assert got['total'][33] == c['w'][33:].sum() - c['w'][300]

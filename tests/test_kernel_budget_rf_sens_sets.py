@@ -2,8 +2,9 @@
 most 128 VGPRs, and the static LDS together with the most a launch adds within a workgroup's 64 KiB.
 
 As built: rf_sens_sets_kernel 89 VGPRs with four samples a thread (with eight it took 166, and spilled under the bound of
-128), rf_sens_sets_fold_kernel 22, rf_sens_sets_init_kernel 8; no static LDS; the launch adds h, the tops, G[Lmax][16]
-and the tile's 16 sample offsets: 1 216 B at Lmax = 8, 14 464 B at Lmax = 100, whatever the samples and the bins."""
+128), and sens_sets_host.h's sens_sets_fold_kernel 22 and sens_sets_init_kernel 8; no static LDS; the launch adds h, the
+tops, G[Lmax][16] and the tile's 16 sample offsets: 1 216 B at Lmax = 8, 14 464 B at Lmax = 100, whatever the samples and
+the bins."""
 import os
 import sys
 
@@ -20,7 +21,7 @@ def test_rf_sens_sets_kernels_use_no_scratch_and_fit_the_lds():
     rsim = load_sim()
     r = kernel_resources('rf_sens_sets.hip')
     main = {k: v for k, v in r.items() if 'rf_sens_sets_kernel' in k}
-    fold = {k: v for k, v in r.items() if 'rf_sens_sets_fold_kernel' in k}
+    fold = {k: v for k, v in r.items() if 'sens_sets_fold_kernel' in k}
     assert len(main) == 1 and len(fold) == 1, sorted(r)
     for k, v in r.items():
         print('%-60s %3d VGPRs  %3d SGPRs  LDS %d B' % (k, v['vgpr'], v['sgpr'], v['lds']))

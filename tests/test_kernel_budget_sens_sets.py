@@ -1,9 +1,10 @@
 """Resources of the kernels of sens_sets.hip, read from the cross-compiled kernel descriptors (no GPU): no scratch, at
 most 128 VGPRs, and the static LDS together with the most a launch adds within a workgroup's 64 KiB.
 
-As built: sens_sets_kernel 52 VGPRs, sens_sets_fold_kernel 22, sens_sets_init_kernel 8; no static LDS; the launch adds
-sens_sets_lds_doubles: 488 B at (Lmax, nper, nb) = (8, 5, 20), 3 216 B at (100, 60, 1024), 824 B at (20, 21, 200), and
-at its most -- few cells a period, so that a workgroup's 256 items touch every period -- 50 080 B at (100, 60, 1)."""
+As built: sens_sets_kernel 52 VGPRs, and sens_sets_host.h's sens_sets_fold_kernel 22 and sens_sets_init_kernel 8; no
+static LDS; the launch adds sens_sets_lds_doubles: 488 B at (Lmax, nper, nb) = (8, 5, 20), 3 216 B at (100, 60, 1024),
+824 B at (20, 21, 200), and at its most -- few cells a period, so that a workgroup's 256 items touch every period --
+50 080 B at (100, 60, 1)."""
 import os
 import sys
 
